@@ -12,9 +12,15 @@ scaling: per-GPU work fixed), issued by the library itself (avm_gather_states, r
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement), with
   roofline     : FP64 FLOP model of the window-solve kernel / its HIP-event duration vs the
                  78.6 TFLOP/s FP64 peak (vector == matrix rate on MI355X); model in DESIGN.md
+and, with --full only (a plain run sets up, warms up, times the steps and prints the line):
   cpu_baseline : the CPU oracle ("port" of the reference algorithm, compiled -O3 -march=native on this host)
                  timed on the host cores this process may use: median of >= 5 passes, 1 core and all cores
   feature_select: ms/frame + its own roofline and CPU baseline
+  sub-records  : ragged tracks, MARGIN_SECOND_NEW, the extended problem, single-window and host-call latency,
+                 the FP64 peak re-measured by scripts/ubench/peak
+
+--dump-outputs DIR writes what the last timed step handed back (solved states, summaries, the new prior) as
+DIR/<name>.npy; the inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -333,6 +339,65 @@ def launch_check(rank, world):
                           "self_launched": bool(os.environ.get("AVM_BENCH_SELF_LAUNCHED"))}))
 
 
+DUMP_SEED = 0
+DUMP_ROWS_BYTES = 36_000_000      # the solved states, the summaries and the prior's small members
+DUMP_PRIOR_J_BYTES = 20_000_000   # the prior's 96 x 96 factor (74 KB a window): at most 256 windows of it
+DUMP_GATHERED_BYTES = 4_000_000   # N > 1: the all-gathered poses
+
+
+def _dump_rows(n, keep, seed):
+    """Row indices 0..n-1, or a sorted sample of `keep` of them drawn with a fixed seed when keep < n."""
+    import numpy as np
+
+    if keep >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, max(int(keep), 1), replace=False))
+
+
+def _dump_take(x, rows):
+    """x[rows] of a device tensor (indexed on the device) as a float64 host array."""
+    import numpy as np
+    import torch
+
+    return np.ascontiguousarray(x[torch.as_tensor(rows, device=x.device)].cpu().numpy(), dtype=np.float64)
+
+
+def dump_outputs(d, win, summ, prior, gathered):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as d/<name>.npy (float64, under 64 MB in all):
+    the solved states (pose, speedbias, ex_pose, inv_depth), every field of the per-window summaries (summary_<field>), the new
+    prior when the marginalization runs (prior_<member>) and, with N > 1, the all-gathered poses (pose_gathered).  The inputs
+    depend only on the arguments.  A batch too large for the budget is written for a seeded sample of its windows, listed in
+    windows.npy; prior_J is always such a sample (prior_J_windows.npy), pose_gathered when it is large (pose_gathered_rows.npy)."""
+    import numpy as np
+
+    buffers = importlib.import_module(PKG + ".buffers")
+    os.makedirs(d, exist_ok=True)
+    W = win.n_windows
+    full = np.arange(W)
+    out = {k: _dump_take(win.a[k], full) for k in ("pose", "speedbias", "ex_pose", "inv_depth")}
+    s = buffers.summary_to_numpy(summ)
+    for f in s.dtype.names:
+        out["summary_" + f] = np.ascontiguousarray(s[f], dtype=np.float64)
+    if prior is not None:
+        out.update({"prior_" + k: _dump_take(v, full) for k, v in prior.a.items() if k != "J"})
+    rows = _dump_rows(W, DUMP_ROWS_BYTES // sum(v[0].nbytes for v in out.values()), DUMP_SEED)
+    if len(rows) < W:
+        out = {k: v[rows] for k, v in out.items()}
+        out["windows"] = rows.astype(np.float64)
+    if prior is not None:
+        J = prior.a["J"]
+        jr = _dump_rows(W, min(256, DUMP_PRIOR_J_BYTES // (J[0].numel() * 8)), DUMP_SEED + 1)
+        out["prior_J"] = _dump_take(J, jr)
+        out["prior_J_windows"] = jr.astype(np.float64)
+    if gathered is not None:
+        gr = _dump_rows(gathered.shape[0], DUMP_GATHERED_BYTES // (gathered[0].numel() * 8), DUMP_SEED + 2)
+        out["pose_gathered"] = _dump_take(gathered, gr)
+        if len(gr) < gathered.shape[0]:
+            out["pose_gathered_rows"] = gr.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -352,7 +417,12 @@ def main():
                     "device (LOCAL_RANK modulo the visible devices) and the poses are gathered through the host - for exercising the N > 1 path "
                     "end to end on a box with fewer GPUs than ranks (RCCL refuses two ranks on one device); never the configuration to quote")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous of the N ranks on gloo and exit, before HIP is initialised")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the sub-records, the feature "
+                    "selector, the CPU baseline and the FP64 peak (the --no-* options thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus, sys.argv[1:])  # never returns
@@ -381,7 +451,7 @@ def main():
     base = synth.make_windows_parallel(n_distinct, first_id=rank * W, tracks=args.tracks, procs=args.gen_procs or max(1, min(64, ncpu // max(world, 1))))
     host = base if n_distinct == W else synth.tile_windows(base, W)
     t_gen = time.perf_counter() - t_gen
-    extras = world == 1 and not args.no_extras and not args.launch_check
+    extras = world == 1 and args.full and not args.no_extras and not args.launch_check
     sparse_base = None
     if extras and args.tracks == "dense":
         # the ragged-track sub-record (a quarter of the batch generated, tiled: it is a sub-record, the headline batch is all distinct)
@@ -516,6 +586,8 @@ def main():
         allr = allr.view(world, 2)
         per_rank_solve_ms = [float(x) for x in allr[:, 0].cpu()]
         per_rank_gather_ms = [float(x) for x in allr[:, 1].cpu()] if use_lib_gather else None
+    if args.dump_outputs and rank == 0:  # (before the --full records, which reuse the prior's slots)
+        dump_outputs(args.dump_outputs, win, summ, prior_slots, gathered)
 
     result = None
     if rank == 0:
@@ -544,11 +616,11 @@ def main():
             traffic_src = (f"profiles/{prof_name}: (2*FETCH_SIZE + WRITE_SIZE) KB per launch, separate --pmc passes; mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / "
                            "(dispatch ns x 2.4 GHz x 1024 SIMDs); measured on the kernel sources this run was built from (sha256 checked)")
         alg_bytes = W * (44.0 * n_fac + 23.0e3 + 45.6e3 + 3.0e3 + 2.6e3)  # ~140 KB / solve at K=1500
-        # the FP64 peak of THIS device, re-measured in the run when the micro-benchmark is built (scripts/ubench/peak, made by
+        # the FP64 peak of THIS device, re-measured in a --full run when the micro-benchmark is built (scripts/ubench/peak, made by
         # __graft_entry__.build()); else the committed measurement of round 2
         peak_meas = None
         pk = os.path.join(ROOT, "scripts", "ubench", "peak")
-        if os.path.exists(pk) and not args.no_extras:
+        if os.path.exists(pk) and args.full and not args.no_extras:
             try:
                 out = subprocess.run([pk], capture_output=True, text=True, timeout=120).stdout
                 peak_meas = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
@@ -747,7 +819,7 @@ def main():
 
     # ---- feature selector: ms/frame (batch throughput), single-frame latency, FLOP/s of the scoring loop
     fsel_host = None
-    if not args.no_fsel:
+    if args.full and not args.no_fsel:
         FS = fs_m.FeatureSelector(ctx=ctx)
         P = args.fsel_problems
         fsel_host = synth.make_fsel(P, first_id=rank * P)
@@ -907,7 +979,7 @@ def main():
                 del f13b
 
     # ---- CPU baseline (oracle = port of the reference algorithm), rank 0, N=1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle_py
 
         build = native_oracle()

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-fsel --distinct 256 2>/dev/null | python -c "
+python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-fsel --distinct 256 2>/dev/null | python -c "
 import sys,json
 j=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print({k: round(v,3) for k,v in j['kernel_ms'].items()}, 'ragged', j['sparse_tracks']['kernel_ms'], j['sparse_tracks']['prior_square_roots'])"

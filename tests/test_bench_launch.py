@@ -122,3 +122,75 @@ def test_the_committed_rocprof_summary_belongs_to_the_kernel_sources_in_the_tree
     assert err is None, err
     sk = "window_solve_tp_kernel" if "window_solve_tp_kernel" in prof else "window_solve_kernel"  # (the form a 4096-window batch takes)
     assert prof[sk]["traffic_bytes_per_launch"] > 0 and 0 < prof[sk]["mfma_util"] < 1
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+@pytest.mark.parametrize("n_windows", [4096, 32768])
+def test_dump_outputs_stay_within_64_mb_and_sample_the_same_windows_every_time(tmp_path, n_windows):
+    """--dump-outputs at the headline batch (4096 windows: every state, a 256-window sample of the prior's factor) and at a batch too large
+    to write whole (a seeded window sample, listed in windows.npy): float64 files, at most 64 MB in all, the same rows on every call.
+    The batch is one generated window broadcast to n_windows rows on the CPU (the function only indexes it)."""
+    import torch
+
+    from helpers import buffers, synth
+
+    b = _bench_module()
+    w1 = synth.make_windows(1)
+    win = buffers.WindowArrays(dict(w1.dims, n_windows=n_windows),
+                               {k: torch.from_numpy(v).expand(n_windows, *v.shape[1:]) for k, v in w1.a.items()})
+    prior = buffers.PriorOutArrays.alloc(1, w1.dims["max_prior"], w1.dims["max_pblk"])
+    prior = buffers.PriorOutArrays(prior.dims, {k: torch.from_numpy(v).expand(n_windows, *v.shape[1:]) for k, v in prior.a.items()})
+    summ = buffers.summary_alloc(n_windows, "cpu")
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        b.dump_outputs(str(d), win, summ, prior, None)
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert files == sorted(p.name for p in dirs[1].iterdir())
+    assert sum(p.stat().st_size for p in dirs[0].iterdir()) <= 64_000_000
+    got = {f[:-4]: np.load(dirs[0] / f) for f in files}
+    assert all(v.dtype == np.float64 for v in got.values())
+    for f in files:
+        assert np.array_equal(got[f[:-4]], np.load(dirs[1] / f)), f
+    rows = n_windows if n_windows == 4096 else len(got["windows"])
+    assert "windows" not in got if n_windows == 4096 else 0 < rows < n_windows
+    assert got["pose"].shape == (rows, 11, 7) and got["summary_final_cost"].shape == (rows,) and got["prior_r"].shape[0] == rows
+    assert got["prior_J"].shape == (256, w1.dims["max_prior"], w1.dims["max_prior"]) and len(np.unique(got["prior_J_windows"])) == 256
+    assert np.array_equal(got["pose"], np.broadcast_to(w1.a["pose"], got["pose"].shape))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_what_it_solved(tmp_path):
+    """`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` (no --full): the line says how many steps were timed and what one
+    took, carries none of the --full records, and DIR holds the solved batch - the same states the CPU oracle reaches from the same
+    inputs, which depend only on the arguments."""
+    import oracle_py
+
+    from helpers import abi, buffers, rel, synth
+
+    W = 32
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--windows", str(W), "--gen-procs", "1",
+                        "--dump-outputs", str(d)], env=_clean_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _json_line(r.stdout)
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["unit"] == "solves/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert not {"cpu_baseline", "feature_select", "sparse_tracks", "latency_single_window_ms", "latency_host_call_ms"} & set(j)
+    w = synth.make_windows(W, first_id=0, tracks="dense")
+    opt = abi.default_options()
+    po, so = buffers.PriorOutArrays.alloc(W), buffers.summary_alloc(W)
+    oracle_py.window_solve(opt, w, po, so)
+    for k in ("pose", "speedbias", "inv_depth"):
+        g = np.load(d / f"{k}.npy")
+        assert g.dtype == np.float64 and g.shape == w.a[k].shape
+        assert rel(g, w.a[k]) < 1e-6, (k, rel(g, w.a[k]))
+    assert np.array_equal(np.load(d / "summary_num_iterations.npy"), so["num_iterations"].astype(np.float64))
+    assert np.array_equal(np.load(d / "prior_n.npy"), po.a["n"].astype(np.float64))
