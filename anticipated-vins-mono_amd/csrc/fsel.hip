@@ -885,35 +885,16 @@ AVM_DEV double fs_rowbcast_k(double v) {  // lane K of every 16-lane row -> the 
   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x150 + K, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
 }
-AVM_DEV double fs_rowbcast(double v, int k) {  // k is a compile-time constant at every call site (fully unrolled loops)
-  switch (k) {
-    case 0: return fs_rowbcast_k<0>(v);
-    case 1: return fs_rowbcast_k<1>(v);
-    case 2: return fs_rowbcast_k<2>(v);
-    case 3: return fs_rowbcast_k<3>(v);
-    case 4: return fs_rowbcast_k<4>(v);
-    case 5: return fs_rowbcast_k<5>(v);
-    case 6: return fs_rowbcast_k<6>(v);
-    case 7: return fs_rowbcast_k<7>(v);
-    case 8: return fs_rowbcast_k<8>(v);
-    case 9: return fs_rowbcast_k<9>(v);
-    case 10: return fs_rowbcast_k<10>(v);
-    case 11: return fs_rowbcast_k<11>(v);
-    case 12: return fs_rowbcast_k<12>(v);
-    case 13: return fs_rowbcast_k<13>(v);
-    case 14: return fs_rowbcast_k<14>(v);
-    default: return fs_rowbcast_k<15>(v);
-  }
-}
 
 // acc += (lane k of src's 16-lane row) * nmul in ONE instruction: v_fmac_f64_dpp with row_newbcast (the FP64 ALU of gfx90a+ takes a DPP operand
-// of that one kind).  Round 6, scripts/ubench/dpp2.hip: 5.8 cycles an issue against 4.8 for a plain v_fmac_f64 - and it does accumulate; the round-3
-// probe (scripts/ubench/dpp.hip: "assembles but does not accumulate") issued it right behind the VALU write of its source, and a DPP read needs two wait
-// states there which the compiler's hazard recognizer does not add inside inline assembly.  The caller keeps those two wait states (fs_dpp_fence) between the
-// last write of any operand and the first instruction of a run; inside a run of these nothing reads what a neighbour writes.
-#ifndef FS_NO_FMAC_DPP
-#define FS_FMAC_DPP 1
-#endif
+// of that one kind).  Round 6, scripts/ubench/dpp2.hip: 5.8 cycles an issue against 4.8 for a plain v_fmac_f64.  (The pre-round-6 form - two 32-bit
+// DPP moves per (pivot, column) feeding a plain multiply-add per block row - was removed; commit 24fd667 is the last that has it.)
+// The wait-state rule: a DPP instruction reads its DPP source (its first source operand) correctly only if no VALU instruction has written that
+// VGPR within the two wait states before it (the round-3 probe, scripts/ubench/dpp.hip, broke it and read as "does not accumulate").  The
+// compiler's hazard recognizer does not look inside inline assembly, so the caller keeps those two wait states itself (fs_dpp_fence: s_nop 1)
+// between the last write of any operand and the first instruction of a run, and after the run before the next broadcast; inside a run nothing
+// reads what a neighbour writes.  The scheduler may still move independent instructions between a fence and its run:
+// tests/test_isa_dpp_hazards.py checks every DPP instruction of the compiled code object against the rule.
 AVM_DEV void fs_dpp_fence() { asm volatile("s_nop 1"); }
 template <int K>
 AVM_DEV void fs_fmac_bcast(double& acc, double src, double nmul) {
@@ -1304,7 +1285,6 @@ AVM_DEV bool fsel_logdet4(const double* sC, const double* sdpp, const double* D,
   FS_TK(1)
   double dkeep[NB];  // lane j keeps the pivot of row bj BS + j
   bool bad = false;
-#ifdef FS_FMAC_DPP
   // m[bi][gk] += A[gk][gj] * (-mult[bi]) with A[gk][gj] = lane k of m[bk][gj], taken by the multiply-add itself (fs_fmac_bcast): one instruction per
   // (pivot, column, block row) where it was two 32-bit DPP moves per (pivot, column) and a multiply-add per block row - the same product, the same rounding
   fs_sfor<NB>([&](auto BJ) {
@@ -1336,35 +1316,6 @@ AVM_DEV bool fsel_logdet4(const double* sC, const double* sdpp, const double* D,
       fs_dpp_fence();  // (the next pivot's broadcast reads an entry this run has written)
     });
   });
-#else
-#pragma unroll
-  for (int bj = 0; bj < NB; bj++) {
-    dkeep[bj] = 1.0;
-#pragma unroll
-    for (int j = 0; j < BS; j++) {
-      const int gj = bj * BS + j;
-      const double djj = fs_rowbcast(m[bj][gj], j);
-      if (!(djj > 0.0)) bad = true;
-      dkeep[bj] = (lane & 15) == j ? djj : dkeep[bj];
-      double y = __builtin_amdgcn_rcp(djj), e = fma(-djj, y, 1.0);
-      y = fma(y, e, y);
-      e = fma(-djj, y, 1.0);
-      y = fma(y, e, y);
-      double mult[NB];
-#pragma unroll
-      for (int bi = bj; bi < NB; bi++) mult[bi] = m[bi][gj] * y;
-#pragma unroll
-      for (int bk = bj; bk < NB; bk++)
-#pragma unroll
-        for (int k = (bk == bj ? j + 1 : 0); k < BS; k++) {
-          const int gk = bk * BS + k;
-          const double v = fs_rowbcast(m[bk][gj], k);  // A[gk][gj]
-#pragma unroll
-          for (int bi = bk; bi < NB; bi++) m[bi][gk] = fma(-mult[bi], v, m[bi][gk]);
-        }
-    }
-  }
-#endif
   FS_TK(2)
   // log(sqrt(d)): per lane over its block rows, then across the candidate's lanes
   double ldl = 0;
@@ -1393,151 +1344,6 @@ AVM_DEV double fsel_ub4(const double* sdpp, const double* dd, int stride, double
   return fs_row_sum((lane & 15) < BS ? ubl : 0.0);
 }
 
-
-AVM_DEV double fs_rsqrt(double x) {  // v_rsq_f64 + two Newton steps (about one ulp on normal positive numbers)
-  double y = __builtin_amdgcn_rsq(x);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  return y;
-}
-AVM_DEV void wave_lds_sync_fs() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---- the evaluation on the matrix cores (round 3) ------------------------------------------------------------------------------
-// logdet(C + pr D) of FOUR candidates per wavefront by a blocked Cholesky factorization with 4 x 4 tiles whose rank-4 updates run on
-// v_mfma_f64_4x4x4_4b: one instruction does four INDEPENDENT 4 x 4 x 4 products - one per candidate.  Operand layout (measured,
-// scripts/ubench/mfma4.hip): block b = (lane / 4) % 4 is a quad COLUMN of the wavefront, the k index is the 16-lane row:
-//     A[b][i][k] at lane 16 k + 4 b + i,   B[b][k][j] at lane 16 k + 4 b + j,   D[b][i][j] at lane 16 i + 4 b + j.
-// Candidate b's matrix is held as its UPPER tiles U[k][i] (k <= i) in the D layout, one double per lane and tile - lane (li = lane
-// / 16, lj = lane % 4) holds entry (4 k + li, 4 i + lj).  With that choice nothing is ever transposed or moved between lanes:
-//   step k:  L_kk L_kk^T = U[k][k]                     the 4 x 4 diagonal tile, gathered through LDS and factored REDUNDANTLY by the 16
-//                                                      lanes of the block (no broadcast inside the pivot chain)
-//            W_i = L_kk^-1 U[k][i]        (i > k)      one MFMA each: A = L_kk^-1 (every lane selects its entry), B = the tile as it is;
-//                                                      W_i = L_ik^T comes out in the D layout ...
-//            U[j][i] -= W_j^T W_i     (k < j <= i)     ... which is at once the A operand (read as the transpose) and the B operand
-//                                                      of the trailing update: one MFMA per tile, the tile itself the accumulator.
-// 36 tiles at 3 H = 30 (padded to 32 with an identity block: log 1 = 0), 28 + 84 MFMAs per evaluation at 17.7 cycles each
-// (scripts/ubench/mfma4_rate.hip) against 435 (pivot, column) pairs of two 32-bit DPP moves and one or two FP64 multiply-adds each
-// in the DPP formulation (fsel_logdet4 above, which stays in use where it is the faster one: see fsel_frame_kernel).
-// The logarithms are spread over the block's lanes like before (four per lane and evaluation): lane (li, lj) takes pivot lj of the
-// steps k = li (mod 4) and the diagonal entries 4 k + li of the Hadamard bound for k = lj (mod 4); the sums over the block's 16
-// lanes use the same order in every block, so candidates with bit-identical inputs get bit-identical values wherever they sit
-// (the std::map equal-key rule of sortedlogDetUB depends on that).
-// sC / sdpp: the frame's current reduced information and position diagonal (LDS); D, pr: THIS LANE'S candidate (uniform over the
-// block); gather: 64 doubles of LDS scratch per wavefront.  *ld_out = sum_j log(sqrt(d_j)), *ub_out = sum_i log((dpp + pr D)_ii),
-// valid in every lane of the block; returns false on a non-positive pivot (block-uniform).
-AVM_DEV double fs_blk_sum(double v) {  // sum over the 16 lanes {16 i + 4 b + j} of this lane's block, the same order in every lane
-  v += fs_dpp_d<0xB1>(v);                       // quad_perm [1,0,3,2]: j ^ 1
-  v += fs_dpp_d<0x4E>(v);                       // quad_perm [2,3,0,1]: j ^ 2
-  v += __shfl_xor(v, 16, 64);                   // li ^ 1
-  v += __shfl_xor(v, 32, 64);                   // li ^ 2
-  return v;
-}
-template <int T, bool PACKED>
-AVM_DEV bool fsel_logdet4m(const double* sC, const double* sdpp, const double* D, double pr, double* gather, double* ld_out, double* ub_out) {
-  constexpr int NT4 = (T + 3) / 4;
-  const int lane = threadIdx.x & 63, li = lane >> 4, lj = lane & 3, blk = (lane >> 2) & 3;
-  auto dget = [&](int R, int Cc) {  // D[R][Cc], symmetric; PACKED: the lower triangle, row R at R (R + 1) / 2
-    const int hi = max(R, Cc), lo = min(R, Cc);
-    return PACKED ? D[hi * (hi + 1) / 2 + lo] : D[hi * T + lo];
-  };
-  // ---- tiles
-  double U[NT4 * (NT4 + 1) / 2];
-#pragma unroll
-  for (int k = 0; k < NT4; k++)
-#pragma unroll
-    for (int i = k; i < NT4; i++) {
-      const int R = 4 * k + li, Cc = 4 * i + lj;
-      const bool in = R < T && Cc < T;
-      const int Rc = min(R, T - 1), Ccc = min(Cc, T - 1);
-      const double v = sC[Rc * T + Ccc] + pr * dget(Rc, Ccc);
-      U[k * NT4 - k * (k - 1) / 2 + (i - k)] = in ? v : (R == Cc ? 1.0 : 0.0);
-    }
-  // ---- Hadamard upper bound: this lane's diagonal entries 4 k + li, k = lj (mod 4)
-  double ubl = 0.0;
-#pragma unroll
-  for (int q = 0; q < (NT4 + 3) / 4; q++) {
-    const int r = 4 * (lj + 4 * q) + li;
-    const int rc = min(r, T - 1);
-    const double dv = sdpp[rc] + pr * dget(rc, rc);
-    ubl += (r < T && lj + 4 * q < NT4) ? fs_log(dv) : 0.0;
-  }
-  const double ubt = fs_blk_sum(ubl);
-  // ---- factorization
-  double pv[(NT4 + 3) / 4];  // the pivots this lane takes the logarithm of
-#pragma unroll
-  for (int q = 0; q < (NT4 + 3) / 4; q++) pv[q] = 1.0;
-  bool bad = false;
-  double* gb = gather + blk * 16;
-#pragma unroll
-  for (int k = 0; k < NT4; k++) {
-    const int dk = k * NT4 - k * (k - 1) / 2;  // U[k][k]
-    gb[li * 4 + lj] = U[dk];
-    wave_lds_sync_fs();
-    double a[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; r++)
-#pragma unroll
-      for (int c = 0; c <= r; c++) a[r][c] = gb[c * 4 + r];  // (the upper triangle holds the current values: entry (c, r), c <= r)
-    wave_lds_sync_fs();  // (the next step's writes wait for these reads)
-    // 4 x 4 Cholesky, replicated; pivots d_j, their reciprocal square roots, L, L^-1
-    double l[4][4], m[4][4], d[4], rs[4];
-    d[0] = a[0][0];
-    rs[0] = fs_rsqrt(d[0]);
-    l[1][0] = a[1][0] * rs[0], l[2][0] = a[2][0] * rs[0], l[3][0] = a[3][0] * rs[0];
-    d[1] = fma(-l[1][0], l[1][0], a[1][1]);
-    rs[1] = fs_rsqrt(d[1]);
-    l[2][1] = fma(-l[2][0], l[1][0], a[2][1]) * rs[1], l[3][1] = fma(-l[3][0], l[1][0], a[3][1]) * rs[1];
-    d[2] = fma(-l[2][1], l[2][1], fma(-l[2][0], l[2][0], a[2][2]));
-    rs[2] = fs_rsqrt(d[2]);
-    l[3][2] = fma(-l[3][1], l[2][1], fma(-l[3][0], l[2][0], a[3][2])) * rs[2];
-    d[3] = fma(-l[3][2], l[3][2], fma(-l[3][1], l[3][1], fma(-l[3][0], l[3][0], a[3][3])));
-    rs[3] = fs_rsqrt(d[3]);
-    bad |= !(d[0] > 0.0) || !(d[1] > 0.0) || !(d[2] > 0.0) || !(d[3] > 0.0);
-    m[0][0] = rs[0], m[1][1] = rs[1], m[2][2] = rs[2], m[3][3] = rs[3];
-    m[1][0] = -(l[1][0] * m[0][0]) * rs[1];
-    m[2][1] = -(l[2][1] * m[1][1]) * rs[2];
-    m[2][0] = -fma(l[2][1], m[1][0], l[2][0] * m[0][0]) * rs[2];
-    m[3][2] = -(l[3][2] * m[2][2]) * rs[3];
-    m[3][1] = -fma(l[3][2], m[2][1], l[3][1] * m[1][1]) * rs[3];
-    m[3][0] = -fma(l[3][2], m[2][0], fma(l[3][1], m[1][0], l[3][0] * m[0][0])) * rs[3];
-    // the pivot whose logarithm this lane takes: pivot lj of the steps k = li (mod 4)
-    {
-      const double dsel = lj == 0 ? d[0] : (lj == 1 ? d[1] : (lj == 2 ? d[2] : d[3]));
-      pv[k / 4] = (k & 3) == li ? dsel : pv[k / 4];
-    }
-    if (k + 1 < NT4) {
-      // A operand of W = L^-1 U: A[i'][k'] = (L^-1)[i'][k'] at lane 16 k' + 4 b + i', i.e. this lane needs (L^-1)[lj][li]
-      double asel = 0.0;
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int c = 0; c <= r; c++) asel = (lj == r && li == c) ? m[r][c] : asel;
-      double W[NT4];
-#pragma unroll
-      for (int i = k + 1; i < NT4; i++) W[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(asel, U[dk + (i - k)], 0.0, 0, 0, 0);
-#pragma unroll
-      for (int j = k + 1; j < NT4; j++) {
-        const double nw = -W[j];
-#pragma unroll
-        for (int i = j; i < NT4; i++) {
-          const int t_ji = j * NT4 - j * (j - 1) / 2 + (i - j);
-          U[t_ji] = __builtin_amdgcn_mfma_f64_4x4x4f64(nw, W[i], U[t_ji], 0, 0, 0);
-        }
-      }
-    }
-  }
-  // log(sqrt(d)): this lane's pivots, then across the block
-  double ldl = 0.0;
-#pragma unroll
-  for (int q = 0; q < (NT4 + 3) / 4; q++) ldl += (li + 4 * q < NT4 && pv[q] > 0.0) ? 0.5 * fs_log(pv[q]) : 0.0;
-  *ld_out = fs_blk_sum(ldl), *ub_out = ubt;
-  // (a non-positive pivot anywhere in the block's factorization: every lane of the block saw it)
-  return !bad;
-}
 
 // One greedy step of workgroup `bx` of problem p: settle round k - 1, evaluate round k.  Returns true when the problem is
 // finished (the same answer in every workgroup of the problem: it depends on the shared state only).
@@ -1699,21 +1505,9 @@ AVM_DEV void fsel_frame_body(const FselDev& A, int32_t* sync, int nslots, int te
   __shared__ double sC[T * T], sdpp[T];
   __shared__ int32_t s_alive[FS_FRAME_MAXC];
   extern __shared__ double s_delta[];
-  // Which evaluation: the matrix-core form (fsel_logdet4m) where the instruction issue rate is the limit - two teams per XCD, i.e. two
-  // wavefronts per SIMD, 3 H <= 32 - and the DPP form (fsel_logdet4) where a wavefront has its SIMD to itself and the evaluation's
-  // dependent chain is what counts (a single frame: 1.38 ms against 1.46) or where the 55 tiles of 3 H = 39 do not fit the registers
-  // next to everything else (90 spilled registers, 0.33 -> 0.37 ms per frame).  Measured: profiles/r03_experiments.md, 3.
-  // Round 6: with the broadcast folded into the multiply-add (fs_fmac_bcast) the DPP form issues 45 % fewer instructions and wins there too - 16 frames per
-  // call 0.140 -> 0.119 ms per frame, 32 frames 0.127 -> 0.104 - so the matrix-core form is only built on request (-DFS_MF).
-#ifdef FS_MF
-  constexpr bool MF = TPX == 2 && T <= 32;
-#else
-  constexpr bool MF = false;
-#endif
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int g = MF ? (lane >> 2) & 3 : lane >> 4;  // this lane's candidate slot: its MFMA block (quad column) / its 16-lane DPP row
-  const bool rec_lane = MF ? (lane & 0x33) == 0 : (lane & 15) == 0;  // one lane per candidate writes the records
-  __shared__ double s_gather[MF ? (FS_NT / 64) * 64 : 1];
+  const int g = lane >> 4;  // this lane's candidate slot: its 16-lane DPP row
+  const bool rec_lane = (lane & 15) == 0;  // one lane per candidate writes the records
   int bx = blockIdx.x, team = 0;
   if (TEAMS) {
     unsigned xcc;
@@ -1879,16 +1673,11 @@ AVM_DEV void fsel_frame_body(const FselDev& A, int32_t* sync, int nslots, int te
       const bool live = l < nc && s_alive[min(l, FS_FRAME_MAXC - 1)] != 0;
       if (__any(live)) {
         double ld, ubt;
-        bool ok;
-        if constexpr (MF) {
-          ok = fsel_logdet4m<T, PACKD>(sC, sdpp, D, pr, s_gather + wv * 64, &ld, &ubt);
-        } else {
 #ifdef FS_TRACE_EVAL
-          ok = fsel_logdet4<T, BS, NB, true, PACKD>(sC, sdpp, D, pr, &ld, &ubt, tke);
+        const bool ok = fsel_logdet4<T, BS, NB, true, PACKD>(sC, sdpp, D, pr, &ld, &ubt, tke);
 #else
-          ok = fsel_logdet4<T, BS, NB, true, PACKD>(sC, sdpp, D, pr, &ld, &ubt);
+        const bool ok = fsel_logdet4<T, BS, NB, true, PACKD>(sC, sdpp, D, pr, &ld, &ubt);
 #endif
-        }
         if (live && rec_lane && l != test_drop) {  // (test_drop: a record that never arrives, tests only; -1 otherwise)
           fsel_rec_store<!TEAMS>(recF + (k & 1) * FS_FRAME_MAXC + l, ok ? (ld_nn + 2.0 * ld) : __builtin_nan(""), tag0 + k + 1);
           fsel_rec_store<!TEAMS>(recU + (k & 1) * FS_FRAME_MAXC + l, ub_nn + ubt, tag0 + k + 1);
@@ -1916,10 +1705,11 @@ AVM_DEV void fsel_frame_body(const FselDev& A, int32_t* sync, int nslots, int te
 #undef FS_SEG
 }
 
-// The kernel proper.  The instances that evaluate on the matrix cores (two teams per XCD, 3 H <= 32) are pinned to two wavefronts
-// per SIMD: left alone the allocator takes 334 registers for them, one wavefront per SIMD, and the second team of an XCD never
-// becomes resident (every launch then times out and falls back).  The DPP instances are left to the scheduler - the attribute
-// costs them 3-4 %.
+// The kernel proper.  fsel_frame_kernel_mf is the instance for two teams per XCD (3 H <= 30), pinned to the two wavefronts per SIMD that
+// two teams run at.  The pin came with the matrix-core evaluation (round 3: left alone the allocator took 334 registers for it, one
+// wavefront per SIMD, and the second team of an XCD never became resident); that form was removed after round 6 (commit 24fd667 is the
+// last that has it).  The instance keeps its name, which the profile records use, and its attribute, without which its code changes.
+// The instances with a SIMD per wavefront are left to the scheduler - the attribute costs them 3-4 %.
 template <int T, int BS, int NB, int TPX>
 __global__ __launch_bounds__(FS_NT) void fsel_frame_kernel(FselDev A, int32_t* sync, int nslots, int test_drop) {
   fsel_frame_body<T, BS, NB, TPX>(A, sync, nslots, test_drop);

@@ -348,13 +348,6 @@ AVM_DEV double fast_rsqrt(double x) {
   return y;
 }
 
-AVM_DEV double fast_rsqrt_pe(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  return y;
-}
-
 struct Frames {
   const double* R;  // [11][9]
   const double* A;  // [11][9]  ric^T * R_f^T
@@ -388,7 +381,7 @@ AVM_DEV double proj_eval(const double* x, Frames fr, const double* ric, const do
   const double sum = 1.0 + sn * c;
   const double rho0 = b * log(sum);
   // sqrt(max(DBL_MIN, 1 / sum)), Corrector's sqrt(rho'): 1.4916681462400413e-154 = sqrt(DBL_MIN)
-  const double srho = apply_loss ? fmax(fast_rsqrt_pe(sum), 1.4916681462400413e-154) : 1.0;
+  const double srho = apply_loss ? fmax(fast_rsqrt(sum), 1.4916681462400413e-154) : 1.0;
   r[0] = srho * r0;
   r[1] = srho * r1;
   if (WANT_J) {
@@ -2256,7 +2249,7 @@ AVM_DEV void tp_diag_chain(int nb, int patch, int buf, int stamp) {
   if (r < NB) {
     const double dc = lds[L_PATCH + patch * (16 * TP_PS) + min(r, nb - 1) * (TP_PS + 1)];
     if (!(dc > 0.0)) reinterpret_cast<int*>(lds + L_INT)[I_FAIL] = stamp;  // non-positive (or NaN) pivot in a pivot column of step stamp - 1
-    lds[L_LINV + buf * (16 * TP_PS) + r * TP_PS + 16] = fast_rsqrt_pe(dc);
+    lds[L_LINV + buf * (16 * TP_PS) + r * TP_PS + 16] = fast_rsqrt(dc);
   }
 #ifdef AVM_TP
   AVM_PRIO_BULK_CHOL();
@@ -2540,28 +2533,20 @@ AVM_NOINL bool chol_regs() {
         double colv[16];
 #pragma unroll
         for (int q = 0; q < 16; q++) colv[q] = lds[PB + q * TP_PS + rr];
-        const double isq = fast_rsqrt_pe(lds[PB + rr * (TP_PS + 1)]), di2 = isq * isq;
+        const double isq = fast_rsqrt(lds[PB + rr * (TP_PS + 1)]), di2 = isq * isq;
         bv *= isq;
 #pragma unroll
         for (int q = 0; q < 16; q++) colv[q] *= di2;
         double xout = 0.0;
-#ifndef AVM_BS_READLANE  // (round 6, last: 2 v_readlane_b32 + v_fma_f64 per step before - bit-identical, solve 9.29 -> 9.21 ms)
         // x_jj is lane jj's bv; every lane subtracts colv[jj] x_jj - the broadcast as the multiply-add's own DPP operand (v_fmac_f64_dpp row_newbcast: no trip
-        // through the scalar registers; the s_nop is the two wait states a DPP read needs behind the VALU write of the same register)
+        // through the scalar registers; the s_nop is the two wait states a DPP read needs behind the VALU write of the same register).  Round 6: bit-identical
+        // to the 2 v_readlane_b32 + v_fma_f64 per step it replaced, solve 9.29 -> 9.21 ms; commit 24fd667 is the last that has that form.
         tp_sfor<nb>([&](auto JR) {
           constexpr int jj = nb - 1 - JR;
           xout = lr == jj ? bv : xout;
           const double nc = -colv[jj];
           asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "+v"(bv) : "v"(nc), "n"(jj));
         });
-#else
-#pragma unroll
-        for (int jj = nb - 1; jj >= 0; jj--) {
-          const double xj = readlane_d(bv, jj);
-          bv = fma(-colv[jj], xj, bv);
-          xout = lane == jj ? xj : xout;
-        }
-#endif
         if (lane < nb) {
           lds[L_ZV + 16 * i + lane] = xout;
           const int col = tp_perm_dev(16 * i + lane);
@@ -3582,11 +3567,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
       ids[I_PSB] = psb_;
 #else
       // the rule of window_prior_tp_misfit (kernels.hpp): chol_regs' elimination order takes a prior whose only speed-bias block is frame 0's
-#ifdef AVM_NO_CR
-      ids[I_CRFIT] = 0;
-#else
       ids[I_CRFIT] = (nsb_ <= 1 && sbfr_ == 0) ? 1 : 0;
-#endif
 #endif
     }
     for (int f = 1 + (t >> 6); f < NFR; f += NT / 64) {  // features observed in frame f (as imu_j), in feature order
@@ -4282,7 +4263,6 @@ static_assert(SPP + MASM * MXSTG <= 13778, "marg staging must not reach the ex_p
 #endif
 constexpr int PARTW = 146;  // aa 21 | g_a 6 | [ex td].pose0 42 | [ex td]^2 28 | g_[ex td] 7 | [ex td].pose_b 42
 constexpr int MNW = 73;     // columns of W = E^T F here: 66 pose | 6 ex_pose | 1 td
-constexpr int MWS = 80;     // row stride of W[e][.]
 }  // namespace mg
 
 // column of the joint system for W column c (0..71): poses, then ex_pose
@@ -4435,7 +4415,7 @@ AVM_NOINL void marg_feature_sums(int nf0) {
   // densely to the threads; the structural zeros of the frames that do not observe it follow in a loop of their own
   for (int idx = t; idx < nf0 * 2; idx += NT) {
     const int e = idx >> 1, f = (idx & 1) ? 11 : 0;
-    const int no = ids[I_FNOBS + e], s0 = ids[I_FOBS + e];
+    const int no = ids[I_FNOBS + e];
     {
       const double* P = f == 0 ? PF : PF2;
       // all loads of the feature's (<= 10) factors in flight at once, clamped to its last observation and masked
