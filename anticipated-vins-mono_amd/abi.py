@@ -10,6 +10,9 @@ import numpy as np
 WINDOW_SIZE = 10
 NFRAMES = WINDOW_SIZE + 1
 MAX_ITER_TRACE = 16
+# table limits of an avm_window_batch (include/avm.h): the solve's, and the per-feature entry points' around it
+MAX_FEAT, MAX_FEAT_WIDE = 150, 384
+MAX_OBS, MAX_OBS_WIDE = MAX_FEAT * NFRAMES, MAX_FEAT_WIDE * NFRAMES
 
 AVM_OK = 0
 AVM_MEM_HOST, AVM_MEM_DEVICE = 0, 1

@@ -269,7 +269,18 @@ int ensure_window_buffers(avm_ctx* c, int n_windows, bool tp = false) {
   return AVM_OK;
 }
 
-int check_window_batch(avm_ctx* c, const avm_options* opt, const avm_window_batch* b) {
+static_assert(MAXE == AVM_MAX_FEAT && MAXOBS == AVM_MAX_OBS, "avm.h states the solve kernels' limits");
+static_assert(AVM_MAX_FEAT_WIDE == 384 && AVM_MAX_OBS_WIDE == 4224, "the messages below name the limits");
+int check_wide_strides(avm_ctx* c, const avm_window_batch* b) {
+  if (b->max_feat > AVM_MAX_FEAT_WIDE) return fail(c, AVM_ERR_CAPACITY, "max_feat > 384 (AVM_MAX_FEAT_WIDE)");
+  if (b->max_obs > AVM_MAX_OBS_WIDE) return fail(c, AVM_ERR_CAPACITY, "max_obs > 4224 (AVM_MAX_OBS_WIDE)");
+  return AVM_OK;
+}
+
+// wide: the pre-integration (it reads no feature table) takes the strides the API accepts for a window, AVM_MAX_FEAT_WIDE /
+// AVM_MAX_OBS_WIDE - a contract of avm.h, no limit of its kernels; the solve's LDS carve - and the factor evaluation's, which
+// stages the inverse depths in the same state vector - holds AVM_MAX_FEAT / AVM_MAX_OBS (avm.h)
+int check_window_batch(avm_ctx* c, const avm_options* opt, const avm_window_batch* b, bool wide = false) {
   if (!opt || !b || b->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (opt->estimate_td && (!b->obs_vel_td || !b->td))
     return fail(c, AVM_ERR_INVALID, "estimate_td != 0 needs obs_vel_td (velocity, cur_td, uv.y per observation) and td");
@@ -277,8 +288,13 @@ int check_window_batch(avm_ctx* c, const avm_options* opt, const avm_window_batc
   if (b->relo_n && (!b->relo_feat || !b->relo_xy || !b->relo_pose))
     return fail(c, AVM_ERR_INVALID, "relo_n is set but relo_feat / relo_xy / relo_pose is NULL");
   if (b->failure_occur && !b->last_pose0) return fail(c, AVM_ERR_INVALID, "failure_occur is set but last_pose0 is NULL");
-  if (b->max_feat > MAXE) return fail(c, AVM_ERR_CAPACITY, "max_feat > 150");
-  if (b->max_obs > MAXOBS) return fail(c, AVM_ERR_CAPACITY, "max_obs > 1650");
+  if (wide) {
+    const int rc = check_wide_strides(c, b);
+    if (rc != AVM_OK) return rc;
+  } else {
+    if (b->max_feat > MAXE) return fail(c, AVM_ERR_CAPACITY, "max_feat > 150");
+    if (b->max_obs > MAXOBS) return fail(c, AVM_ERR_CAPACITY, "max_obs > 1650");
+  }
   if (b->max_prior > MAXPRIOR || b->max_pblk > MAXPBLK) return fail(c, AVM_ERR_CAPACITY, "prior larger than 96 / 16 blocks");
   if (opt->max_num_iterations > AVM_MAX_ITER_TRACE) return fail(c, AVM_ERR_CAPACITY, "max_num_iterations > 16");
   return AVM_OK;
@@ -749,7 +765,7 @@ int avm_imu_preintegrate_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, 
                                double* out_jacobian, double* out_covariance, double* out_sum_dt) {
   if (!c) return AVM_ERR_INVALID;
   (void)hipSetDevice(c->device);
-  int rc = check_window_batch(c, opt, batch);
+  int rc = check_window_batch(c, opt, batch, true);
   if (rc != AVM_OK) return rc;
   if (batch->n_windows == 0) return AVM_OK;
   if ((rc = validate_windows(c, mem, batch, CHK_IMU)) != AVM_OK) return rc;
@@ -826,6 +842,12 @@ int avm_debug_fsel_evaluations(avm_ctx* c, int64_t* out) {
   return AVM_OK;
 }
 
+// test hook (not in avm.h): the table sizes of avm.h as this library was compiled with them, for the ctypes mirror check
+int avm_debug_table_limits(int* out) {
+  out[0] = AVM_MAX_FEAT, out[1] = AVM_MAX_OBS, out[2] = AVM_MAX_FEAT_WIDE, out[3] = AVM_MAX_OBS_WIDE;
+  return 4;
+}
+
 // test hook (not in avm.h): sizeof of every ABI struct, for the ctypes mirror check
 int avm_debug_struct_sizes(int* out) {
   out[0] = (int)sizeof(avm_options), out[1] = (int)sizeof(avm_window_batch), out[2] = (int)sizeof(avm_prior_out);
@@ -845,8 +867,10 @@ int avm_triangulate_batch(avm_ctx* c, avm_mem mem, avm_window_batch* batch, doub
   if (!c) return AVM_ERR_INVALID;
   (void)hipSetDevice(c->device);
   if (!batch || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
-  if (batch->max_feat > MAXE) return fail(c, AVM_ERR_CAPACITY, "max_feat > 150");
-  if (batch->max_obs > MAXOBS) return fail(c, AVM_ERR_CAPACITY, "max_obs > 1650");
+  {
+    const int crc = check_wide_strides(c, batch);  // (the API's table contract: the kernel runs one thread per feature, any count)
+    if (crc != AVM_OK) return crc;
+  }
   if (batch->n_windows == 0) return AVM_OK;
   {
     const int vrc = validate_windows(c, mem, batch, CHK_TRACKS);

@@ -136,13 +136,24 @@ typedef struct avm_options {
                                                 also forces the eigen-decomposition path) */
 } avm_options;
 
+/* Table sizes of an avm_window_batch.  AVM_MAX_FEAT_WIDE / AVM_MAX_OBS_WIDE are the largest strides the API accepts for a
+ * window: avm_imu_preintegrate_batch and avm_triangulate_batch take them (their kernels hold nothing per feature on chip;
+ * the cap is this contract, not a kernel limit), larger strides get AVM_ERR_CAPACITY naming it.  avm_slide_window and
+ * avm_fsel_build_cloud take tables of any size.  AVM_MAX_FEAT / AVM_MAX_OBS are what the solve kernels are built for
+ * today: avm_window_solve_batch, avm_window_solve and avm_window_eval_factors keep the window's inverse depths in a compute
+ * unit's LDS and refuse larger strides with AVM_ERR_CAPACITY. */
+#define AVM_MAX_FEAT 150
+#define AVM_MAX_OBS (AVM_MAX_FEAT * AVM_NFRAMES)           /* 1650 */
+#define AVM_MAX_FEAT_WIDE 384
+#define AVM_MAX_OBS_WIDE (AVM_MAX_FEAT_WIDE * AVM_NFRAMES) /* 4224 */
+
 /* A batch of independent sliding windows, struct-of-arrays over the window index.
  * [B] = n_windows.  Strides are the max_* fields so that one batch can hold
  * ragged windows.  Maps the inputs of Estimator::optimization() (SURVEY §8 A1,A14). */
 typedef struct avm_window_batch {
   int32_t n_windows;
-  int32_t max_feat;  /* stride of per-feature arrays (>= max n_feat) */
-  int32_t max_obs;   /* stride of per-observation arrays (>= max total observations) */
+  int32_t max_feat;  /* stride of per-feature arrays (>= max n_feat); limits above */
+  int32_t max_obs;   /* stride of per-observation arrays (>= max total observations); limits above */
   int32_t max_samp;  /* stride of IMU sample arrays (>= max samples per interval) */
   int32_t max_prior; /* leading dimension of prior_J / prior_r (>= max prior_n) */
   int32_t max_pblk;  /* stride of prior block tables */

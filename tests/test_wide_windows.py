@@ -1,0 +1,208 @@
+"""Windows with more than 150 features (include/avm.h, AVM_MAX_FEAT_WIDE / AVM_MAX_OBS_WIDE).
+
+The reference keeps up to 1000 features per window and tracks 150 per image, so a window of eleven images can hold more
+than 150.  The steps of solveOdometry() around the solve that keep nothing per feature on chip -
+pre-integration and triangulation - take tables of up to 384 features / 4 224 observation slots; the window roll and the
+depth cloud take any size.  Each is checked against the CPU oracle on wide windows, and narrow content is checked to come
+out bit-identical whether it sits in narrow or in wide tables.
+"""
+import importlib
+
+import numpy as np
+import pytest
+
+from helpers import abi, buffers, rel, synth
+
+# (tracks, n_feat, max_feat): just over 150, a sequence-sized window, the widest tables
+WIDE = [("sparse", 151, 151), ("sparse", 300, 384), ("dense", 300, 300), ("dense", abi.MAX_FEAT_WIDE, abi.MAX_FEAT_WIDE)]
+
+
+def _est(ctx, **kw):
+    o = abi.default_options()
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return importlib.import_module("anticipated-vins-mono_amd.estimator").Estimator(ctx=ctx, options=o)
+
+
+def _err():
+    return importlib.import_module("anticipated-vins-mono_amd.lib").AvmError
+
+
+def _restride(w, max_feat, max_obs):
+    """The same windows in tables of other strides (the per-feature and per-observation arrays padded or cut)."""
+    a = {k: v.copy() for k, v in w.a.items()}
+    for k in ("inv_depth", "feat_start", "feat_nobs", "feat_obs_begin"):
+        v = np.ones((w.n_windows, max_feat), a[k].dtype) if k == "inv_depth" else np.zeros((w.n_windows, max_feat), a[k].dtype)
+        n = min(max_feat, a[k].shape[1])
+        v[:, :n] = a[k][:, :n]
+        a[k] = v
+    xy = np.zeros((w.n_windows, max_obs, 2))
+    n = min(max_obs, a["obs_xy"].shape[1])
+    xy[:, :n] = a["obs_xy"][:, :n]
+    a["obs_xy"] = xy
+    return buffers.WindowArrays(dict(w.dims, max_feat=max_feat, max_obs=max_obs), a)
+
+
+def test_table_limits_mirror_the_header():
+    """abi.py's table sizes against the values the library was compiled with from include/avm.h (no GPU needed)."""
+    import ctypes as C
+
+    L = importlib.import_module("anticipated-vins-mono_amd.lib").lib()
+    out = (C.c_int * 4)()
+    assert L.avm_debug_table_limits(out) == 4
+    assert list(out) == [abi.MAX_FEAT, abi.MAX_OBS, abi.MAX_FEAT_WIDE, abi.MAX_OBS_WIDE]
+    assert abi.MAX_OBS == abi.MAX_FEAT * abi.NFRAMES and abi.MAX_OBS_WIDE == abi.MAX_FEAT_WIDE * abi.NFRAMES
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tracks,nf,mf", WIDE)
+def test_triangulation_on_wide_windows_matches_oracle(ctx, oracle, tracks, nf, mf):
+    E = _est(ctx)
+    w = synth.make_windows(3, tracks=tracks, n_feat=nf, max_feat=mf)
+    assert w.dims["max_obs"] > abi.MAX_OBS or w.dims["max_feat"] > abi.MAX_FEAT
+    keep = w.a["inv_depth"].copy()
+    w.a["inv_depth"][:, ::2] = -1.0  # "no depth yet"
+    w.a["inv_depth"][0, 1] = 0.0
+    wg, wo = w.copy(), w.copy()
+    E.triangulate(wg, init_depth=5.0)
+    oracle.triangulate(wo, init_depth=5.0)
+    assert np.array_equal(wg.a["inv_depth"][:, 3::2], keep[:, 3::2])  # features with a depth are left alone
+    assert np.array_equal(wg.a["inv_depth"][:, nf:], w.a["inv_depth"][:, nf:])  # nothing past n_feat is written
+    for b in range(3):
+        assert (wg.a["inv_depth"][b, :nf] > 0).all()
+        assert rel(wg.a["inv_depth"][b, :nf], wo.a["inv_depth"][b, :nf]) < 1e-9
+    wd = w.to_device("cuda:0")
+    E.triangulate(wd, init_depth=5.0)
+    assert np.array_equal(wd.to_host().a["inv_depth"], wg.a["inv_depth"])
+
+
+@pytest.mark.gpu
+def test_preintegration_with_wide_tables_matches_oracle(ctx, oracle):
+    E = _est(ctx)
+    w = synth.make_windows(3, tracks="sparse", n_feat=300, max_feat=abi.MAX_FEAT_WIDE)
+    d, J, P, sd = E.preintegrate(w)
+    od, oJ, oP, osd, _ = oracle.preintegrate(E.options, w)
+    for a, b in ((d, od), (J, oJ), (P, oP), (sd, osd)):
+        assert rel(a, b) < 1e-12
+
+
+@pytest.mark.gpu
+def test_narrow_content_in_wide_tables_is_untouched(ctx):
+    """The same 150-feature windows in tables of the solve's strides and of the widest strides: every output is bit-identical."""
+    E = _est(ctx)
+    for tracks in ("sparse", "dense"):
+        n = synth.make_windows(3, tracks=tracks, n_feat=150, max_feat=150)
+        n.a["inv_depth"][:, ::3] = -1.0
+        wd = _restride(n, abi.MAX_FEAT_WIDE, abi.MAX_OBS_WIDE)
+        assert wd.dims["max_feat"] == 384 and wd.dims["max_obs"] == 4224
+        for x, y in zip(E.preintegrate(n), E.preintegrate(wd)):
+            assert np.array_equal(x, y)
+        tn, tw = n.copy(), wd.copy()
+        E.triangulate(tn, 5.0)
+        E.triangulate(tw, 5.0)
+        assert np.array_equal(tn.a["inv_depth"], tw.a["inv_depth"][:, :150])
+
+
+def _same_tables(g, o):
+    for k in ("pose", "speedbias", "n_feat", "imu_n", "imu_lin_ba", "imu_lin_bg"):
+        assert np.array_equal(g[k], o[k]), k
+    for b in range(len(g["n_feat"])):
+        n = g["n_feat"][b]
+        assert np.array_equal(g["feat_start"][b, :n], o["feat_start"][b, :n]) and np.array_equal(g["feat_nobs"][b, :n], o["feat_nobs"][b, :n])
+        assert n == 0 or rel(g["inv_depth"][b, :n], o["inv_depth"][b, :n]) < 1e-13
+        for e in range(n):
+            no, gb, ob = g["feat_nobs"][b, e], g["feat_obs_begin"][b, e], o["feat_obs_begin"][b, e]
+            assert np.array_equal(g["obs_xy"][b, gb:gb + no], o["obs_xy"][b, ob:ob + no]), (b, e)
+        for j in range(10):
+            m = g["imu_n"][b, j]
+            assert np.array_equal(g["imu_dt"][b, j, :m], o["imu_dt"][b, j, :m])
+            assert np.array_equal(g["imu_acc"][b, j, :m + 1], o["imu_acc"][b, j, :m + 1])
+            assert np.array_equal(g["imu_gyr"][b, j, :m + 1], o["imu_gyr"][b, j, :m + 1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flag,shift", [(abi.MARGIN_OLD, True), (abi.MARGIN_OLD, False), (abi.MARGIN_SECOND_NEW, True)])
+def test_window_roll_on_wide_windows_matches_oracle(ctx, oracle, flag, shift):
+    """avm_slide_window's one-lane compaction of the feature list on tables of 384 features, host and device resident."""
+    E = _est(ctx)
+    w = synth.make_windows(3, tracks="sparse", n_feat=abi.MAX_FEAT_WIDE, max_feat=abi.MAX_FEAT_WIDE, max_samp=40)
+    w.a["n_feat"][1] = 290
+    wo, wd = w.copy(), w.copy().to_device("cuda:0")
+    assert oracle.slide_window(wo, flag, shift, 5.0) == 0
+    E.slideWindow(w, flag, shift, 5.0)
+    E.slideWindow(wd, flag, shift, 5.0)
+    assert (wo.a["n_feat"] > abi.MAX_FEAT).all()
+    if flag == abi.MARGIN_OLD and shift:
+        assert wo.a["n_feat"].sum() < 384 + 290 + 384  # features left with one observation are erased: the list is compacted
+    _same_tables(w.a, wo.a)
+    _same_tables(wd.to_host().a, wo.a)
+
+
+@pytest.mark.gpu
+def test_depth_cloud_of_wide_windows_matches_oracle(selector, oracle):
+    B = 3
+    w = synth.make_windows(B, tracks="sparse", n_feat=300, max_feat=abi.MAX_FEAT_WIDE)
+    w.a["inv_depth"][:, 3::7] *= -1.0
+    rng = np.random.default_rng(5)
+    k1_pos = w.a["pose"][:, 10, :3] + 0.1 * rng.normal(size=(B, 3))
+    k1_quat = w.a["pose"][:, 10, 3:].copy()
+    for mc in (abi.MAX_FEAT_WIDE, 200):
+        n, xy, dep = selector.initKDTree(w, k1_pos, k1_quat, max_cloud=mc)
+        on, oxy, odep = oracle.fsel_build_cloud(w, k1_pos, k1_quat, max_cloud=mc)
+        assert np.array_equal(n, on) and n.min() > abi.MAX_FEAT
+        assert rel(xy, oxy) < 1e-13 and np.array_equal(dep, odep)
+
+
+def _roll_stream(seq, n_images, tri, roll):
+    """solveOdometry() without the solve over a wide stream: triangulate, roll (MARGIN_OLD, shift_depth), next image.
+    Yields each window after its triangulation."""
+    w, ids = seq.first_window()
+    w.a["inv_depth"][0, : int(w.a["n_feat"][0])] = -1.0
+    for k in range(n_images):
+        tri(w)
+        yield w
+        roll(w)
+        ids = seq.next_image(w, ids, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sid", [0, 3])
+def test_wide_stream_of_triangulations_and_rolls_matches_oracle(ctx, oracle, sid):
+    """The realistic generator's stream with the tracks it really has (synth.Sequence cuts them to max_feat, 150 by default):
+    twelve images of triangulation and window roll on device against the same chain through the oracle."""
+    E = _est(ctx)
+    mk = lambda: synth.Sequence(sid, n_frames=34, n_landmarks=600, max_feat=320)
+    gpu = _roll_stream(mk(), 12, lambda w: E.triangulate(w, 5.0), lambda w: E.slideWindow(w, abi.MARGIN_OLD, True, 5.0))
+    ora = _roll_stream(mk(), 12, lambda w: oracle.triangulate(w, 5.0), lambda w: oracle.slide_window(w, abi.MARGIN_OLD, True, 5.0))
+    widest = 0
+    for k, (wg, wo) in enumerate(zip(gpu, ora)):
+        n = int(wo.a["n_feat"][0])
+        widest = max(widest, n)
+        assert int(wg.a["n_feat"][0]) == n, k
+        for t in ("feat_start", "feat_nobs", "feat_obs_begin"):
+            assert np.array_equal(wg.a[t][0, :n], wo.a[t][0, :n]), (k, t)
+        assert np.array_equal(wg.a["obs_xy"], wo.a["obs_xy"]), k
+        assert (wg.a["inv_depth"][0, :n] > 0).all() and rel(wg.a["inv_depth"][0, :n], wo.a["inv_depth"][0, :n]) < 1e-9, k
+    assert widest > 200
+
+
+@pytest.mark.gpu
+def test_tables_over_the_wide_limits_are_refused_with_their_messages(ctx):
+    """Strides over AVM_MAX_FEAT_WIDE / AVM_MAX_OBS_WIDE: AVM_ERR_CAPACITY naming the limit, before any device work; at the limits
+    exactly: accepted."""
+    AvmError = _err()
+    E = _est(ctx)
+    w = synth.make_windows(1, tracks="sparse", n_feat=200, max_feat=200)
+    over_f = _restride(w, abi.MAX_FEAT_WIDE + 1, 2200)
+    over_o = _restride(w, 200, abi.MAX_OBS_WIDE + 1)
+    for ww, what in ((over_f, r"max_feat > 384 \(AVM_MAX_FEAT_WIDE\)"), (over_o, r"max_obs > 4224 \(AVM_MAX_OBS_WIDE\)")):
+        keep = ww.a["inv_depth"].copy()
+        keep[:, ::2] = ww.a["inv_depth"][:, ::2] = -1.0
+        with pytest.raises(AvmError, match=r"status -5: " + what):
+            E.triangulate(ww, 5.0)
+        assert np.array_equal(ww.a["inv_depth"], keep)  # nothing was triangulated
+        with pytest.raises(AvmError, match=r"status -5: " + what):
+            E.preintegrate(ww)
+    at = _restride(w, abi.MAX_FEAT_WIDE, abi.MAX_OBS_WIDE)
+    E.preintegrate(at)
+    E.triangulate(at, 5.0)
