@@ -161,6 +161,22 @@ __host__ __device__ inline int window_prior_tp_misfit(const avm_window_batch& B,
   return (nsb > 1 || later ? 1 : 0) | (late ? 2 : 0);
 }
 
+// Launch of a kernel whose dynamic LDS exceeds the default limit.  hipFuncAttributeMaxDynamicSharedMemorySize is set once per process
+// and kernel, by the first call: a function-local static per Kernel, initialised under the language's guard, so concurrent first calls from
+// two threads are safe.  A failed hipFuncSetAttribute is remembered and returned by every later call as well; it is not tried again.
+template <auto Kernel>
+hipError_t lds_attr_once(int lds_bytes) {
+  static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  return e;
+}
+template <auto Kernel, class... Args>
+hipError_t launch_lds(int grid, int block, int lds_bytes, hipStream_t stream, const Args&... args) {
+  const hipError_t e = lds_attr_once<Kernel>(lds_bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds_bytes, stream, args...);
+  return hipGetLastError();
+}
+
 // first_bad: TWO ints.  [0]: INT_MAX when every window / problem passes, else (index * 8 + rule) of the lowest failing index;
 // [1] (windows, with CHK_PRIOR): the OR of window_prior_tp_misfit() over the windows (left alone when every prior fits)
 hipError_t launch_validate_windows(const avm_window_batch& b, int what, int* first_bad, hipStream_t stream);

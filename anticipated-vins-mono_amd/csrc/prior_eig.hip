@@ -4,7 +4,7 @@
 //     linearized_jacobians = diag(sqrt(S))   V^T ,   linearized_residuals = diag(1/sqrt(S)) V^T b' ,
 // with S the eigenvalues clamped to 0 below eps (marginalization_factor.cpp:292-299).
 //
-// marginalize_kernel (window_solve.hip) leaves A' (lower triangle is read) in PO.J[w] and b' in PO.r[w]; this
+// marginalize_kernel (solve/marg_kernel.hpp) leaves A' (lower triangle is read) in PO.J[w] and b' in PO.r[w]; this
 // kernel overwrites both in place.  One 256-thread workgroup per window, 48 KB of LDS: three workgroups share a CU.
 //
 // Method (Veselic-Hari / Drmac): A' = G G^T by a diagonally pivoted Cholesky factorization, then ONE-SIDED Jacobi on
@@ -126,7 +126,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 //     transpose - so (like the selector's evaluation on the 4 x 4 x 4 form) nothing is transposed or moved between lanes:
 //   * block column k:  L_kk from the diagonal tile (through a 2 KB LDS patch into lane = row form: a 16-pivot chain of v_readlane
 //     broadcasts, with the rows of the identity riding along in lanes 16..31 and ending as L_kk^-T, the scheme of chol_diag_block in
-//     window_solve.hip);  W_i = L_kk^-1 U[k][i] (A operand = L_kk^-1 from LDS, B = the tile);  U[j][i] -= W_j^T W_i (both operands
+//     solve/cholesky_lds.hpp);  W_i = L_kk^-1 U[k][i] (A operand = L_kk^-1 from LDS, B = the tile);  U[j][i] -= W_j^T W_i (both operands
 //     straight from registers).  W_i = L_ik^T is block (k, i) of J = L^T: the factor is the output.
 //   * r0 = L^-1 b' by blocks (tile^T x vector products reduced over the four row groups, the diagonal solves through L_kk^-1).
 //   * certification with the EXPLICIT inverse (120 more MFMAs, column block by column block, only its norms are kept):
@@ -792,11 +792,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
   }
 }
 
+static bool print_occupancy() {
+  int nb = -1;
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(prior_eig_kernel), NT, P_END * 8);
+  fprintf(stderr, "[avm] prior_eig_kernel: %d workgroups / CU (LDS %d B)\n", nb, P_END * 8);
+  return true;
+}
+
 }  // namespace pe
 
 hipError_t launch_prior_eig(const avm_prior_out& po, int n_windows, double eps, double noise_rel, const double* scale, long long* prof, int* done,
                             hipStream_t stream) {
-  static bool attr_set = false;
   // AVM_PRIOR_LITERAL=1: the reference's square root, literally - the eigen-decomposition for every window and the clamp S > eps and
   // nothing else (as avm_options::marg_noise_rel = 0).  AVM_PRIOR_FORCE_EIG=1: the eigen-decomposition for every window, the clamp as
   // the options say (A/B tests of the two forms of the square root).  Read per call: the tests flip them inside one process.
@@ -805,24 +811,20 @@ hipError_t launch_prior_eig(const avm_prior_out& po, int n_windows, double eps, 
   const bool lit1 = lit && lit[0] == '1';
   const int literal = (lit1 || (fe && fe[0] == '1')) ? 1 : 0;
   if (lit1) noise_rel = 0.0;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pe::prior_eig_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, pe::P_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-    if (prof) {
-      int nb = -1;
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(pe::prior_eig_kernel), pe::NT, pe::P_END * 8);
-      fprintf(stderr, "[avm] prior_eig_kernel: %d workgroups / CU (LDS %d B)\n", nb, pe::P_END * 8);
-    }
+  // (the LDS attribute once per process, a failure to set it remembered: kernels.hpp; the occupancy query below needs it set)
+  const hipError_t e = lds_attr_once<pe::prior_eig_kernel>(pe::P_END * 8);
+  if (e != hipSuccess) return e;
+  if (prof) {
+    static const bool printed = pe::print_occupancy();  // (by the first profiled call)
+    (void)printed;
   }
   // the well-conditioned windows on one wavefront each; what that kernel leaves (done[w] == 0) goes through the pivoted path
   // (AVM_PRIOR_LITERAL=1 / AVM_PRIOR_FORCE_EIG=1 / AVM_PRIOR_NO_FAST=1: everything through the pivoted path, for A/B tests)
   const char* nf = getenv("AVM_PRIOR_NO_FAST");
   const bool fast = done && !literal && !(nf && nf[0] == '1');
   if (fast) hipLaunchKernelGGL(pe::prior_chol_kernel, dim3(n_windows), dim3(64), 0, stream, po, n_windows, eps, noise_rel, scale, done);
-  hipLaunchKernelGGL(pe::prior_eig_kernel, dim3(n_windows), dim3(pe::NT), pe::P_END * 8, stream, po, n_windows, eps, noise_rel, scale, prof, literal,
-                     fast ? (const int*)done : (const int*)nullptr);
-  return hipGetLastError();
+  return launch_lds<pe::prior_eig_kernel>(n_windows, pe::NT, pe::P_END * 8, stream, po, n_windows, eps, noise_rel, scale, prof, literal,
+                                          fast ? (const int*)done : (const int*)nullptr);
 }
 
 }  // namespace avm

@@ -18,6 +18,15 @@
 // streamed through a per-workgroup global scratch slot that stays L2 resident.
 // All arithmetic FP64.  Every reduction has a fixed order, so results are bit-reproducible
 // run to run and independent of how windows are sharded over ranks.
+//
+// csrc/Makefile compiles this file three ways:
+//   window_solve.o      latency build: 512 threads and the whole CU's LDS per window, the reference's default problem;
+//                       also marginalize_kernel and eval_factors_kernel
+//   window_solve_x.o    -DAVM_X, extended build: the same with ex_pose / td / relo_Pose as variables (178 x 178 system); the solve only
+//   window_solve_tp.o   -DAVM_TP, throughput build: 256 threads and <= 80 KB of LDS, two windows per CU; solve and marginalization
+// What all three share is here, with the differences inside a function under #ifdef AVM_X / AVM_TP.  A function or kernel that only
+// some builds have - the marginalization among them - is a file under solve/, behind a conditional include at its place in the
+// definition order (the compiler emits functions in that order); solve/layout.hpp has each build's map of LDS and the tuning constants.
 #include <cfloat>
 #include <utility>
 
@@ -54,208 +63,7 @@ AVM_DEV void lds_base_check() {
 #define PROFQ_T0() pq__ = clock64()
 #define PROFQ(c, k) do { if ((c).prof && threadIdx.x == 0) { long long n__ = clock64(); (c).prof[k] += n__ - pq__; pq__ = n__; } } while (0)
 
-#ifdef AVM_TP
-// THROUGHPUT build (window_solve_tp.o, -DAVM_TP): the same minimizer as a 256-thread workgroup (four wavefronts, one per SIMD) with at most
-// 80 KB of LDS, so that TWO windows are resident per CU and the dependent chains of one overlap the other's.  What makes it fit:
-//   * only the dense pose-pose rows of S (66 packed rows, 18 KB) stay in LDS as they are; the speed-bias rows are kept in their
-//     structural form (per 9-row block the 18 pose and 18 speed-bias columns an IMU factor can reach, plus the prior's speed-bias x pose
-//     strip), in the range the frame tasks' staging occupies during phase A;
-//   * the factorization runs on REGISTER tiles distributed over the four wavefronts (chol_regs below), fed from those two forms;
-//   * the frame tasks stage half a chunk (32 factors) at a time.
-constexpr int NT = 256;
-#else
-constexpr int NT = 512;          // threads per workgroup (8 wavefronts)
-#endif
-constexpr int croff(int i) { return 2 * ((i >> 1) + 1) * ((i >> 1) + (i & 1)); }  // roff() at compile time
-constexpr int SROWS = croff(NF + 1);  // padded packed lower triangle of the NF x NF matrix + one augmented row (the RHS): 13944 (16200)
-constexpr int VEC = (NCOL + 7) & ~7;  // padded NCOL: 320 (328)
-constexpr int XSB = 7 * NFRP, XLAM = XSB + 99;  // state vector: poses (relo_Pose as frame 11) | speedbias 99 | inv depth 150 [| ex_pose 7 | td]
-#ifdef AVM_X
-constexpr int XEX = XLAM + MAXE, XTD = XEX + 7;
-constexpr int XN = (XTD + 2) & ~1;  // 342
-#else
-constexpr int XN = XLAM + MAXE + 2;  // 328
-#endif
-
-// LDS carve (offsets in doubles).  Everything between L_S + SPP (end of the pose-pose rows of S) and
-// L_G is dead while the projection factors are being assembled, so that range doubles as the per-wave
-// staging area of the MFMA X^T X products (ASM_WAVES x XSTG doubles).
-constexpr int SPP = croff(NPOSE);  // packed rows 0..NPOSE-1 = the dense pose(-like) block: 2244 (3200)
-constexpr int WLD = 80;
-constexpr int XRS = 132;           // column stride of the frame tasks' column-major staging tile: 128 rows + 4 (bank spread)
-#ifdef AVM_X
-constexpr int WCH = 8;             // rows of the scratch tile at L_WCH (x 80 columns): diag-block temporaries, back-substitution vector
-constexpr int XCOLS = 20;          // staged factor row: Jj(6) | Ji(6) | r | Jex(6) | Jtd
-constexpr int XRS_X = 68;          // column stride of the HALF-chunk staging tile (round 5): 32 factors x 2 residual rows + 4 (bank spread)
-constexpr int XSTG = XCOLS * XRS_X;
-constexpr int ASM_WAVES = 7;       // wavefronts assembling projection factors (round 5: seven half-chunk tiles fit where five whole ones did; eleven
-                                   // frames deal 2 2 2 2 1 1 1 instead of 3 2 2 2 2, and wavefront 7 takes the raw IMU Jacobians AND the prior)
-#elif defined(AVM_TP)
-constexpr int XRS_H = 68;          // column stride of the HALF-chunk staging tile: 32 factors x 2 residual rows + 4 (bank spread)
-constexpr int XSTG = 13 * XRS_H;   // 884
-constexpr int ASM_WAVES = 4;       // every wavefront assembles; wavefront 2 then takes the raw IMU Jacobians, wavefront 3 the prior
-#else
-constexpr int WCH = 32;
-constexpr int XLD = 14;            // staged factor row: Jj(6) | Ji(6) | r (+1 pad)
-constexpr int XSTG = 128 * XLD;    // 64 factors x 2 residual rows (>= 13 * XRS)
-static_assert(13 * XRS <= XSTG, "column-major staging tile fits");
-constexpr int ASM_WAVES = 6;       // wavefronts assembling projection factors (wavefront 6: the raw IMU Jacobians, 7: the prior)
-#endif
-#ifndef AVM_LPT_RUNW
-#define AVM_LPT_RUNW 16
-#endif
-// positions of chol_regs' elimination order (see there): [0, 48) B, [48, 96) F, frame 5's speed-bias block, the dense columns, the right-hand side
-constexpr int TP_M0 = 96, TP_P0 = 105, TP_RHS = TP_P0 + NPOSE;  // 171 (184)
-constexpr int TPT = TP_RHS / 16 + 1;                            // tile columns: 11 (12)
-constexpr int TP_NPOS = 16 * TPT;                               // 176 (192)
-#ifdef AVM_X
-constexpr int TP_NWO = 8;          // wavefronts that hold tiles of the factorization
-#else
-constexpr int TP_NWO = 4;
-#endif
-constexpr int CNB = 16;            // Cholesky panel width (pivot chain per diagonal block); trailing tiles stay 16x16
-constexpr int TLAST = NF / 16;     // last 16-row tile of the packed matrix incl. the augmented row NF: 10 (11)
-constexpr int FRS = 18 * NFRP;     // one frames slot: R (NFRP x 9) then A = ric^T R^T (NFRP x 9)
-constexpr int L_S = 0;
-#ifdef AVM_TP
-// rows 0..65 of S packed as in the other builds, then the union region U: phase A: 4 staging tiles; from phase D on: the speed-bias
-// rows in structural form + the prior's strip; during the factorization: diagonal patch, L_kk^-T (two buffers), the published row of W
-constexpr int SBW = 36;                       // compact speed-bias row: 18 pose columns (poses i-1, i, i+1) | 18 speed-bias columns (i-1, i)
-constexpr int L_U = L_S + SPP;
-constexpr int L_SBC = L_U;                    // [99][SBW]
-constexpr int L_STRIP = L_SBC + 99 * SBW;     // [9][66]: rows of the prior's speed-bias block x every pose column
-constexpr int USZ = 99 * SBW + 9 * NPOSE + 2; // 4160; its last two doubles hold the constants 0.0 and 1.0 for chol_regs' tile load (set by schur_reduce)
-constexpr int L_ZERO = L_U + USZ - 2, L_ONE = L_U + USZ - 1;
-static_assert(ASM_WAVES * XSTG <= USZ, "staging fits the union region");
-constexpr int TP_PS = 17;                     // row stride of the 16 x 16 blocks below: lane = row accesses of a stride-16 block put sixteen lanes on two LDS banks
-constexpr int L_PATCH = L_U;                  // factorization: [2][16][TP_PS] diagonal blocks of the (up to two) pivot columns of a step in lane = row form
-constexpr int L_LINV = L_PATCH + 2 * 16 * TP_PS;  // [4][16][TP_PS]: L_kk^-T (unscaled, see chol_diag_block), 1 / sqrt(pivot) of column r in the padding word of row r (tp_buf)
-constexpr int TP_WSLOTS = 9;                  // tiles of a step's rows of W that exist beside the diagonal (tp_wslot: the factor is sparse in the order chol_regs eliminates in)
-constexpr int L_WROW = L_LINV + 4 * 16 * TP_PS;      // [TP_WSLOTS][256]: the step's rows of W, the tiles that exist in column order, in the accumulator layout [r][lane]
-constexpr int L_PARTV = L_WROW;               // back substitution (the rows of W are dead by then): [4][176] partial sums of the four wavefronts
-constexpr int L_ZV = L_WROW + TP_WSLOTS * 256;  // [176] z = L^-1 b, then x, in elimination order (lds[L_Y] keeps the right-hand side until x replaces it, in the system's order)
-static_assert(L_ZV + TP_NPOS <= L_ZERO && TP_NWO * TP_NPOS <= TP_WSLOTS * 256, "factorization scratch fits the union region");
-static_assert(ASM_WAVES * XSTG <= USZ - 2, "staging leaves the two constants alone");
-constexpr int L_Y = L_U + USZ;                // Gauss-Newton solution y; until the solve writes it: the right-hand side (row NF of the other builds)
-constexpr int L_RHS = L_Y;
-constexpr int WCH_TP = 224;                   // doubles: ys of back_substitute / rvb of jac_times_vec_sq (<= 150), then 64 dump slots
-constexpr int L_ST = L_Y + VEC;
-constexpr int L_XC = L_ST + VEC;
-constexpr int L_WCH = L_XC + XN;
-constexpr int L_DUMP = L_WCH + 160;
-constexpr int L_G = L_WCH + WCH_TP;
-constexpr int L_DD = L_G + VEC;               // (g / D is recomputed where it is needed, as in the extended build)
-// Per-wavefront accumulators of the two per-feature sums that end in LDS anyway (E^T E -> lds[L_HEE], E^T r -> lds[L_G + NF]), over the range the
-// Gauss-Newton step, the dogleg step and the candidate state occupy between evaluations (all three are dead or parked while eval_jac runs: the
-// minimizer recomputes them, and a speculative evaluation parks y in the slot).  Wavefront 0 accumulates in the destinations themselves, wavefronts
-// 1..3 in [3][2][152] here; the per-feature sums add the four in a fixed order.  Round 5: every 8 bytes per factor the frame tasks write to the slot
-// cost 0.1 ms per 4096 windows (profiles/r05e_experiments.md section 10); these two were sixteen of them.
-constexpr int L_ACC = L_Y, ACCW = 152;
-static_assert(L_ACC + 6 * ACCW <= L_WCH, "the accumulators stay inside y | step | candidate state");
-#else
-constexpr int L_Y = L_S + SROWS;   // Gauss-Newton solution y of (H + mu D^2) y = g
-constexpr int L_ST = L_Y + VEC;    // trust region step (scaled space)
-constexpr int L_XC = L_ST + VEC;   // candidate state
-constexpr int L_WCH = L_XC + XN;   // [WCH][80] scratch tile
-constexpr int L_DUMP = L_WCH + 512;     // per-lane dump slots of the masked-out stores
-constexpr int L_G = L_WCH + WCH * WLD;  // scaled gradient g (f | e)
-#endif
-#ifndef AVM_TP
-// Latency and extended builds: the factorization on register tiles (chol_regs, the throughput build's; latency: on wavefronts 0..3, extended: on all
-// eight) reads the packed system once; from then on the range of S is its scratch - same carve as the throughput build's union region, and the
-// right-hand side is row NF of S.
-constexpr int L_RHS = L_S + croff(NF);
-constexpr int TP_PS = 17;
-constexpr int L_PATCH = L_S;
-constexpr int L_LINV = L_PATCH + 2 * 16 * TP_PS;
-#ifdef AVM_X
-constexpr int TP_WSLOTS = 14;
-#else
-constexpr int TP_WSLOTS = 9;
-#endif
-constexpr int L_WROW = L_LINV + 4 * 16 * TP_PS;
-constexpr int L_PARTV = L_WROW;
-constexpr int L_ZV = L_WROW + TP_WSLOTS * 256;
-static_assert(L_ZV + TP_NPOS <= L_S + SROWS && TP_NWO * TP_NPOS <= TP_WSLOTS * 256, "factorization scratch fits the range of S");
-#endif
-#ifdef AVM_TP
-#elif defined(AVM_X)
-constexpr int L_DD = L_G + VEC;    // D   (g / D is recomputed where it is needed: no room for a fourth vector next to the 178 x 178 system)
-#else
-constexpr int L_DG = L_G + VEC;    // g / D
-constexpr int L_DD = L_DG + VEC;   // D
-#endif
-constexpr int L_SC = L_DD + VEC;   // Jacobi scaling
-constexpr int L_X = L_SC + VEC;
-constexpr int L_FR = L_X + XN;     // [2][FRS]
-#ifdef AVM_X
-constexpr int L_RIC = L_FR + 2 * FRS;  // [2][12]: ric 9, tic 3 of the current point / of the candidate
-constexpr int L_HEE = L_RIC + 24;      // E^T E (150) padded
-#else
-constexpr int L_RIC = L_FR + 2 * FRS;  // ric 9, tic 3, current ex_pose 7 (+1 pad)
-constexpr int L_HEE = L_RIC + 20;      // E^T E (150) padded
-#endif
-constexpr int L_DXP = L_HEE + 152;
-constexpr int L_RP = L_DXP + MAXPRIOR;
-#ifdef AVM_X
-constexpr int L_DX2 = L_DXP;       // (the extended build keeps the prior on one wavefront)
-constexpr int L_RED = L_RP + MAXPRIOR;
-#else
-constexpr int L_DX2 = L_RP + MAXPRIOR;  // dx / J0^T r_p of the second wavefront that shares the prior
-constexpr int L_RED = L_DX2 + MAXPRIOR;
-#endif
-constexpr int L_RED_B = L_RED + 16, L_RED_CNT = L_RED + 32;  // second value of a paired reduction; the wavefronts' reduction counters (8 ints)
-constexpr int L_INT = L_RED + 36;  // int region (as doubles): 360 doubles = 720 ints
-constexpr int L_SUM = L_INT + 360;  // cost_trace[16], radius_trace[16]
-constexpr int L_CTX = L_SUM + 32;   // WinCtx of the window being solved (32 doubles)
-constexpr int L_OPT = L_CTX + 32;   // avm_options (copied from the kernel arguments)
-constexpr int L_END = L_OPT + (int)((sizeof(avm_options) + 7) / 8);
-#ifdef AVM_TP
-static_assert(L_END * 8 <= 81920, "two workgroups per CU: 80 KB each");
-#else
-static_assert(L_END * 8 <= 163840, "LDS budget exceeded");
-#endif
-static_assert(L_S + SPP + ASM_WAVES * XSTG <= L_G, "assembly staging overlaps live data");
-// int carve (offsets in ints from L_INT)
-constexpr int I_FSTART = 0, I_FNOBS = 150, I_FOBS = 300, I_PIDX = 450, I_FS = 546, I_PBLK = 560 /* kind,frame,off x16 */, I_FAIL = 620,
-              I_NCOV = 624 /* [12] factors observed in frame b */, I_FRW = 636 /* [12] assembling wave of frame b */,
-              I_PMASK = 648 /* [12] start frames flushed by frame b */, I_TIMEUP = 660 /* max_solver_time reached (set by thread 0) */,
-              I_NRUN = 661 /* [12] distinct start frames among the factors observed in frame b */,
-              I_PSB = 673 /* throughput build: frame of the prior's speed-bias block (its rows x every pose column: the strip) */,
-              I_CNT = 674 /* wavefronts x rows of W published so far in this factorization (chol_regs) */,
-              I_CRFIT = 675 /* latency build: the window's prior fits the sparse factorization (chol_regs), else cholesky_lds */, I_END = 676;
-static_assert(I_END <= 720, "int carve");
-#ifndef AVM_TP
-constexpr int L_ZERO = L_INT + 340, L_ONE = L_INT + 341;  // the constants 0.0 and 1.0 of chol_regs' tile load, in the unused tail of the int carve (set by schur_reduce)
-static_assert(2 * 340 >= I_END, "the constants sit behind the int carve");
-#endif
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// Issue priority of the calling wavefront (throughput build only).  Two windows share every SIMD there, one wavefront each: while one
-// of them streams MFMAs / factor arithmetic (the frame tasks, the Schur tiles, the trailing updates of the factorization: AVM_PRIO_BULK)
-// and the other walks a dependent chain or one of the short barrier-separated vector phases of the trust-region loop (AVM_PRIO_LIGHT),
-// the arbiter should hand the next free issue slot to the latter - its instructions are the window's critical path, the bulk work
-// fills whatever is left.  (The pivot chains have run at priority 3 since round 4.)
-#ifdef AVM_TP
-#ifndef AVM_PRIO_L
-#define AVM_PRIO_L 2
-#endif
-#ifndef AVM_PRIO_CHOL
-#define AVM_PRIO_CHOL 1
-#endif
-#ifndef AVM_PRIO_SCHUR
-#define AVM_PRIO_SCHUR 1
-#endif
-#define AVM_PRIO_BULK() __builtin_amdgcn_s_setprio(0)
-#define AVM_PRIO_BULK_CHOL() __builtin_amdgcn_s_setprio(AVM_PRIO_CHOL)
-#define AVM_PRIO_BULK_SCHUR() __builtin_amdgcn_s_setprio(AVM_PRIO_SCHUR)
-#define AVM_PRIO_LIGHT() __builtin_amdgcn_s_setprio(AVM_PRIO_L)
-#else
-#define AVM_PRIO_BULK() ((void)0)
-#define AVM_PRIO_BULK_CHOL() ((void)0)
-#define AVM_PRIO_BULK_SCHUR() ((void)0)
-#define AVM_PRIO_LIGHT() ((void)0)
-#endif
+#include "solve/layout.hpp"
 
 AVM_DEV void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1230,178 +1038,7 @@ AVM_DEV double frame_task(const WinCtx&, const avm_options&, int wvi, int stage_
   return cost;
 }
 #else
-// The same task with every optional member of the problem: staged row [Jj | Ji | r | Jex | Jtd] (20 columns, two 16-wide
-// operand tiles), frame 11 = the relocalization frame (its "observations" are the match points, its pose relo_Pose).
-// X^T X now has three tiles: D00 = [Jj Ji r]^2 as before, D10 = [Jex Jtd]^T [Jj Ji r] and D11 = [Jex Jtd]^2.
-//   D00, per start-frame run a:  (b,a), (a,a) -> PART[b][a], g_a;        total: (b,b), g_b
-//   D10, per run:  [Jex Jtd]^T Ji -> PART[b][a][27..68];                 total: [Jex Jtd]^T Jj -> S rows 72..78 x cols 6b.. (owned by
-//        this frame), [Jex Jtd]^T r -> PARTX[b][28..34]
-//   D11, total: -> PARTX[b][0..27]
-// Members that are switched off (estimate_extrinsic / estimate_td == 0) stage exact zeros, so their blocks come out zero.
-AVM_DEV double frame_task(const WinCtx&, const avm_options&, int b, int stage_off) {
-  const WinCtx& c = lds_ctx();
-  const avm_options& o = lds_opt();
-  double* lds = LDS();
-  double* stage = lds + stage_off;
-  int* ids = reinterpret_cast<int*>(lds + L_INT);
-  const int lane = threadIdx.x & 63;
-  const int ncov = ids[I_NCOV + b];
-  const int32_t* cov = c.cov + b * MAXE;
-  Frames fr{lds + L_FR, lds + L_FR + 9 * NFRP};
-  const double* ric = ric_of(0);
-  const double* xs = lds + L_X;
-  const double sqi = o.focal_length / 1.5;
-  const bool relo = b == NFRP - 1;
-  const bool use_td = c.est_td && !relo;  // the relocalization factors are plain ProjectionFactors (estimator.cpp:783)
-  const double exm = c.est_ex ? 1.0 : 0.0;
-  const double td = xs[XTD];
-  double* W = c.sc + Scratch::W;
-  double* PF = c.sc + Scratch::PF;
-  double* PART = c.sc + Scratch::PART + (size_t)b * NFR * SPARTW;
-  double* PX = c.sc + Scratch::PART + PARTX0 + (size_t)b * PARTX;
-  const double* scl = lds + L_SC;
-  d4 Dtot = {0, 0, 0, 0}, D00 = {0, 0, 0, 0}, E00 = {0, 0, 0, 0}, D10 = {0, 0, 0, 0}, E10 = {0, 0, 0, 0}, D10tot = {0, 0, 0, 0},
-     D11 = {0, 0, 0, 0}, E11 = {0, 0, 0, 0};
-  int a_run = -1, pmask = 0;
-  double cost = 0;
-  const int drow = lane >> 4, dcol = lane & 15;
-  auto flush = [&]() {
-    if (a_run < 0) return;
-    D00 += E00, D10 += E10;
-    E00 = E10 = d4{0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int row = drow + 4 * r;
-      const double v = D00[r];
-      if (row < 6 && dcol >= 6 && dcol < 12) lds[L_S + roff(6 * b + row) + 6 * a_run + (dcol - 6)] = v * (scl[6 * b + row] * scl[6 * a_run + (dcol - 6)]);  // Jj^T Ji (S is written Jacobi-scaled, as in the other builds)
-      if (row >= 6 && row < 12) {
-        const int i = row - 6;
-        if (dcol >= 6 && dcol < 12 && dcol - 6 <= i) PART[a_run * SPARTW + i * (i + 1) / 2 + (dcol - 6)] = v;  // Ji^T Ji (lower)
-        if (dcol == 12) PART[a_run * SPARTW + 21 + i] = v;                                                    // Ji^T r
-      }
-      if (row < 7 && dcol >= 6 && dcol < 12) PART[a_run * SPARTW + 27 + row * 6 + (dcol - 6)] = D10[r];         // [Jex Jtd]^T Ji
-    }
-    pmask |= 1 << a_run;
-    Dtot += D00, D10tot += D10;
-    D00 = D10 = d4{0, 0, 0, 0};
-  };
-  for (int chunk0 = 0; chunk0 < ncov; chunk0 += 64) {
-    const int idx = chunk0 + lane;
-    const bool act = idx < ncov;
-    const int e = cov[min(idx, ncov - 1)];
-    const int fa = ids[I_FSTART + e];
-    const int s0 = ids[I_FOBS + e], s = s0 + (b - fa);
-    double ob[4];
-    ob[0] = c.obs[2 * s0], ob[1] = c.obs[2 * s0 + 1];
-    if (relo)
-      ob[2] = c.relo_xy[2 * min(idx, ncov - 1)], ob[3] = c.relo_xy[2 * min(idx, ncov - 1) + 1];
-    else
-      ob[2] = c.obs[2 * s], ob[3] = c.obs[2 * s + 1];
-    double ai[4] = {0, 0, 0, 0}, aj[4] = {0, 0, 0, 0};
-    if (use_td) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) ai[k] = c.aux[4 * s0 + k], aj[k] = c.aux[4 * s + k];
-      td_shift(ob, ai, aj, td, o.tr, o.row);
-    }
-    double r[2] = {0, 0}, Ji[12], Jj[12], Je[2] = {0, 0}, Jx[12], Jt[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 12; k++) Ji[k] = 0, Jj[k] = 0, Jx[k] = 0;
-    if (act) {
-      cost += proj_eval<true>(xs, fr, ric, ric + 9, ob[0], ob[1], ob[2], ob[3], xs[XLAM + e], fa, b, sqi, o.cauchy_a, true, r, Ji, Jj, Je, Jx,
-                              Jt, ai[0], ai[1], aj[0], aj[1]);
-#pragma unroll
-      for (int k = 0; k < 12; k++) Jx[k] *= exm;
-      if (!use_td) Jt[0] = Jt[1] = 0.0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) {
-        W[(6 * b + k) * WLE + e] = Jj[k] * Je[0] + Jj[6 + k] * Je[1];
-        if (k >= 3) PF[(k * NFRP + b) * WLE + e] = Ji[k] * Je[0] + Ji[6 + k] * Je[1];  // (k < 3: minus W's entry, see the base build's frame task)
-        PF[((8 + k) * NFRP + b) * WLE + e] = Jx[k] * Je[0] + Jx[6 + k] * Je[1];
-      }
-      PF[(6 * NFRP + b) * WLE + e] = Je[0] * Je[0] + Je[1] * Je[1];
-      PF[(7 * NFRP + b) * WLE + e] = Je[0] * r[0] + Je[1] * r[1];
-      PF[(14 * NFRP + b) * WLE + e] = Jt[0] * Je[0] + Jt[1] * Je[1];
-    }
-    // The staging tile holds HALF a chunk (lanes 0-31 stage and the wavefront multiplies, then lanes 32-63: the scheme of the throughput build
-    // and of marg_frame_task).  A run that straddles the two halves simply continues: the switch below only acts on a new start frame.
-    const int nact = min(64, ncov - chunk0);
-    const int fav = act ? fa : -1;
-#pragma unroll 1
-    for (int half = 0; half < 2; half++) {
-      const int h0 = 32 * half, lim = min(nact, h0 + 32);
-      if (h0 >= nact) break;  // (uniform)
-      if ((lane >> 5) == half) {
-        dv2* st = reinterpret_cast<dv2*>(stage) + (lane & 31);
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-          st[k * (XRS_X / 2)] = dv2{Jj[k], Jj[6 + k]};
-          st[(6 + k) * (XRS_X / 2)] = dv2{Ji[k], Ji[6 + k]};
-          st[(13 + k) * (XRS_X / 2)] = dv2{Jx[k], Jx[6 + k]};
-        }
-        st[12 * (XRS_X / 2)] = dv2{r[0], r[1]};
-        st[19 * (XRS_X / 2)] = dv2{Jt[0], Jt[1]};
-      }
-      wave_lds_sync();
-      int l = h0;
-      while (l < lim) {
-        const int a_cur = __shfl(fav, l, 64);
-        const int l_end = min(l + __popcll(__ballot(act && fa == a_cur && lane >= l)), lim);
-        if (a_cur != a_run) {
-          flush();
-          a_run = a_cur;
-        }
-        const int j_end = (l_end - h0 + 3) >> 2;
-#pragma unroll 1
-        for (int j0 = (l - h0) >> 2; j0 < j_end; j0 += 4) {
-          // D10 / D11 have seven rows ([Jex Jtd]): two four-row strips on v_mfma_f64_4x4x4 each (18 cycles of the FP64 pipe an issue against
-          // 64; schur_strip4's operand layout: A = row li % 4 of the strip in every quad, B as the 16 x 16 tile takes it, D = register r of the
-          // tile's accumulator for strip r) - 128 + 8 x 18 = 272 instead of 384 cycles per step: 5.78 -> 5.60 ms per 1024 windows (round 5)
-          dv2 u0[4], u1[4], ua[4], ub[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const int ro = 8 * min(j0 + u, 7) + 2 * drow;
-            u0[u] = *reinterpret_cast<const dv2*>(stage + min(dcol, 12) * XRS_X + ro);
-            u1[u] = *reinterpret_cast<const dv2*>(stage + (13 + min(dcol, 6)) * XRS_X + ro);
-            ua[u] = *reinterpret_cast<const dv2*>(stage + (13 + (dcol & 3)) * XRS_X + ro);
-            ub[u] = *reinterpret_cast<const dv2*>(stage + (13 + min(4 + (dcol & 3), 6)) * XRS_X + ro);
-          }
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const int f = h0 + 4 * (j0 + u) + drow;
-            const bool in = f >= l && f < l_end;
-            const double a0 = (in && dcol < 13) ? u0[u][0] : 0.0, a1 = (in && dcol < 13) ? u0[u][1] : 0.0;
-            const double x0 = (in && dcol < 7) ? u1[u][0] : 0.0, x1 = (in && dcol < 7) ? u1[u][1] : 0.0;
-            const double p0 = in ? ua[u][0] : 0.0, p1 = in ? ua[u][1] : 0.0;
-            const double q0 = (in && (dcol & 3) < 3) ? ub[u][0] : 0.0, q1 = (in && (dcol & 3) < 3) ? ub[u][1] : 0.0;
-            D00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a0, D00, 0, 0, 0);
-            D10[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(p0, a0, D10[0], 0, 0, 0), D10[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(q0, a0, D10[1], 0, 0, 0);
-            D11[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(p0, x0, D11[0], 0, 0, 0), D11[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(q0, x0, D11[1], 0, 0, 0);
-            E00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a1, E00, 0, 0, 0);
-            E10[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(p1, a1, E10[0], 0, 0, 0), E10[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(q1, a1, E10[1], 0, 0, 0);
-            E11[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(p1, x1, E11[0], 0, 0, 0), E11[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(q1, x1, E11[1], 0, 0, 0);
-          }
-        }
-        l = l_end;
-      }
-      wave_lds_sync();
-    }
-  }
-  flush();
-  D11 += E11;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int row = drow + 4 * r;
-    if (row < 6 && dcol <= row) lds[L_S + roff(6 * b + row) + 6 * b + dcol] = Dtot[r] * (scl[6 * b + row] * scl[6 * b + dcol]);   // (b,b) lower
-    if (row < 6 && dcol == 12) lds[L_G + 6 * b + row] = Dtot[r];                         // g_b (the gradient is scaled afterwards, as a vector)
-    if (row < 7) {
-      if (dcol < 6) lds[L_S + roff(XC_EX + row) + 6 * b + dcol] = D10tot[r] * (scl[XC_EX + row] * scl[6 * b + dcol]);  // ([ex td], pose b)
-      if (dcol == 12) PX[28 + row] = D10tot[r];                                          // [Jex Jtd]^T r
-      if (dcol <= row) PX[row * (row + 1) / 2 + dcol] = D11[r];                          // ([ex td], [ex td]) lower
-    }
-  }
-  if (lane == 0) ids[I_PMASK + b] = pmask;
-  return cost;
-}
+#include "solve/frame_task_x.hpp"
 #endif
 
 // One wavefront, one IMU factor i: J = sqrt_info * [r | J_raw] (15 x 31) and its Gram matrix on v_mfma_f64_16x16x4,
@@ -2189,6 +1826,22 @@ constexpr TpOffsets tp_make_offsets() {
 }
 __device__ const TpOffsets tp_offsets = tp_make_offsets();
 
+// One of the five latency shadows of the 16-pivot elimination chains (tp_diag_chain, chol_diag_block, pinv16_cholesky: the one definition for
+// the three).  Pivot j's reciprocal is a dependent chain - v_rcp_f64, then two Newton steps - and the rank-1 update of pivot j - 1 (columns
+// j + 1 .. NB - 1 of the caller's row a[NB], factor uprev) is dealt over the shadows before, between and after its four steps, three columns
+// per shadow: AVM_PIVOT_TAIL(0 .. 4, FENCE) around the caller's e / y updates.  Uses the caller's a, NB, j, uprev.  FENCE (a constant):
+// scheduling barriers around the shadow, so that the compiler keeps the hand-made interleaving.
+#define AVM_PIVOT_TAIL(slot, FENCE)                                                                                    \
+  if (FENCE) __builtin_amdgcn_sched_barrier(0);                                                                        \
+  if (j > 0) {                                                                                                         \
+    double sk[3];                                                                                                      \
+    _Pragma("unroll") for (int q = 0; q < 3; q++) sk[q] = readlane_d(a[j - 1], min(j + 1 + (slot) + 5 * q, NB - 1));   \
+    if (FENCE) __builtin_amdgcn_sched_barrier(0);                                                                      \
+    _Pragma("unroll") for (int q = 0; q < 3; q++)                                                                      \
+      if (j + 1 + (slot) + 5 * q < NB) a[j + 1 + (slot) + 5 * q] = fma(-uprev, sk[q], a[j + 1 + (slot) + 5 * q]);      \
+  }                                                                                                                    \
+  if (FENCE) __builtin_amdgcn_sched_barrier(0);
+
 // 16-pivot chain on the diagonal block in LDS patch `patch` ([row][16], symmetric): chol_diag_block with the patch as its source and
 // destination.  Leaves L~ (lower, unscaled: times sqrt(d_c) per column c, the pivot d_c on the diagonal) in the patch and
 // L~^-T with 1 / sqrt(d_c) behind it in buffer `buf`.
@@ -2214,26 +1867,15 @@ AVM_DEV void tp_diag_chain(int nb, int patch, int buf, int stamp) {
     if (j > 0) a[j] = fma(-uprev, readlane_d(a[j - 1], j), a[j]);
     const double djj = readlane_d(a[j], j);
     double y = __builtin_amdgcn_rcp(djj), e = 0;
-#define AVM_TAIL(slot)                                                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                                                                   \
-  if (j > 0) {                                                                                                         \
-    double sk[3];                                                                                                      \
-    _Pragma("unroll") for (int q = 0; q < 3; q++) sk[q] = readlane_d(a[j - 1], min(j + 1 + (slot) + 5 * q, NB - 1));   \
-    __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    _Pragma("unroll") for (int q = 0; q < 3; q++)                                                                      \
-      if (j + 1 + (slot) + 5 * q < NB) a[j + 1 + (slot) + 5 * q] = fma(-uprev, sk[q], a[j + 1 + (slot) + 5 * q]);      \
-  }                                                                                                                    \
-  __builtin_amdgcn_sched_barrier(0);
-    AVM_TAIL(0)
+    AVM_PIVOT_TAIL(0, true)
     e = fma(-djj, y, 1.0);
-    AVM_TAIL(1)
+    AVM_PIVOT_TAIL(1, true)
     y = fma(y, e, y);
-    AVM_TAIL(2)
+    AVM_PIVOT_TAIL(2, true)
     e = fma(-djj, y, 1.0);
-    AVM_TAIL(3)
+    AVM_PIVOT_TAIL(3, true)
     y = fma(y, e, y);
-    AVM_TAIL(4)
-#undef AVM_TAIL
+    AVM_PIVOT_TAIL(4, true)
     uprev = a[j] * y;
   }
   {
@@ -2598,321 +2240,8 @@ int tp_pattern_export(int* out) {
 }
 // (end of chol_regs)
 #ifndef AVM_TP  // the other builds (the latency build: for a prior chol_regs' pattern does not hold): left-looking factorization of the packed system in LDS
-// Scratch of the factorization inside the tile at L_WCH (dead while S is being factored): L^-T of the current and of the
-// next diagonal block, and a per-lane dump slot for the masked-out stores.
-constexpr int L_CLT = L_WCH /* two buffers of 256: block j's L^-T in buffer j & 1 */, L_CDUMP = L_WCH + 512;
-
-// ---- tiles of the factorization, 16x16 on v_mfma_f64_16x16x4 --------------------------------------------------------
-// Everything is unconditional (a predicated LDS access compiles to a branch with its own s_waitcnt): operand rows are
-// clamped to the last valid row (the duplicates only reach outputs that are not stored), destination loads are clamped to
-// a valid address and masked-out stores go to a per-lane dump slot.  The k index of a product is a summation index, so
-// lane group lk takes columns 4 lk + {0..3} of a 16-column block: two 16-byte loads per operand instead of four 8-byte ones.
-struct CholTile {
-  double d[4];
-  int o[4];  // destination offsets (doubles from lds[0]); masked-out entries point at the dump slot
-};
-
-// Factor the nb x nb diagonal block at c0 in the registers of the calling wavefront (lane = row, register = column).
-//  * Select-free: lanes / columns outside the block (and the upper triangle) just carry finite junk that is never stored.
-//  * Lanes 16..31 carry the rows of the identity through the same eliminations: lane 16+i ends with row i of L^-T, which the
-//    MFMA panel solve multiplies the rows below with (zero extra instructions in the pivot chain).
-//  * Square-root free: column j is divided by its pivot with v_rcp_f64 + two Newton steps; rows and L^-T are stored
-//    unscaled (times sqrt(d_c) per column c, the pivot d_c itself on the diagonal) and the consumers apply rsqrt(d_c):
-//    the panel solve (which also raises the non-positive-pivot flag) and chol_solve_lds.
-//  * The wavefront is instruction-issue bound (~4.5 cycles per FP64 / v_readlane instruction, 3 instructions per
-//    (pivot, column) pair), so everything else is kept out of it: no pivot bookkeeping, stores by address select, and the
-//    rank-1 update of pivot j-1 is software-pipelined by hand into the latency shadows of pivot j's reciprocal chain.
-AVM_NOINL void chol_diag_block(int c0, int nb, int buf) {
-  constexpr int NB = CNB;
-  double* S = LDS() + L_S;
-  const int r = threadIdx.x & 63;
-  __builtin_amdgcn_s_setprio(3);  // this wavefront is the critical path of the factorization: win issue arbitration
-  double a[NB];
-  const bool idl = (r & 48) == 16;
-  const int rc = min(r, nb - 1);
-  double* row = S + roff(c0 + rc) + c0;
-  {
-#pragma unroll
-    for (int k = 0; k < NB; k++) a[k] = row[k];  // 16 reads in flight at immediate offsets; past the diagonal they run into the
-                                                 // next packed rows (still inside the factor's LDS region + slack): junk, never stored
-#pragma unroll
-    for (int k = 0; k < NB; k++) a[k] = idl ? ((r & 15) == k ? 1.0 : 0.0) : a[k];  // lanes 16..31: the identity's rows
-  }
-  double uprev = 0.0;
-#pragma unroll
-  for (int j = 0; j < NB; j++) {
-    if (j > 0) a[j] = fma(-uprev, readlane_d(a[j - 1], j), a[j]);
-    const double djj = readlane_d(a[j], j);
-    double y = __builtin_amdgcn_rcp(djj), e = 0;
-#define AVM_TAIL(slot)                                                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                                                                   \
-  if (j > 0) {                                                                                                         \
-    double sk[3];                                                                                                      \
-    _Pragma("unroll") for (int q = 0; q < 3; q++) sk[q] = readlane_d(a[j - 1], min(j + 1 + (slot) + 5 * q, NB - 1));   \
-    __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    _Pragma("unroll") for (int q = 0; q < 3; q++)                                                                      \
-      if (j + 1 + (slot) + 5 * q < NB) a[j + 1 + (slot) + 5 * q] = fma(-uprev, sk[q], a[j + 1 + (slot) + 5 * q]);      \
-  }                                                                                                                    \
-  __builtin_amdgcn_sched_barrier(0);
-    AVM_TAIL(0)
-    e = fma(-djj, y, 1.0);
-    AVM_TAIL(1)
-    y = fma(y, e, y);
-    AVM_TAIL(2)
-    e = fma(-djj, y, 1.0);
-    AVM_TAIL(3)
-    y = fma(y, e, y);
-    AVM_TAIL(4)
-#undef AVM_TAIL
-    uprev = a[j] * y;
-  }
-  {
-    double* dst = idl ? LDS() + L_CLT + buf * (NB * NB) + (r & 15) * NB : row;
-    double* dump = LDS() + L_CDUMP + r;
-    const int kmax = idl ? NB - 1 : (r < nb ? r : -1);
-#pragma unroll
-    for (int k = 0; k < NB; k++) *(k <= kmax ? dst + k : dump) = a[k];
-  }
-  __builtin_amdgcn_s_setprio(0);
-}
-
-// U_ij = A_ij - sum_{p < j} X_ip X_jp^T: the update of tile (ti, tj) by the panels [p_begin, p_end) at once (LEFT-looking),
-// accumulated in registers over the solved panels - 4 tj MFMAs on four independent chains - and ONE read-modify-write of the destination
-// (right-looking costs a destination round trip per panel, and the LDS write path is the slow one: ~70 B/clk).
-AVM_DEV void chol_left_tile(int ti, int tj, int p_begin, int p_end) {
-  constexpr int NR = NF + 1;
-  double* S = LDS() + L_S;
-  const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
-  const dv2* pa = reinterpret_cast<const dv2*>(S + roff(min(16 * ti + lr, NR - 1)) + 4 * lk);
-  const dv2* pb = reinterpret_cast<const dv2*>(S + roff(min(16 * tj + lr, NF - 1)) + 4 * lk);
-  CholTile T;  // (destination part only)
-  {
-    const int gj = 16 * tj + lr;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int gi = 16 * ti + lk + 4 * r;
-      const bool ok = gi < NR && gj < NF && gj <= gi;
-      const int gic = min(gi, NR - 1);
-      const int ol = L_S + roff(gic) + min(gj, min(gic, NF - 1));
-      T.d[r] = LDS()[ol];
-      T.o[r] = ok ? ol : L_CDUMP + lane;
-    }
-  }
-  d4 D0 = {0, 0, 0, 0}, D1 = {0, 0, 0, 0}, D2 = {0, 0, 0, 0}, D3 = {0, 0, 0, 0};
-  const bool diag = ti == tj;
-#pragma unroll 1
-  for (int p = p_begin; p < p_end; p++) {
-    const dv2 a0 = pa[8 * p], a1 = pa[8 * p + 1];
-    dv2 b0 = a0, b1 = a1;
-    if (!diag) b0 = pb[8 * p], b1 = pb[8 * p + 1];
-    D0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[0], b0[0], D0, 0, 0, 0);
-    D1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[1], b0[1], D1, 0, 0, 0);
-    D2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[0], b1[0], D2, 0, 0, 0);
-    D3 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[1], b1[1], D3, 0, 0, 0);
-  }
-  const d4 D = (D0 + D1) + (D2 + D3);
-#pragma unroll
-  for (int r = 0; r < 4; r++) LDS()[T.o[r]] = T.d[r] - D[r];
-}
-
-// X_ij = (A_ij - X_{i,j-1} X_{j,j-1}^T) L_jj^-T: the tile of row block ti in block column j (c0 = 16 j, nb columns), for the
-// rows >= c0 + nb.  `upd`: the tile still lacks the update of the last solved panel (j - 1); that product is computed
-// TRANSPOSED - X_{j,j-1} X_{i,j-1}^T - because the accumulator layout of the transposed tile is exactly the A operand
-// layout of the solve: the update costs no round trip through LDS.  bop = L_jj^-T (B operand), isq = rsqrt(d_c) of the
-// lane's column (see chol_diag_block).
-AVM_DEV void chol_panel_tile(int ti, int c0, int nb, const double (&bop)[CNB / 4], double isq, bool upd) {
-  constexpr int NB = CNB, NR = NF + 1;
-  double* lds = LDS();
-  double* S = lds + L_S;
-  const int lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
-  const int c1 = c0 + nb;
-  const int row = 16 * ti + lr;
-  const double* pa = S + roff(min(row, NR - 1)) + c0 + lk;
-  const bool va = row < NR && row >= c1;
-  double aop[NB / 4];
-#pragma unroll
-  for (int m = 0; m < NB / 4; m++) aop[m] = pa[4 * m];  // past-the-row reads stay inside the LDS carve and are masked below
-  if (upd) {
-    const dv2* pj = reinterpret_cast<const dv2*>(S + roff(min(c0 + lr, NF - 1)) + (c0 - NB) + 4 * lk);
-    const dv2* pi = reinterpret_cast<const dv2*>(S + roff(min(row, NR - 1)) + (c0 - NB) + 4 * lk);
-    const dv2 a0 = pj[0], a1 = pj[1], b0 = pi[0], b1 = pi[1];
-    d4 C0 = {0, 0, 0, 0}, C1 = {0, 0, 0, 0}, C2 = {0, 0, 0, 0}, C3 = {0, 0, 0, 0};
-    C0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[0], b0[0], C0, 0, 0, 0);
-    C1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[1], b0[1], C1, 0, 0, 0);
-    C2 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[0], b1[0], C2, 0, 0, 0);
-    C3 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[1], b1[1], C3, 0, 0, 0);
-    const d4 C = (C0 + C1) + (C2 + C3);  // C[m] = (X_{i,j-1} X_{j,j-1}^T)[row lr][column lk + 4 m]
-#pragma unroll
-    for (int m = 0; m < NB / 4; m++) aop[m] -= C[m];
-  }
-#pragma unroll
-  for (int m = 0; m < NB / 4; m++) aop[m] = (va && lk + 4 * m < nb) ? aop[m] : 0.0;
-  d4 Da = {0, 0, 0, 0}, Db = {0, 0, 0, 0};
-  Da = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[0], bop[0], Da, 0, 0, 0);
-  Db = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[1], bop[1], Db, 0, 0, 0);
-  Da = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[2], bop[2], Da, 0, 0, 0);
-  Db = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[3], bop[3], Db, 0, 0, 0);
-  const d4 D = (Da + Db) * isq;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int gi = 16 * ti + lk + 4 * r;
-    lds[(gi < NR && gi >= c1 && lr < nb) ? L_S + roff(gi) + c0 + lr : L_CDUMP + lane] = D[r];
-  }
-}
-
-// In-place lower Cholesky of the packed NFxNF matrix in lds[L_S]; returns false on a non-positive pivot.
-// The right-hand side rides along as row NF of the packed storage, so the forward substitution L z = b happens as part of
-// the factorization (z ends up in that row).  LEFT-looking by 16-column blocks, ONE workgroup barrier per block column,
-// everything lagging one panel behind the diagonal.  At the barrier that opens phase j: the panels p < j are solved, the
-// diagonal block j is factored (L_jj^-T in buffer j & 1), the tiles of block column j carry the updates of the panels
-// p <= j - 2 and the diagonal tile (j + 1, j + 1) those of the panels p <= j - 1.  Phase j:
-//   wavefront 0  (the critical path): tile (j + 1, j) = [last panel's update, solve]; diagonal tile (j + 1, j + 1) -= panel
-//                j; then its 16-pivot chain (chol_diag_block).  It reads nothing the others write in this phase.
-//   the helpers  (wavefronts 1-3, 5-7; wavefront 4 shares wavefront 0's SIMD and FP64 pipe and stays idle): the other
-//                tiles (i, j) = [last panel's update, solve]; block column j + 1 receives the panels p < j (solved before
-//                the phase began); the diagonal tile (j + 2, j + 2) receives the panels p <= j from the helper that
-//                solves tile (j + 2, j).
-// Every tile is read-modify-written once for all its early panels and once more, fused with its solve, for the last one.
-AVM_NOINL bool cholesky_lds(long long* prof) {
-  struct { long long* prof; } c{prof};
-  double* lds = LDS();
-  double* S = lds + L_S;
-  const int t = threadIdx.x, wv = t >> 6, lane = t & 63, lr = lane & 15, lk = lane >> 4;
-  constexpr int NB = CNB;
-  constexpr int NHELP = NT / 64 - 2;
-  const int hslot = wv < 4 ? wv - 1 : wv - 5 + 3;  // helpers 1 2 3 5 6 7 -> 0..5 (wavefronts 0 and 4: not helpers)
-  const bool helper = wv != 0 && wv != 4;
-  int* s_fail = reinterpret_cast<int*>(lds + L_INT) + I_FAIL;
-  if (t == 0) *s_fail = 0;
-  PROF_T0();
-  if (wv == 0) chol_diag_block(0, NB, 0);
-  __syncthreads();
-  PROF(c, 4);
-  for (int j = 0, c0 = 0; c0 < NF; j++, c0 += NB) {
-    const int nb = min(NB, NF - c0), c1 = c0 + nb;
-    const int t0 = c1 >> 4;  // first tile row with rows below the block (the block's own tile row when nb < 16)
-    // B operand of the solves = L_jj^-T (left in buffer j & 1 by chol_diag_block, stored times sqrt(d_c) per column: the
-    // pivots sit on the diagonal of the block)
-    double bop[NB / 4];
-    {
-      const double* LT = lds + L_CLT + (j & 1) * (NB * NB);
-#pragma unroll
-      for (int m = 0; m < NB / 4; m++) bop[m] = LT[(lk + 4 * m) * NB + lr];
-    }
-    const int cc = c0 + min(lr, nb - 1);
-    const double dc = S[roff(cc) + cc];
-    if (!(dc > 0.0)) *s_fail = 1;  // non-positive (or NaN) pivot: every wavefront sees the same values
-    const double isq = fast_rsqrt(dc);  // applied to the product's columns: its latency hides under the loads and MFMAs
-#pragma unroll
-    for (int m = 0; m < NB / 4; m++) bop[m] = (lk + 4 * m < nb && lr < nb) ? bop[m] : 0.0;
-    const bool last = c1 >= NF;
-    if (wv == 0) {
-      const long long q0 = clock64();
-      chol_panel_tile(t0, c0, nb, bop, isq, j > 0 && t0 > j);
-      if (!last) {
-        wave_lds_sync();
-        chol_left_tile(j + 1, j + 1, j, j + 1);  // (the panels before were applied a phase ago by the first helper)
-        wave_lds_sync();
-        chol_diag_block(c1, min(NB, NF - c1), (j + 1) & 1);
-      }
-      if (c.prof && t == 0) c.prof[28] += clock64() - q0;
-    } else if (helper) {
-      const long long q0 = clock64();
-      for (int ti = t0 + 1 + hslot; ti <= TLAST; ti += NHELP) chol_panel_tile(ti, c0, nb, bop, isq, j > 0 && ti > j);
-      // the diagonal tile (j + 2, j + 2) only needs its own row block's panels: the helper that has just solved tile
-      // (j + 2, j) applies all of them, panel j included, so that wavefront 0 adds a single panel next phase
-      if (!last && hslot == 0 && j + 2 <= TLAST) {
-        wave_lds_sync();
-        chol_left_tile(j + 2, j + 2, 0, j + 1);
-      }
-      if (!last && j > 0) {
-        // tiles (j + 2 .. TLAST, j + 1) receive the panels p < j; dealt in the opposite order of the panel tiles above
-        const int ntile = TLAST - (j + 1);
-        for (int k = NHELP - 1 - hslot; k < ntile; k += NHELP) chol_left_tile(j + 2 + k, j + 1, 0, j);
-      }
-      if (c.prof && t == 64) c.prof[27] += clock64() - q0;
-    }
-    __syncthreads();
-    PROF(c, 5);
-    if (*s_fail) return false;
-    if (last) break;
-  }
-  return true;
-}
-
-// Backward substitution L^T x = z with z in the augmented row of lds[L_S] (left there by cholesky_lds), result to
-// lds[vec..vec+NF).  13.6K multiply-adds on an 11-block serial chain: all of it runs in wavefront 0 with no workgroup
-// barrier (a barrier costs ~250 cycles, two per block were most of the old version's time).  Per 16-column block, last
-// to first:  lane r (mod 16) holds column r of the block triangle scaled so that x_r comes straight out of v_readlane
-// (x_r = d_r^-1/2 z_r - d_r^-1 sum_i raw[i][r] x_i; the diagonal blocks are stored unscaled, see chol_diag_block) and
-// the 16 steps are readlane -> fma; entries at or above the diagonal are finite junk that only reaches values that
-// have already been consumed.  The finished x_i stay in SGPRs and are applied to the remaining b[j], j < c0, by all
-// 64 lanes (loads issued ahead of the chain).
-template <int NBV>
-AVM_DEV void chol_solve_block(double* S, double* b, int c0, int lane) {
-  const int rr = min(lane & 15, NBV - 1);
-  const double* col = S + c0 + rr;  // + roff(row): column c0+rr
-  const double dr = col[roff(c0 + rr)];
-  double colv[NBV];
-#pragma unroll
-  for (int i = 0; i < NBV; i++) colv[i] = col[roff(c0 + i)];  // uniform row offset; i < rr reads (finite) entries of the next rows
-  double bv = b[c0 + rr];
-  // rows of the block for all (<= 160 = 3 x 64) remaining columns: in flight during the chain (clamped addresses; a
-  // segment beyond c0 is simply not stored)
-  const int jc = max(c0 - 1, 0);
-  double v0[3][NBV], acc[3];
-#pragma unroll
-  for (int sgm = 0; sgm < 3; sgm++) {
-    const int j = min(64 * sgm + lane, jc);
-    acc[sgm] = b[j];
-#pragma unroll
-    for (int i = 0; i < NBV; i++) v0[sgm][i] = S[roff(c0 + i) + j];
-  }
-  const double isq = fast_rsqrt(dr), di2 = isq * isq;
-  bv *= isq;
-#pragma unroll
-  for (int i = 0; i < NBV; i++) colv[i] *= di2;
-  double xs[NBV], xout = 0.0;
-#pragma unroll
-  for (int jj = NBV - 1; jj >= 0; jj--) {
-    xs[jj] = readlane_d(bv, jj);
-    bv = fma(-colv[jj], xs[jj], bv);
-    xout = lane == jj ? xs[jj] : xout;
-  }
-  if (lane < NBV) b[c0 + lane] = xout;
-#pragma unroll
-  for (int sgm = 0; sgm < 3; sgm++) {
-    if (64 * sgm >= c0) break;  // (uniform)
-    double a0 = acc[sgm], a1 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NBV; i++) {
-      if (i & 1) a1 = fma(-v0[sgm][i], xs[i], a1); else a0 = fma(-v0[sgm][i], xs[i], a0);
-    }
-    if (64 * sgm + lane < c0) b[64 * sgm + lane] = a0 + a1;
-  }
-  wave_lds_sync();
-}
-
-AVM_NOINL void chol_solve_lds(int vec) {
-  double* lds = LDS();
-  double* S = lds + L_S;
-  double* b = lds + vec;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  constexpr int NB = 16;
-  if (wv == 0) {
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-      if (lane + 64 * q < NF) b[lane + 64 * q] = S[roff(NF) + lane + 64 * q];
-    wave_lds_sync();
-    if (NF % NB) chol_solve_block<(NF % NB) ? (NF % NB) : NB>(S, b, (NF / NB) * NB, lane);
-    // (unrolled: every block's row offsets become immediates of its LDS reads)
-#pragma unroll
-    for (int blk = NF / NB - 1; blk >= 0; blk--) chol_solve_block<NB>(S, b, blk << 4, lane);
-  }
-  __syncthreads();
-}
-
-#endif  // AVM_TP / LDS factorization
+#include "solve/cholesky_lds.hpp"
+#endif
 
 // One wavefront's share of the Schur update: the tiles (R, C), R in {R0, R1}, C in {C0, C1}, C <= R, of the 5x5
 // grid (-1 = absent).  Every 16-column block of W is loaded once per k-step and feeds all the tiles that use it.
@@ -3056,75 +2385,7 @@ AVM_DEV void schur_macro_tile(const WinCtx&) {
 }
 
 #ifndef AVM_X
-// Tile row 4 of the 5 x 5 grid holds three rows: pose columns 64, 65 and the right-hand side.  As 16 x 16 tiles that is a third of the
-// update's matrix instructions for 3 / 80 of its rows; v_mfma_f64_4x4x4 - four independent 4 x 4 x 4 products per instruction, a
-// quarter of the FP64 pipe time (scripts/ubench/pair.hip: 18 cycles against 64) - does the same strip with the SAME B operand a
-// 16 x 16 tile takes (lane 16 k + c holds W[column c][feature k]: block b = c / 4 is the quad column, fsel.hip's layout note) when all
-// four blocks get the three rows (+ one of zeros) as their A: lane 16 k + c holds row c % 4.  D[i][c] comes out at lane 16 i + c.
-// The strip over the column blocks C0, C1, C2 (-1 = absent), round 5.
-template <int C0, int C1, int C2>
-AVM_DEV void schur_strip4(const WinCtx&) {
-  const WinCtx& c = lds_ctx();
-  double* lds = LDS();
-  const double* scl = lds + L_SC;
-  gcdouble* W = c.sc + Scratch::W;  // Wt[c][e]
-  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4, ai = li & 3;
-  constexpr int NC = C2 >= 0 ? 3 : (C1 >= 0 ? 2 : 1);
-  constexpr int CB[3] = {C0, C1, C2};
-  constexpr int KB = 8;
-  static_assert(NPOSE == 66, "rows 64, 65 | right-hand side | zeros");
-  double D[3] = {0, 0, 0};
-  for (int e0 = 0; e0 < c.nf; e0 += 4 * KB) {
-    double va[KB], vc[3][KB], fe[KB], xe[KB];
-    {
-      gcdv2* src = reinterpret_cast<gcdv2*>(W + (size_t)min(64 + ai, NPOSE - 1) * WLE + e0 + 8 * lk);
-#pragma unroll
-      for (int m2 = 0; m2 < KB / 2; m2++) {
-        const dv2 v = src[m2];
-        va[2 * m2] = v.x, va[2 * m2 + 1] = v.y;
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < NC; b++) {
-      if (CB[b] == 4) continue;  // (the diagonal block's columns 64, 65 are the A rows of the lanes li < 2)
-      gcdv2* src = reinterpret_cast<gcdv2*>(W + (size_t)(16 * CB[b] + li) * WLE + e0 + 8 * lk);
-#pragma unroll
-      for (int m2 = 0; m2 < KB / 2; m2++) {
-        const dv2 v = src[m2];
-        vc[b][2 * m2] = v.x, vc[b][2 * m2 + 1] = v.y;
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < KB; m++) {
-      const int el = min(e0 + 8 * lk + m, MAXE + 1);
-      fe[m] = lds[L_ST + el], xe[m] = lds[L_ST + 152 + el];
-    }
-#pragma unroll
-    for (int m = 0; m < KB; m++) {
-      const bool on = e0 + 8 * lk + m < c.nf;
-      const double w = (on && ai < 2) ? va[m] : 0.0;
-      const double aop = ai == 2 ? xe[m] : w * fe[m];  // (x_e = 0 beyond the window's features: schur_reduce)
-#pragma unroll
-      for (int b = 0; b < NC; b++) {
-        const double bop = CB[b] == 4 ? (li < 2 ? w : 0.0) : (on ? vc[b][m] : 0.0);
-        D[b] = mfma4(aop, bop, D[b]);
-      }
-    }
-  }
-  // lane (lk, li): row 64 + lk (lk = 2: the right-hand side, 3: nothing), column 16 C + li
-#pragma unroll
-  for (int b = 0; b < NC; b++) {
-    const int gi = 64 + lk, gj = 16 * CB[b] + li;
-    const bool body = gi < NPOSE && gj <= gi, rhs = gi == NPOSE && gj < NPOSE;
-#ifdef AVM_TP
-    const int off = body ? L_S + roff(gi) + gj : (rhs ? L_RHS + gj : L_DUMP + lane);
-#else
-    const int off = body ? L_S + roff(gi) + gj : (rhs ? L_S + roff(NF) + gj : L_DUMP + lane);
-#endif
-    const double sc = (body ? scl[min(gi, NPOSE - 1)] : 1.0) * scl[min(gj, NPOSE - 1)];
-    lds[off] = lds[off] - sc * D[b];
-  }
-}
+#include "solve/schur_strip4.hpp"
 #endif
 
 // Schur complement on the inverse depths, then the right-hand side into the augmented row:
@@ -3624,19 +2885,12 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
       // chunks' worth) and two fifths of the prior's rows, wavefront 3 the other three fifths: they start with that load.
       // (Round 5: with the issue priorities those two run at the light level and weigh less than they did: 60 / 300 factors' worth,
       //  re-measured - were 88 / 380: ragged tracks 11.82 -> 11.74 ms, dense 12.54 -> 12.49.)
-#ifndef AVM_TP_WIMU
-#define AVM_TP_WIMU 60
-#endif
-#ifndef AVM_TP_WPRI
-#define AVM_TP_WPRI 300
-#endif
-      int fc = t == 2 ? AVM_TP_WIMU + (c.pn > 0 ? 2 * AVM_TP_WPRI / 5 : 0) : (t == 3 && c.pn > 0 ? 3 * AVM_TP_WPRI / 5 : 0), done = 0;
+      int fc = t == 2 ? TP_WIMU + (c.pn > 0 ? 2 * TP_WPRI / 5 : 0) : (t == 3 && c.pn > 0 ? 3 * TP_WPRI / 5 : 0), done = 0;
       if (t == 0) ids[I_FRW] = -1;
       for (int k = 1; k < NFRP; k++) {
-        constexpr int RUNW = AVM_LPT_RUNW;
         int bb = -1, bn = -1;
         for (int f = 1; f < NFRP; f++) {
-          const int n = ids[I_NCOV + f] + RUNW * max(ids[I_NRUN + f] - 1, 0);
+          const int n = ids[I_NCOV + f] + LPT_RUNW * max(ids[I_NRUN + f] - 1, 0);
           if (!(done & (1 << f)) && n > bn) bn = n, bb = f;
         }
         const int own = (fc + 63) >> 6, with = (fc + bn + 63) >> 6;
@@ -3660,13 +2914,12 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
       int fc = 0, done = 0;
       if (t == 0) ids[I_FRW] = -1;
       for (int k = 1; k < NFRP; k++) {
-        // (a frame weighs its factors plus RUNW factors' worth for every accumulation run beyond the first - a run costs a flush of
+        // (a frame weighs its factors plus LPT_RUNW factors' worth for every accumulation run beyond the first - a run costs a flush of
         //  the partial blocks and a group of eight MFMAs however short it is: with ragged tracks a frame has up to ten runs of a
         //  handful of factors each, and by factor counts alone two wavefronts ended up with twice the others' time)
-        constexpr int RUNW = AVM_LPT_RUNW;
         int bb = -1, bn = -1;
         for (int f = 1; f < NFRP; f++) {
-          const int n = ids[I_NCOV + f] + RUNW * max(ids[I_NRUN + f] - 1, 0);
+          const int n = ids[I_NCOV + f] + LPT_RUNW * max(ids[I_NRUN + f] - 1, 0);
           if (!(done & (1 << f)) && n > bn) bn = n, bb = f;
         }
         const int own = (fc + 63) >> 6, with = (fc + bn + 63) >> 6;
@@ -4208,1298 +3461,18 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
   }
 }
 
-#if !defined(AVM_X)
-// =====================================================================================
-// Post-solve marginalization: MarginalizationInfo::addResidualBlockInfo / preMarginalize /
-// marginalize / getParameterBlocks (vins_estimator/src/factor/marginalization_factor.cpp:89-319)
-// as driven by Estimator::optimization() (estimator.cpp:817-990), one workgroup per window.
-//
-// Variable layout of the joint system: poses 0..65 | speed-bias 66..164 | ex_pose 165..170 (171 dims,
-// packed lower triangle in LDS).  Factors: old prior, IMU factor 0, every projection factor of the
-// features that start in frame 0 (with their ex_pose Jacobians) — assembled with the same MFMA X^T X
-// scheme as the solve (X row = Jj | Ji | r | Jex).  The inverse depths of those features are
-// eliminated first as scalar pivots (they are mutually independent; identical to the reference's joint
-// eigen-pseudo-inverse of Amm whenever no eigenvalue is clamped), then pose0/speedbias0 through the
-// eigen-decomposition of their 15x15 block with the reference's 1e-8 clamp, and the kept block is
-// square-rooted through a second eigen-decomposition (parallel cyclic Jacobi in LDS).
-// Deterministic block order (the reference's is address-hash order): kept = poses by frame,
-// speed-bias by frame, ex_pose.
-namespace mg {
-constexpr int MXRS = 68;                              // rows per staged column: HALF a chunk (32 factors x 2 residual rows) + 4 (bank spread)
-constexpr int MXSTG = 20 * MXRS;                      // column-major staging tile: Jj 0-5 | Ji 6-11 | r 12 | Jex 13-18 | Jtd 19
-#ifdef AVM_TP
-// THROUGHPUT form of the marginalization (marginalize_tp_kernel in window_solve_tp.o, round 5): the same phases as a 256-thread
-// workgroup inside the throughput build's 80 KB of LDS, so that TWO windows are resident per CU - the kernel is a sequence of short
-// latency-bound phases (62 % of its wavefront cycles waiting), and a second window fills them.  What makes it fit: the joint system
-// only holds the variables a marginalization can touch - poses | speed-bias 0, 1 | ex_pose | td = 91 instead of 172 (packed 33 KB
-// instead of 117): IMU factor 0 reaches speed-biases 0 and 1, the projection factors the poses and ex_pose / td, and the old prior
-// whatever it kept last time, which for a prior the reference can build is a subset of these (estimator.cpp:904-916 keeps
-// para_SpeedBias[1], shifted to frame 0).  A prior with a speed-bias block of a later frame takes the other kernel (the host checks:
-// window_prior_fits_marg_tp).  Speed-biases 0 and 1 keep their indices (66 .. 83), so imu_col() and SB0 + 9 fr hold unchanged.
-constexpr int MEX0 = 84, MTD = 90, MVARS = 91;
-constexpr int MASM = 4;                               // every wavefront assembles (frames 1 8 9 | 2 7 10 | 3 6 + raw IMU, prior | 4 5 + prior)
-#else
-constexpr int MEX0 = 165, MTD = 171, MVARS = 172;     // 172 variables: poses | speed-biases | ex_pose | td
-constexpr int MASM = 7;                               // assembling wavefronts (staging must stay below row 165: half tiles let seven fit)
+#ifndef AVM_X  // marginalization: latency and throughput builds
+#include "solve/marg.hpp"
+#include "solve/marg_kernel.hpp"
 #endif
-constexpr int MROWS = croff(MVARS);
-#ifdef AVM_TP
-// LDS of the throughput form: S (4232) | EA EV EB / IMU factor rows (2048) | T (1536) | g_e (152) ... b in the scaling vector's place;
-// the staging tiles of phase A lie over everything from row 66 of S to 7684, all of it written after phase A only
-constexpr int M_WCH = MROWS;                          // Amm, its eigenvectors / inverse factor, Arm (n x 16); before: the IMU factor's rows
-constexpr int M_GT = M_WCH + 2048;                    // T = Arm Amm^+ (n x 16)
-constexpr int M_GE = M_GT + 96 * 16;                  // g_e (152)
-constexpr int M_G = L_SC;                             // b over the 91 variables (the Jacobi scaling is the solve's)
-static_assert(M_GE + 152 <= M_G && MVARS <= VEC && M_G + VEC <= L_X, "marg layout (throughput form)");
-static_assert(L_S + SPP + MASM * MXSTG <= M_G, "marg staging must not reach b");
+
+#if defined(AVM_TP)
+#include "solve/launch_tp.hpp"
+#elif defined(AVM_X)
+#include "solve/launch_x.hpp"
 #else
-constexpr int M_G = MROWS;                            // b over the 171 variables (176)
-constexpr int M_GE = M_G + 176;                       // g_e (152)
-constexpr int M_WCH = M_GE + 152;                     // [24][80] Schur staging / IMU factor rows
-constexpr int M_GT = L_G;                             // T = Arm Amm^+ in the range of the solve's gradient / scaling vectors (unused here)
-constexpr int MWCH = 24;
-static_assert(M_WCH + MWCH * WLD <= L_G, "marg layout");
-static_assert(SPP + MASM * MXSTG <= 13778, "marg staging must not reach the ex_pose rows (roff(165))");
-#endif
-constexpr int PARTW = 146;  // aa 21 | g_a 6 | [ex td].pose0 42 | [ex td]^2 28 | g_[ex td] 7 | [ex td].pose_b 42
-constexpr int MNW = 73;     // columns of W = E^T F here: 66 pose | 6 ex_pose | 1 td
-}  // namespace mg
-
-// column of the joint system for W column c (0..71): poses, then ex_pose
-AVM_DEV int mg_col(int c) { return c < NPOSE ? c : mg::MEX0 + (c - NPOSE); }  // (td: W column 72 -> variable 171)
-
-// One wavefront's share of the elimination of the start-0 inverse depths (marginalization): the tiles (R, C),
-// R in {R0, R1}, C in {C0, C1}, C <= R, of  W^T diag(1 / E^T E) W  over the 72 (padded 80) columns of W = E^T F
-// (66 pose + 6 ex_pose columns, row-major [e][72] here).  Padded row 72 carries g_e / (E^T E) in place of a W column,
-// so tile row 4 also delivers the right-hand-side update.  Operands straight from the scratch slot, 8 k-steps of
-// loads in flight, no staging, no barriers.
-template <int R0, int R1, int C0, int C1>
-AVM_DEV void marg_schur_macro_tile(int nf0) {
-  using namespace mg;
-  const WinCtx& c = lds_ctx();
-  double* lds = LDS();
-  gcdouble* W = c.sc + Scratch::W;
-  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-  constexpr int NR = R1 >= 0 ? 2 : 1, NC = C1 >= 0 ? 2 : 1;
-  constexpr int RB[2] = {R0, R1}, CB[2] = {C0, C1};
-  constexpr bool SAME = R0 == C0 && R1 == C1;
-  constexpr int KB = 8, NW = MNW;
-  d4 D[2][2] = {{{0, 0, 0, 0}, {0, 0, 0, 0}}, {{0, 0, 0, 0}, {0, 0, 0, 0}}};
-  for (int e0 = 0; e0 < nf0; e0 += 4 * KB) {
-    double vr[2][KB], vc[2][KB], fe[KB], xe[KB];
-    // (the k index is a summation index: lane group lk takes the 8 consecutive features e0 + 8 lk .. + 7 = 64 contiguous bytes of a
-    //  column of Wt, as in schur_macro_tile; rows clamped, masked afterwards; the features beyond nf0 read stale but finite entries of
-    //  the region - WLE leaves room for the 8-feature granularity - and are masked out by `on`)
-#pragma unroll
-    for (int a = 0; a < NR; a++) {
-      gcdv2* src = reinterpret_cast<gcdv2*>(W + (size_t)min(16 * RB[a] + li, NW - 1) * WLE + e0 + 8 * lk);
-#pragma unroll
-      for (int m2 = 0; m2 < KB / 2; m2++) {
-        const dv2 v = src[m2];
-        vr[a][2 * m2] = v.x, vr[a][2 * m2 + 1] = v.y;
-      }
-    }
-    if (!SAME) {
-#pragma unroll
-      for (int b = 0; b < NC; b++) {
-        gcdv2* src = reinterpret_cast<gcdv2*>(W + (size_t)min(16 * CB[b] + li, NW - 1) * WLE + e0 + 8 * lk);
-#pragma unroll
-        for (int m2 = 0; m2 < KB / 2; m2++) {
-          const dv2 v = src[m2];
-          vc[b][2 * m2] = v.x, vc[b][2 * m2 + 1] = v.y;
-        }
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < KB; m++) {
-      const int ec = min(e0 + 8 * lk + m, nf0 - 1);
-      fe[m] = lds[L_HEE + ec], xe[m] = lds[L_HEE + ec] * lds[M_GE + ec];
-    }
-#pragma unroll
-    for (int m = 0; m < KB; m++) {
-      const bool on = e0 + 8 * lk + m < nf0;
-      double aop[2], bop[2];
-#pragma unroll
-      for (int a = 0; a < NR; a++) {
-        const int col = 16 * RB[a] + li;
-        const double w = (on && col < NW) ? vr[a][m] : 0.0;
-        aop[a] = col == NW ? (on ? xe[m] : 0.0) : w * fe[m];
-        if (SAME) bop[a] = w;
-      }
-      if (!SAME) {
-#pragma unroll
-        for (int b = 0; b < NC; b++) bop[b] = (on && 16 * CB[b] + li < NW) ? vc[b][m] : 0.0;
-      }
-#pragma unroll
-      for (int a = 0; a < NR; a++)
-#pragma unroll
-        for (int b = 0; b < NC; b++)
-          if (CB[b] <= RB[a]) D[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[a], bop[b], D[a][b], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < NR; a++)
-#pragma unroll
-    for (int b = 0; b < NC; b++) {
-      if (CB[b] > RB[a]) continue;
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int gi = 16 * RB[a] + lk + 4 * r, gj = 16 * CB[b] + li;
-        if (gi < NW && gj <= gi) {
-          const int si = mg_col(gi), sj = mg_col(gj);
-          lds[L_S + roff(max(si, sj)) + min(si, sj)] -= D[a][b][r];
-        }
-        if (gi == NW && gj < NW) lds[M_G + mg_col(gj)] -= D[a][b][r];
-      }
-    }
-}
-
-// ... and the two single-wavefront jobs beside the frame tasks (IMU factor 0's raw Jacobians on one lane, the old prior's residual and gradient)
-AVM_NOINL void marg_imu0_raw() {
-  const WinCtx& c = lds_ctx();
-  double* lds = LDS();
-  imu_raw<true>(lds + L_X, lds + L_FR, lds_opt(), c.pdelta, c.pjac, c.psum[0], c.lba, c.lbg, 0, c.sc + Scratch::IJRAW);
-}
-AVM_NOINL void marg_prior_wave(int rb, int re, int buf_off) { (void)prior_wave<true>(L_X, rb, re, buf_off); }
-// Phase D of the marginalization (IMU factor 0: J = sqrt_info [r | J_raw], then J^T J and J^T r into the system) as a function of its own
-AVM_NOINL void marg_imu0_gram() {
-  const WinCtx& c = lds_ctx();
-  using namespace mg;
-  double* lds = LDS();
-  const int t = threadIdx.x;
-  const double* IJR = c.sc + Scratch::IJRAW;
-  double* IJ = lds + M_WCH;
-  for (int idx = t; idx < 465; idx += NT) {
-    const int r = idx / 31, cc = idx % 31;
-    // (sqrt_info is stored with zeros below its diagonal: all fifteen products, their thirty loads in flight at once - as a loop
-    //  from k = r every step was a trip to the slot of its own)
-    double ps[15], ij[15];
-#pragma unroll
-    for (int k = 0; k < 15; k++) ps[k] = c.psqrt[r * 15 + k], ij[k] = IJR[k * 31 + cc];
-    double sacc = 0;
-#pragma unroll
-    for (int k = 0; k < 15; k++) sacc += k >= r ? ps[k] * ij[k] : 0.0;
-    IJ[idx] = sacc;
-  }
-  __syncthreads();
-  for (int q = t; q < 495; q += NT) {
-    if (q < 465) {
-      int p = 0;
-      while ((p + 1) * (p + 2) / 2 <= q) p++;
-      const int qq = q - p * (p + 1) / 2;
-      double sacc = 0;
-      for (int r = 0; r < 15; r++) sacc += IJ[r * 31 + 1 + p] * IJ[r * 31 + 1 + qq];
-      const int ip = imu_col(0, p), iq = imu_col(0, qq);
-      lds[L_S + roff(max(ip, iq)) + min(ip, iq)] += sacc;
-    } else {
-      const int p = q - 465;
-      double sacc = 0;
-      for (int r = 0; r < 15; r++) sacc += IJ[r * 31 + 1 + p] * IJ[r * 31];
-      lds[M_G + imu_col(0, p)] += sacc;
-    }
-  }
-  __syncthreads();
-}
-// Phase B of the marginalization (the per-feature sums) as a function of its own, like marg_schur_phase: its ten-deep load arrays are 140 registers
-AVM_NOINL void marg_feature_sums(int nf0) {
-  const WinCtx& c = lds_ctx();
-  using namespace mg;
-  double* lds = LDS();
-  int* ids = reinterpret_cast<int*>(lds + L_INT);
-  const int t = threadIdx.x;
-  double* W = c.sc + Scratch::W;
-  const double* PF = c.sc + Scratch::PF;
-  const double* PF2 = c.sc + Scratch::PF + 8 * (size_t)NFR * WLE;
-  // (the factor of feature e observed in frame k - these features start in frame 0 - sits at [quantity][k][e])
-  // the two heavy items of a feature (f == 0: its own pose block, hee, g_e;  f == 11: the ex_pose / td columns) are dealt
-  // densely to the threads; the structural zeros of the frames that do not observe it follow in a loop of their own
-  for (int idx = t; idx < nf0 * 2; idx += NT) {
-    const int e = idx >> 1, f = (idx & 1) ? 11 : 0;
-    const int no = ids[I_FNOBS + e];
-    {
-      const double* P = f == 0 ? PF : PF2;
-      // all loads of the feature's (<= 10) factors in flight at once, clamped to its last observation and masked
-      // (f == 11: the six ex_pose columns and the td column, W columns 66..72)
-      double pv[7][NFR - 1];
-#pragma unroll
-      for (int k = 1; k < NFR; k++)
-#pragma unroll
-        for (int q = 0; q < 7; q++) {  // (f == 0, q < 3: Ji_t^T Je is minus the observing frame's W entry - marg_frame_task does not store it twice)
-          const int kk = min(k, max(no - 1, 0));
-          pv[q][k - 1] = (f == 0 && q < 3) ? W[(size_t)(6 * kk + q) * WLE + e] : P[(size_t)(min(q, (f == 0 || !c.est_td) ? 5 : 6) * NFR + kk) * WLE + e];
-        }
-      double sacc[7] = {0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int k = 1; k < NFR; k++)
-#pragma unroll
-        for (int q = 0; q < 7; q++) sacc[q] += k < no ? pv[q][k - 1] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 6; q++) W[(size_t)(6 * f + q) * WLE + e] = (f == 0 && q < 3) ? -sacc[q] : sacc[q];
-      if (f == 11) W[(size_t)72 * WLE + e] = c.est_td ? sacc[6] : 0.0;
-      if (f == 0) {
-        double hv[2][NFR - 1];
-#pragma unroll
-        for (int k = 1; k < NFR; k++) {
-          const int kk = min(k, max(no - 1, 0));
-          hv[0][k - 1] = PF[(size_t)(6 * NFR + kk) * WLE + e], hv[1][k - 1] = PF[(size_t)(7 * NFR + kk) * WLE + e];
-        }
-        double he = 0, ge = 0;
-#pragma unroll
-        for (int k = 1; k < NFR; k++) he += k < no ? hv[0][k - 1] : 0.0, ge += k < no ? hv[1][k - 1] : 0.0;
-        lds[L_HEE + e] = he;
-        lds[M_GE + e] = ge;
-      }
-    }
-  }
-  for (int idx = t; idx < nf0 * (NFR - 1); idx += NT) {
-    const int e = idx / (NFR - 1), f = 1 + idx % (NFR - 1);
-    if (f >= ids[I_FNOBS + e]) {
-#pragma unroll
-      for (int q = 0; q < 6; q++) W[(size_t)(6 * f + q) * WLE + e] = 0.0;
-    }
-  }
-}
-
-// Phase F of the marginalization as a function of its own (round 6): inlined, its accumulators and operands pushed the kernel body's
-// allocation so far that the registers holding SPILLED SGPRs were spilled themselves - every thread-range predicate of the kernel then began
-// with a trip to scratch memory (106 sites, 32 of them in this phase's scatter).
-AVM_NOINL void marg_schur_phase(int nf0) {
-#ifdef AVM_TP
-  AVM_PRIO_BULK();
-  switch (threadIdx.x >> 6) {  // four wavefronts, one per SIMD: 4 | 3 + 1 | 3 | 2 + 2 tiles (as schur_reduce)
-    case 0: marg_schur_macro_tile<2, 3, 0, 1>(nf0); break;
-    case 1: marg_schur_macro_tile<0, 1, 0, 1>(nf0), marg_schur_macro_tile<4, -1, 4, -1>(nf0); break;
-    case 2: marg_schur_macro_tile<2, 3, 2, 3>(nf0); break;
-    default: marg_schur_macro_tile<4, -1, 0, 1>(nf0), marg_schur_macro_tile<4, -1, 2, 3>(nf0); break;
-  }
-  AVM_PRIO_LIGHT();
-#else
-  switch (threadIdx.x >> 6) {
-    case 0: marg_schur_macro_tile<2, 3, 0, 1>(nf0); break;
-    case 1: marg_schur_macro_tile<0, 1, 0, 1>(nf0); break;
-    case 2: marg_schur_macro_tile<2, 3, 2, 3>(nf0); break;
-    case 3: marg_schur_macro_tile<4, -1, 0, 1>(nf0); break;
-    case 7: marg_schur_macro_tile<4, -1, 2, 3>(nf0); break;
-    case 5: marg_schur_macro_tile<4, -1, 4, -1>(nf0); break;
-    default: break;
-  }
-#endif
-}
-
-AVM_NOINL void marg_frame_task(const WinCtx&, const avm_options&, int b0, int b1, int stage_off) {
-  // The wavefront's (at most two) frames b0 < b1 as ONE list of factors, 64 at a time: a chunk may straddle the two frames (5
-  // chunks for two frames of 150 factors instead of 3 + 3), the MFMA accumulation is cut at the frame boundary.
-  const WinCtx& c = lds_ctx();
-  const avm_options& o = lds_opt();
-  using namespace mg;
-  double* lds = LDS();
-  double* stage = lds + stage_off;
-  int* ids = reinterpret_cast<int*>(lds + L_INT);
-  (void)ids;
-  const int lane = threadIdx.x & 63;
-  const int n0 = ids[I_NCOV + b0], n1 = b1 < NFR ? ids[I_NCOV + b1] : 0, ntot = n0 + n1;
-  Frames fr{lds + L_FR, lds + L_FR + 99};
-  const double* xs = lds + L_X;
-  const double sqi = o.focal_length / 1.5;
-  // FEATURE-MAJOR like the solve's slot (round 3): the lanes of a chunk are consecutive features of one frame, so W / PF / PF2 are
-  // written as whole cache lines (they were [feature][column] and [quantity][observation slot]: 8-byte stores 640 and 88 bytes
-  // apart, 80 K of this phase's 181 K cycles per window)
-  double* W = c.sc + Scratch::W;       // Wt[MNW][WLE]: E^T F, column-major over the features
-  double* PF = c.sc + Scratch::PF;     // [8][NFR][WLE] Ji^T Je (6), Je^T Je, Je^T r of the factor (feature e, frame b)
-  double* PF2 = c.sc + Scratch::PF + 8 * (size_t)NFR * WLE;  // [7][NFR][WLE] Jex^T Je (6), Jtd^T Je
-  const double td = lds[L_RIC + 19];   // para_Td (0 unless estimate_td)
-  d4 D00 = {0, 0, 0, 0}, D10 = {0, 0, 0, 0}, D11 = {0, 0, 0, 0}, E00 = {0, 0, 0, 0}, E10 = {0, 0, 0, 0}, E11 = {0, 0, 0, 0};
-  const int drow = lane >> 4, dcol = lane & 15;
-  // COMPACT (no time offset in the problem: the reference's default): Jj's translation columns are minus Ji's (projection_factor.cpp:
-  // 81-95: both are +-reduce ric^T Rj^T), so the staged row is [Jj_r 0-2 | Ji_t 3-5 | Ji_r 6-8 | r 9 | Jex 10-15] - ONE 16-column tile
-  // and ONE X^T X product per k-step instead of three; the three Gram tiles the scatter below works on are read back out of it
-  // (entries of other lanes through ds_bpermute, signs for the columns that stand for Jj_t) when a frame ends.
-  const bool cp = !c.est_td;
-  auto gram_get = [&](const d4& G, int Rs, int Cs) {  // entry (Rs, Cs) of a 16 x 16 accumulator tile, for every lane its own
-    const int src = (Rs & 3) * 16 + Cs, q = Rs >> 2;
-    const double v0 = __shfl(G[0], src, 64), v1 = __shfl(G[1], src, 64), v2 = __shfl(G[2], src, 64), v3 = __shfl(G[3], src, 64);
-    return q == 0 ? v0 : (q == 1 ? v1 : (q == 2 ? v2 : v3));
-  };
-  auto cmap = [](int p, double& sg) {  // column p of [Jj | Ji | r] -> its column in the compact row, and its sign
-    sg = p < 3 ? -1.0 : 1.0;
-    return p < 3 ? 3 + p : (p < 6 ? p - 3 : (p < 9 ? p - 3 : (p < 12 ? p - 3 : 9)));
-  };
-  auto end_frame = [&](int b) {  // the blocks frame b owns, from the accumulators
-    double* PART = c.sc + Scratch::PART + (size_t)b * PARTW;
-    D00 += E00, D10 += E10, D11 += E11;
-    if (cp) {
-      const d4 G = D00 + D10;  // (all four chains of the one tile)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int row = drow + 4 * r;
-        double sr, sc2;
-        const int mr = cmap(min(row, 12), sr), mc = cmap(min(dcol, 12), sc2);
-        const double g00 = gram_get(G, mr, mc), g10 = gram_get(G, 10 + min(row, 5), mc), g11 = gram_get(G, 10 + min(row, 5), 10 + min(dcol, 5));
-        D00[r] = (row < 13 && dcol < 13) ? sr * sc2 * g00 : 0.0;
-        D10[r] = (row < 6 && dcol < 13) ? sc2 * g10 : 0.0;
-        D11[r] = (row < 6 && dcol < 6) ? g11 : 0.0;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int row = drow + 4 * r;
-      // D00: rows/cols over [Jj | Ji | r]
-      if (row < 6 && dcol <= row) lds[L_S + roff(6 * b + row) + 6 * b + dcol] = D00[r];                   // (b,b)
-      if (row < 6 && dcol >= 6 && dcol < 12) lds[L_S + roff(6 * b + row) + (dcol - 6)] = D00[r];          // (b,0)
-      if (row < 6 && dcol == 12) lds[M_G + 6 * b + row] = D00[r];                                         // g_b
-      if (row >= 6 && row < 12) {
-        const int i = row - 6;
-        if (dcol >= 6 && dcol < 12 && dcol - 6 <= i) PART[i * (i + 1) / 2 + (dcol - 6)] = D00[r];         // (0,0)
-        if (dcol == 12) PART[21 + i] = D00[r];                                                            // g_0
-      }
-      // D10: rows = [Jex | Jtd] (7), cols = [Jj | Ji | r]
-      if (row < 7) {
-        if (dcol < 6) PART[104 + row * 6 + dcol] = D10[r];                      // ([ex td], pose b)
-        if (dcol >= 6 && dcol < 12) PART[27 + row * 6 + (dcol - 6)] = D10[r];   // ([ex td], pose 0)
-        if (dcol == 12) PART[97 + row] = D10[r];                                // g_[ex td]
-        if (dcol <= row) PART[69 + row * (row + 1) / 2 + dcol] = D11[r];        // ([ex td], [ex td])
-      }
-    }
-    D00 = D10 = D11 = E00 = E10 = E11 = d4{0, 0, 0, 0};
-  };
-  // inputs of a chunk (feature id, its two observations) are fetched one chunk ahead, as in the solve's frame task (round 5: the
-  // id and then the observations were two dependent trips to memory at the top of every chunk)
-  int e_nx = 0, b_nx = b0, s0_nx = 0;
-  double ob_nx[4] = {0, 0, 0, 0};
-  auto fetch = [&](int chunk0) {
-    const int ic = min(chunk0 + lane, max(ntot - 1, 0));
-    b_nx = ic < n0 ? b0 : b1;
-    e_nx = c.cov[b_nx * MAXE + (ic < n0 ? ic : ic - n0)];  // (inactive lanes repeat the last factor: valid, never stored)
-    s0_nx = ids[I_FOBS + e_nx];
-    const int s = s0_nx + b_nx;
-    ob_nx[0] = c.obs[2 * s0_nx], ob_nx[1] = c.obs[2 * s0_nx + 1], ob_nx[2] = c.obs[2 * s], ob_nx[3] = c.obs[2 * s + 1];
-  };
-  if (ntot > 0) fetch(0);
-  for (int chunk0 = 0; chunk0 < ntot; chunk0 += 64) {
-    const int idx = chunk0 + lane;
-    const bool act = idx < ntot;
-    const int b = b_nx, e = e_nx, s0 = s0_nx, s = s0 + b;
-    const double ob0 = ob_nx[0], ob1 = ob_nx[1], ob2 = ob_nx[2], ob3 = ob_nx[3];
-    if (chunk0 + 64 < ntot) fetch(chunk0 + 64);
-    double r[2] = {0, 0}, Ji[12], Jj[12], Je[2] = {0, 0}, Jx[12], Jt[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 12; k++) Ji[k] = 0, Jj[k] = 0, Jx[k] = 0;
-    if (act) {
-      double ob[4] = {ob0, ob1, ob2, ob3}, ai[4] = {0, 0, 0, 0}, aj[4] = {0, 0, 0, 0};
-      if (c.est_td) {  // ProjectionTdFactor (estimator.cpp:874-885)
-#pragma unroll
-        for (int k = 0; k < 4; k++) ai[k] = c.aux[4 * s0 + k], aj[k] = c.aux[4 * s + k];
-        td_shift(ob, ai, aj, td, o.tr, o.row);
-      }
-      proj_eval<true>(xs, fr, lds + L_RIC, lds + L_RIC + 9, ob[0], ob[1], ob[2], ob[3], xs[XLAM + e], 0, b, sqi, o.cauchy_a, true, r, Ji, Jj,
-                      Je, Jx, Jt, ai[0], ai[1], aj[0], aj[1]);
-      if (!c.est_td) Jt[0] = Jt[1] = 0.0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) {
-        W[(size_t)(6 * b + k) * WLE + e] = Jj[k] * Je[0] + Jj[6 + k] * Je[1];
-        if (k >= 3) PF[(size_t)(k * NFR + b) * WLE + e] = Ji[k] * Je[0] + Ji[6 + k] * Je[1];  // (k < 3: minus W's entry, as in the solve's frame task)
-        PF2[(size_t)(k * NFR + b) * WLE + e] = Jx[k] * Je[0] + Jx[6 + k] * Je[1];
-      }
-      PF[(size_t)(6 * NFR + b) * WLE + e] = Je[0] * Je[0] + Je[1] * Je[1];
-      PF[(size_t)(7 * NFR + b) * WLE + e] = Je[0] * r[0] + Je[1] * r[1];
-      if (c.est_td) PF2[(size_t)(6 * NFR + b) * WLE + e] = Jt[0] * Je[0] + Jt[1] * Je[1];  // (without a time offset the per-feature sums take a zero instead)
-    }
-    // staged column-major like the solve kernel's frame tasks (Jj 0-5 | Ji 6-11 | r 12 | Jex 13-18): one 16-byte store
-    // per column, contiguous across the lanes; inactive lanes stage zeros, so no row needs masking.  The tile holds half
-    // a chunk: lanes 0-31 stage and the wavefront multiplies, then lanes 32-63.
-    const int nact = min(64, ntot - chunk0);
-#pragma unroll 1
-    for (int half = 0; half < 2; half++) {
-      const int nh = min(max(nact - 32 * half, 0), 32);
-      if (nh == 0) break;  // (uniform)
-      if ((lane >> 5) == half) {
-        dv2* st = reinterpret_cast<dv2*>(stage) + (lane & 31);
-        if (cp) {
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            st[k * (MXRS / 2)] = dv2{Jj[3 + k], Jj[9 + k]};
-            st[(3 + k) * (MXRS / 2)] = dv2{Ji[k], Ji[6 + k]};
-            st[(6 + k) * (MXRS / 2)] = dv2{Ji[3 + k], Ji[9 + k]};
-          }
-          st[9 * (MXRS / 2)] = dv2{r[0], r[1]};
-#pragma unroll
-          for (int k = 0; k < 6; k++) st[(10 + k) * (MXRS / 2)] = dv2{Jx[k], Jx[6 + k]};
-        } else {
-#pragma unroll
-          for (int k = 0; k < 6; k++) {
-            st[k * (MXRS / 2)] = dv2{Jj[k], Jj[6 + k]};
-            st[(6 + k) * (MXRS / 2)] = dv2{Ji[k], Ji[6 + k]};
-            st[(13 + k) * (MXRS / 2)] = dv2{Jx[k], Jx[6 + k]};
-          }
-          st[12 * (MXRS / 2)] = dv2{r[0], r[1]};
-          st[19 * (MXRS / 2)] = dv2{Jt[0], Jt[1]};
-        }
-      }
-      wave_lds_sync();
-      // the factors of frame b0 in this half, then those of b1 (either may be empty)
-      const int g0 = chunk0 + 32 * half;                      // list position of the half's first factor
-      const int nb0 = min(max(n0 - g0, 0), nh);               // factors of b0 in the half
-#pragma unroll 1
-      for (int run = 0; run < 2; run++) {
-        const int l = run == 0 ? 0 : nb0, l_end = run == 0 ? nb0 : nh;
-        if (l_end <= l) continue;  // (uniform)
-        if (run == 1 && g0 + l == n0 && n0 > 0) end_frame(b0);  // frame b1 begins exactly here: frame b0 is complete
-        // lane group drow takes the two rows of factor 4 j + drow (one 16-byte read per tile), four j at a time: 24 MFMAs on
-        // six independent chains; factors outside the run are masked out by their index
-        const int j_end = (l_end + 3) >> 2;
-        if (cp) {  // one tile: two MFMAs (the two residual rows) per k-step, eight in flight
-#pragma unroll 1
-          for (int j0 = l >> 2; j0 < j_end; j0 += 4) {
-            dv2 u0[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) u0[u] = *reinterpret_cast<const dv2*>(stage + dcol * MXRS + 8 * min(j0 + u, 7) + 2 * drow);
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-              const int f = 4 * (j0 + u) + drow;
-              const bool on = f >= l && f < l_end;
-              const double a0 = on ? u0[u][0] : 0.0, a1 = on ? u0[u][1] : 0.0;
-              if (u & 1) {
-                D10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a0, D10, 0, 0, 0);  // (D10 / E10: the second pair of chains of the
-                E10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a1, E10, 0, 0, 0);  //  same tile, folded into D00 below)
-              } else {
-                D00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a0, D00, 0, 0, 0);
-                E00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a1, E00, 0, 0, 0);
-              }
-            }
-          }
-          continue;
-        }
-#pragma unroll 1
-        for (int j0 = l >> 2; j0 < j_end; j0 += 4) {
-          dv2 u0[4], u1[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const int ro = 8 * min(j0 + u, 7) + 2 * drow;
-            u0[u] = *reinterpret_cast<const dv2*>(stage + min(dcol, 12) * MXRS + ro);
-            u1[u] = *reinterpret_cast<const dv2*>(stage + (13 + min(dcol, 6)) * MXRS + ro);
-          }
-#pragma unroll
-          for (int u = 0; u < 4; u++) {
-            const int f = 4 * (j0 + u) + drow;
-            const bool on = f >= l && f < l_end;
-            const double a0 = (on && dcol < 13) ? u0[u][0] : 0.0, a1 = (on && dcol < 13) ? u0[u][1] : 0.0;
-            const double x0 = (on && dcol < 7) ? u1[u][0] : 0.0, x1 = (on && dcol < 7) ? u1[u][1] : 0.0;
-            D00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, a0, D00, 0, 0, 0);
-            D10 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, a0, D10, 0, 0, 0);
-            D11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, x0, D11, 0, 0, 0);
-            E00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, a1, E00, 0, 0, 0);
-            E10 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, a1, E10, 0, 0, 0);
-            E11 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, x1, E11, 0, 0, 0);
-          }
-        }
-      }
-      wave_lds_sync();
-    }
-  }
-  // what is still in the accumulators belongs to the last frame with factors; a frame without factors owns zeros
-  if (n1 > 0) {
-    end_frame(b1);
-    if (n0 == 0) end_frame(b0);
-  } else {
-    end_frame(b0);
-    if (b1 < NFR) end_frame(b1);
-  }
-}
-
-// Cyclic Jacobi eigen-decomposition of the symmetric n x n matrix A (row-major, leading dimension ld) in LDS.
-// Only the LOWER triangle of A is read and written.  On return the diagonal of A holds the eigenvalues and
-// the columns of V the eigenvectors (A0 = V diag V^T).
-// Round-robin pairing: n/2 disjoint rotations per step.  A <- J^T A J is applied as independent 2x2 blocks
-// (rows of pair k1, columns of pair k2, k1 >= k2); V <- V J with threads grouped by pair so the rotation is
-// loaded once for several rows.  The step is LDS-instruction bound, so every access is kept to the minimum:
-// rotation table read as double2 / int2, no mirrored writes.  Two barriers per step.
-template <int NTH>
-AVM_NOINL int jacobi_eig_lds(int A_off, int V_off, int n, int ld, int rot_off) {
-  double* A = LDS() + A_off;
-  double* V = LDS() + V_off;
-  double2* rcs = reinterpret_cast<double2*>(LDS() + rot_off);        // [np] (c, s)
-  int2* rpq = reinterpret_cast<int2*>(LDS() + rot_off + 2 * 64);     // [np] (p, q), p < q
-  double* red = LDS() + L_RED;
-  constexpr bool WAVE = NTH == 64;  // a single wavefront: wave-level ordering of its LDS traffic is enough
-  auto sync = [&]() {
-    if (WAVE)
-      wave_lds_sync();
-    else
-      __syncthreads();
-  };
-  const int t = WAVE ? (threadIdx.x & 63) : threadIdx.x;
-  const int ne = (n + 1) & ~1, np = ne >> 1;
-  for (int i = t; i < n * n; i += NTH) V[(i / n) * ld + i % n] = (i / n == i % n) ? 1.0 : 0.0;
-  // static work assignment
-  //  - blocks (k1 >= k2): up to MAXB per thread
-  //  - V: thread -> pair kv = t / tpp, rows (t % tpp) + tpp * m
-  constexpr int MAXB = 3, MAXR = 8;
-  const int nblk = np * (np + 1) / 2;
-  short bk1[MAXB], bk2[MAXB];
-#pragma unroll
-  for (int u = 0; u < MAXB; u++) {
-    const int idx = t + u * NTH;
-    bk1[u] = -1, bk2[u] = 0;
-    if (idx < nblk) {
-      int k1 = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
-      while ((k1 + 1) * (k1 + 2) / 2 <= idx) k1++;
-      while (k1 * (k1 + 1) / 2 > idx) k1--;
-      bk1[u] = (short)k1, bk2[u] = (short)(idx - k1 * (k1 + 1) / 2);
-    }
-  }
-  const int tpp = max(1, NTH / np);          // threads per pair for the V update
-  const int kv = t / tpp, rv0 = t % tpp;     // pair and first row of this thread (kv >= np: idle)
-  sync();
-  auto Lw = [&](int i, int j) -> double& { return A[max(i, j) * ld + min(i, j)]; };
-  int sweeps = 0;
-  for (int sweep = 0; sweep < 20; sweep++) {
-    // converged when every |a_pq| <= tol sqrt(a_pp a_qq) (relative criterion: keeps the small eigenvalues
-    // accurate, which matters for the 1e-8 clamp next to eigenvalues of 1e12)
-    double off = 0;
-    for (int i = t; i < n * n; i += NTH) {
-      const int r = i / n, q = i % n;
-      if (r <= q) continue;
-      const double v = fabs(A[r * ld + q]);
-      const double sc = sqrt(fabs(A[r * ld + r]) * fabs(A[q * ld + q]));
-      off = fmax(off, sc > 0.0 ? v / sc : (v > 0.0 ? 1.0 : 0.0));
-    }
-    if (WAVE) {
-      off = wave_max(off);
-    } else {
-      off = block_max<NTH>(off, red);
-    }
-    if (off <= 1e-15) break;
-    sweeps++;
-    for (int step = 0; step < ne - 1; step++) {
-      if (t < np) {
-        const int a = t == 0 ? ne - 1 : (step + t) % (ne - 1);
-        const int b = t == 0 ? step : (step - t + (ne - 1)) % (ne - 1);
-        const int pI = min(a, b), qI = max(a, b);
-        double cs = 1.0, sn = 0.0;
-        if (qI < n) {
-          const double apq = A[qI * ld + pI];
-          if (fabs(apq) > 1e-300) {
-            const double tau = (A[qI * ld + qI] - A[pI * ld + pI]) / (2.0 * apq);
-            const double tt = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            cs = fast_rsqrt(1.0 + tt * tt);
-            sn = tt * cs;
-          }
-        }
-        rcs[t] = double2{cs, sn};
-        rpq[t] = int2{pI, qI};
-      }
-      sync();
-#pragma unroll
-      for (int u = 0; u < MAXB; u++) {
-        if (bk1[u] < 0) continue;
-        const int k1 = bk1[u], k2 = bk2[u];
-        const int2 pq1 = rpq[k1], pq2 = rpq[k2];
-        const double2 r1v = rcs[k1], r2v = rcs[k2];
-        const int p1 = pq1.x, q1 = pq1.y, p2 = pq2.x, q2 = pq2.y;
-        const double c1 = r1v.x, s1 = r1v.y, c2 = r2v.x, s2 = r2v.y;
-        const bool r1 = q1 < n, r2 = q2 < n;  // a dummy partner (odd n) leaves its line untouched (c = 1, s = 0)
-        if (k1 != k2) {
-          double& e00 = Lw(p1, p2);
-          const double a00 = e00, a01 = r2 ? Lw(p1, q2) : 0.0, a10 = r1 ? Lw(q1, p2) : 0.0, a11 = (r1 && r2) ? Lw(q1, q2) : 0.0;
-          const double b00 = c1 * a00 - s1 * a10, b01 = c1 * a01 - s1 * a11;
-          const double b10 = s1 * a00 + c1 * a10, b11 = s1 * a01 + c1 * a11;
-          e00 = c2 * b00 - s2 * b01;
-          if (r2) Lw(p1, q2) = s2 * b00 + c2 * b01;
-          if (r1) Lw(q1, p2) = c2 * b10 - s2 * b11;
-          if (r1 && r2) Lw(q1, q2) = s2 * b10 + c2 * b11;
-        } else {
-          // diagonal block of the pair itself: [app apq; apq aqq] -> diag(app - t apq, aqq + t apq)
-          const double app = A[p1 * ld + p1];
-          if (r1) {
-            const double aqq = A[q1 * ld + q1], apq = A[q1 * ld + p1];
-            A[p1 * ld + p1] = c1 * c1 * app - 2.0 * c1 * s1 * apq + s1 * s1 * aqq;
-            A[q1 * ld + q1] = s1 * s1 * app + 2.0 * c1 * s1 * apq + c1 * c1 * aqq;
-            A[q1 * ld + p1] = (c1 * c1 - s1 * s1) * apq + c1 * s1 * (app - aqq);
-          }
-        }
-      }
-      if (kv < np) {
-        const int2 pq = rpq[kv];
-        if (pq.y < n) {
-          const double2 cs2 = rcs[kv];
-#pragma unroll
-          for (int m = 0; m < MAXR; m++) {
-            const int i = rv0 + tpp * m;
-            if (i < n) {
-              const double x = V[i * ld + pq.x], y = V[i * ld + pq.y];
-              V[i * ld + pq.x] = cs2.x * x - cs2.y * y;
-              V[i * ld + pq.y] = cs2.y * x + cs2.x * y;
-            }
-          }
-        }
-      }
-      sync();
-    }
-  }
-  return sweeps;
-}
-
-// Fast path of the 16 x 16 pseudo-inverse of the marginalization (Amm^+ = V diag(lambda > eps ? 1 / lambda : 0) V^T,
-// marginalization_factor.cpp:283-286) for the usual case that NO eigenvalue is clamped: then Amm^+ is the plain inverse,
-// which one wavefront gets from the same register-resident square-root-free Cholesky as the solve's diagonal blocks
-// (lanes 0..15 = rows, lanes 16..31 = rows of the identity -> L^-T), ~3K cycles instead of ~135K for the Jacobi sweeps.
-// The condition is checked rigorously: lambda_min >= 1 / trace(Amm^-1), so "trace(Amm^-1) < 1 / eps" (and positive
-// pivots) proves that every eigenvalue is above eps; otherwise the caller falls back to the eigen-decomposition.
-// On success the result is handed over in the eigen-solver's output format: EV[i][c] = (L D^1/2)^-T rows, diag(EA) = the
-// pivots d_c, so that EV diag(1 / d) EV^T = Amm^-1.  EA is left untouched on failure.  Call with one full wavefront.
-AVM_NOINL bool pinv16_cholesky(double* EA, double* EV, int m, double eps) {  // (outlined: its sixteen-register row was spilled inside the kernel body)
-  constexpr int NB = 16;
-  const int r = threadIdx.x & 63;
-  const bool idl = (r & 48) == 16;
-  double a[NB];
-  {
-    const int rc = r & 15;
-#pragma unroll
-    for (int k = 0; k < NB; k++) a[k] = idl ? (rc == k ? 1.0 : 0.0) : EA[rc * NB + min(k, rc)];
-  }
-  double uprev = 0.0, dvec = 1.0;
-#pragma unroll
-  for (int j = 0; j < NB; j++) {
-    if (j > 0) a[j] = fma(-uprev, readlane_d(a[j - 1], j), a[j]);
-    const double djj = readlane_d(a[j], j);
-    dvec = (r & 15) == j ? djj : dvec;
-    double y = __builtin_amdgcn_rcp(djj), e = 0;
-#define AVM_TAIL(slot)                                                                                                 \
-  if (j > 0) {                                                                                                         \
-    double sk[3];                                                                                                      \
-    _Pragma("unroll") for (int q = 0; q < 3; q++) sk[q] = readlane_d(a[j - 1], min(j + 1 + (slot) + 5 * q, NB - 1));   \
-    _Pragma("unroll") for (int q = 0; q < 3; q++)                                                                      \
-      if (j + 1 + (slot) + 5 * q < NB) a[j + 1 + (slot) + 5 * q] = fma(-uprev, sk[q], a[j + 1 + (slot) + 5 * q]);      \
-  }
-    AVM_TAIL(0)
-    e = fma(-djj, y, 1.0);
-    AVM_TAIL(1)
-    y = fma(y, e, y);
-    AVM_TAIL(2)
-    e = fma(-djj, y, 1.0);
-    AVM_TAIL(3)
-    y = fma(y, e, y);
-    AVM_TAIL(4)
-#undef AVM_TAIL
-    uprev = a[j] * y;
-  }
-  // trace(Amm^-1) = sum_i sum_c x_i[c]^2 / d_c over the real indices; pivots must be positive
-  double tr = 0.0;
-  bool bad = false;
-#pragma unroll
-  for (int c = 0; c < NB; c++) {
-    const double dc = readlane_d(dvec, c);
-    if (c < m) {
-      bad |= !(dc > 0.0);
-      tr = fma(a[c] * a[c], 1.0 / dc, tr);
-    }
-  }
-  tr = (idl && (r & 15) < m) ? tr : 0.0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) tr += __shfl_xor(tr, off, 64);
-  const bool fast = !bad && tr * eps < 1.0;  // (NaN compares false)
-  if (fast) {
-    if (idl) {
-#pragma unroll
-      for (int c = 0; c < NB; c++) EV[(r & 15) * NB + c] = a[c];
-    }
-    wave_lds_sync();
-    if (r < NB) EA[r * NB + r] = dvec;  // pad indices (>= m) carry pivot 1 and are masked by the consumer
-  }
-  return fast;
-}
-
-#ifdef AVM_TP
-#define AVM_MARG_KERNEL marginalize_tp_kernel
-#define AVM_MARG_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))  // two four-wavefront workgroups per CU, like the solve beside it
-#else
-#define AVM_MARG_KERNEL marginalize_kernel
-#define AVM_MARG_OCC
-#endif
-__global__ __launch_bounds__(NT) AVM_MARG_OCC void AVM_MARG_KERNEL(SolveArgs A, avm_prior_out PO, int* err, double* scale_out) {
-  lds_base_check();
-  AVM_PRIO_LIGHT();
-  using namespace mg;
-  double* lds = LDS();
-  int* ids = reinterpret_cast<int*>(lds + L_INT);
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const avm_options& o = lds_opt();
-  const avm_window_batch& B = A.b;
-  const int flag = A.opt.marginalization_flag;
-  for (int w = blockIdx.x; w < B.n_windows; w += gridDim.x) {
-    WinCtx cl;
-    cl.prof = A.prof ? as_global(A.prof + (size_t)blockIdx.x * PROF_SLOTS) : nullptr;
-    cl.sc = as_global(A.scratch + (size_t)blockIdx.x * Scratch::TOTAL);
-    cl.osf = as_global(A.iscratch + (size_t)blockIdx.x * ISCRATCH);
-    cl.cov = cl.osf + MAXOBS;
-    cl.w = w;
-    cl.nf = B.n_feat[w];
-    cl.obs = as_global(B.obs_xy + (size_t)w * B.max_obs * 2);
-    cl.pdelta = as_global(A.pre_delta + (size_t)w * 100), cl.pjac = as_global(A.pre_jac + (size_t)w * 2250), cl.psqrt = as_global(A.pre_sqrt + (size_t)w * 2250);
-    cl.psum = as_global(A.pre_sum_dt + (size_t)w * 10);
-    cl.lba = as_global(B.imu_lin_ba + (size_t)w * 30), cl.lbg = as_global(B.imu_lin_bg + (size_t)w * 30);
-    cl.pn = B.prior_n ? B.prior_n[w] : 0;
-    cl.pnblk = cl.pn > 0 ? B.prior_nblk[w] : 0;
-    cl.ldp = B.max_prior;
-    cl.pJ = as_global(B.prior_J + (size_t)w * B.max_prior * B.max_prior);
-    cl.pr = as_global(B.prior_r + (size_t)w * B.max_prior);
-    cl.px0 = as_global(B.prior_x0 + (size_t)w * B.max_pblk * 9);
-    cl.nobs_tot = 0;
-    cl.est_ex = 0, cl.est_td = (A.opt.estimate_td != 0 && B.obs_vel_td && B.td) ? 1 : 0;
-    cl.aux = cl.est_td ? as_global(B.obs_vel_td + (size_t)w * B.max_obs * 4) : nullptr;
-    cl.relo_n = 0, cl.has_relo = 0, cl.relo_xy = nullptr;  // (the relocalization factors take no part in the marginalization)
-    __syncthreads();  // the previous window's readers of the LDS context are done
-    lds_store_ctx(cl, A.opt);
-    const WinCtx& c = lds_ctx();
-    __syncthreads();
-    PROF_T0();
-    // ---- load the post-solve state and tables.  Every table entry of this thread is requested before the first one is stored (round 5:
-    // written as one loop per table, each load waited for its own store - eight dependent trips to memory per window, half of this phase)
-    static_assert(NT >= 160 && 99 <= NT && MAXE <= NT, "one entry of every table per thread");
-    {
-      const int nfl = c.nf, npb = c.pnblk;
-      constexpr int PBT0 = NT >= 512 ? 256 : 160;
-      const bool in_f = t < nfl, in_pb = t >= PBT0 && t < PBT0 + npb;
-      const int kpb = in_pb ? t - PBT0 : 0;
-      const double v_pose = B.pose[(size_t)w * 77 + min(t, 76)], v_sb = B.speedbias[(size_t)w * 99 + min(t, 98)];
-      const double v_lam = in_f ? B.inv_depth[(size_t)w * B.max_feat + t] : 1.0;
-      const size_t kf = (size_t)w * B.max_feat + (in_f ? t : 0);
-      const int v_fs = B.feat_start[kf], v_fn = B.feat_nobs[kf], v_fo = B.feat_obs_begin[kf];
-      const double v_ex = B.ex_pose[(size_t)w * 7 + min(t, 6)];
-      const double v_td = (t == 7 && c.est_td) ? B.td[w] : 0.0;
-      const int v_pk = in_pb ? B.prior_blk_kind[(size_t)w * B.max_pblk + kpb] : 0, v_pf = in_pb ? B.prior_blk_frame[(size_t)w * B.max_pblk + kpb] : 0;
-      double ex[7] = {0, 0, 0, 0, 0, 0, 1};
-      if (t == 0) {
-#pragma unroll
-        for (int k = 0; k < 7; k++) ex[k] = B.ex_pose[(size_t)w * 7 + k];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      for (int i = t; i < MAXPRIOR; i += NT) lds[L_DXP + i] = 0.0, lds[L_RP + i] = 0.0;
-#ifdef AVM_TP
-      for (int i = t; i < MROWS; i += NT) lds[L_S + i] = 0.0;
-      for (int i = t; i < VEC; i += NT) lds[M_G + i] = 0.0;
-      for (int i = t; i < 152; i += NT) lds[M_GE + i] = 0.0;
-#else
-      for (int i = t; i < MROWS + 176 + 152; i += NT) lds[i] = 0.0;  // S, b, g_e
-#endif
-      for (int i = t; i < 152; i += NT) lds[L_HEE + i] = 0.0;
-      if (t < 77) lds[L_X + t] = v_pose;
-      if (t < 99) lds[L_X + XSB + t] = v_sb;
-      if (t < MAXE) lds[L_X + XLAM + t] = v_lam;
-      if (in_f) ids[I_FSTART + t] = v_fs, ids[I_FNOBS + t] = v_fn, ids[I_FOBS + t] = v_fo;
-      if (t < 7) lds[L_RIC + 12 + t] = v_ex;
-      if (t == 7) lds[L_RIC + 19] = v_td;  // para_Td
-      if (in_pb) ids[I_PBLK + kpb * 3] = v_pk, ids[I_PBLK + kpb * 3 + 1] = v_pf;  // the prior's block table
-      if (t == 0) {
-        double R[9];
-        q2R(quat{ex[6], ex[3], ex[4], ex[5]}, R);
-        for (int k = 0; k < 9; k++) lds[L_RIC + k] = R[k];
-        for (int k = 0; k < 3; k++) lds[L_RIC + 9 + k] = ex[k];
-      }
-    }
-    __syncthreads();
-    if (t == 0) {  // offsets and state columns of the prior's blocks (read after the barrier that precedes phase A)
-      int off = 0;
-      for (int k = 0; k < c.pnblk; k++) {
-        const int kind = ids[I_PBLK + k * 3], fr = ids[I_PBLK + k * 3 + 1];
-        ids[I_PBLK + k * 3 + 2] = off;
-        const int n = kind == AVM_BLK_SPEEDBIAS ? 9 : (kind == AVM_BLK_TD ? 1 : 6);
-        for (int q = 0; q < n; q++)
-          ids[I_PIDX + off + q] = kind == AVM_BLK_POSE ? fr * 6 + q : (kind == AVM_BLK_SPEEDBIAS ? SB0 + fr * 9 + q : (kind == AVM_BLK_TD ? MTD : MEX0 + q));
-        off += n;
-      }
-    }
-    // does the prior take part?  MARGIN_SECOND_NEW needs pose[WINDOW_SIZE-1] in it (estimator.cpp:926-927)
-    bool use_prior = c.pn > 0;
-    bool has9 = false;
-    for (int k = 0; k < c.pnblk; k++)
-      if (ids[I_PBLK + k * 3] == AVM_BLK_POSE && ids[I_PBLK + k * 3 + 1] == AVM_WINDOW_SIZE - 1) has9 = true;
-    if (flag == AVM_MARGIN_SECOND_NEW && !(use_prior && has9)) {
-      if (t == 0) PO.n[w] = -1, PO.nblk[w] = 0;  // nothing to do: the caller keeps the old prior
-      continue;
-    }
-    const bool imu0 = flag == AVM_MARGIN_OLD && c.psum[0] < o.max_sum_dt;  // estimator.cpp:841
-    if (flag == AVM_MARGIN_OLD) {
-      for (int f = 1 + wv; f < NFR; f += NT / 64) {  // start-frame-0 features observed in frame f (ballot compaction, see the solve)
-        int n = 0;
-        for (int e0 = 0; e0 < c.nf; e0 += 64) {
-          const int e = min(e0 + lane, MAXE - 1);
-          const bool in = e0 + lane < c.nf && ids[I_FSTART + e] == 0 && f < ids[I_FNOBS + e];
-          const unsigned long long m = __ballot(in);
-          if (in) c.cov[f * MAXE + n + __popcll(m & ((1ull << lane) - 1ull))] = e;
-          n += __popcll(m);
-        }
-        if (lane == 0) ids[I_NCOV + f] = n;
-      }
-    } else if (t < NFR) {
-      ids[I_NCOV + t] = 0;
-    }
-    if (t == 0) ids[I_NCOV] = 0;
-    build_frames(L_X, 0);
-    double* IJR = c.sc + Scratch::IJRAW;
-    for (int i = t; i < 465; i += NT) IJR[i] = 0.0;
-    __syncthreads();
-    int nf0 = 0;  // features starting at frame 0 (they come first)
-    for (int e0 = 0; e0 < c.nf; e0 += 64) nf0 += __popcll(__ballot(e0 + lane < c.nf && ids[I_FSTART + min(e0 + lane, MAXE - 1)] == 0));
-    PROF(c, 16);
-    // ---- phase A: projection factors of the start-0 features || IMU factor 0
-#ifdef AVM_TP
-    {
-      // four wavefronts, one per SIMD: frames {1 8 9} {2 7 10} {3 6} {4 5} (a start-0 feature's track ends early or late: the factor
-      // counts fall with the frame, and this deal keeps the sums level), a pair as one list of factors, the third frame after it;
-      // wavefront 2 then takes IMU factor 0 and two fifths of the old prior's rows, wavefront 3 the other three fifths (each reads J0
-      // along its own rows only; the partial gradients are added in phase E, as in the solve)
-      static_assert(NFR == 11 && MASM == 4, "the deal below");
-      const int stage = L_S + SPP + wv * MXSTG;
-      AVM_PRIO_BULK();
-      switch (wv) {
-        case 0: marg_frame_task(c, o, 1, 8, stage), marg_frame_task(c, o, 9, NFR, stage); break;
-        case 1: marg_frame_task(c, o, 2, 7, stage), marg_frame_task(c, o, 10, NFR, stage); break;
-        case 2: marg_frame_task(c, o, 3, 6, stage); break;
-        default: marg_frame_task(c, o, 4, 5, stage); break;
-      }
-      AVM_PRIO_LIGHT();
-      if (wv == 2 && lane == 0 && imu0) marg_imu0_raw();
-      if (wv >= 2 && use_prior) {
-        const int h = (3 * c.pn + 2) / 5;
-        if (wv == 2)
-          marg_prior_wave(h, c.pn, L_DX2);
-        else
-          marg_prior_wave(0, h, L_DXP);
-      }
-    }
-#else
-    if (wv < MASM) {
-      marg_frame_task(c, o, 1 + wv, 1 + wv + MASM, L_S + SPP + wv * MXSTG);  // this wavefront's (at most two) frames
-      static_assert(1 + 2 * MASM >= NFR, "two frames per wavefront cover all frames");
-    } else if (wv == 7) {
-      if (lane == 0 && imu0) marg_imu0_raw();
-      // ... and the old prior's residual and gradient (MarginalizationFactor at the current state): dx, r_p, J0^T r_p
-      if (use_prior) marg_prior_wave(0, c.pn, L_DXP);
-    }
-#endif
-    __syncthreads();
-    PROF(c, 17);
-    // ---- phase B: per-feature sums, PART gather
-    marg_feature_sums(nf0);
-    __syncthreads();  // staging dead: rows >= 66 can be cleared, then the PART sums land (incl. the ex_pose rows)
-    for (int i = SPP + t; i < MROWS; i += NT) lds[L_S + i] = 0.0;
-    __syncthreads();
-    if (flag == AVM_MARGIN_OLD && t < PARTW) {
-      const double* PART = c.sc + Scratch::PART;
-      const int q = t;  // (rows MEX0 .. MEX0 + 6 = the six ex_pose variables and td)
-      // (every frame's PART row was written by its frame task - zeros for a frame without factors -, so all ten loads go out at once:
-      //  behind the `I_NCOV > 0` test they were ten dependent trips to the slot)
-      double pv[NFR - 1];
-#pragma unroll
-      for (int b = 1; b < NFR; b++) pv[b - 1] = PART[(size_t)b * PARTW + q];
-      if (q < 104) {
-        double sacc = 0;
-#pragma unroll
-        for (int b = 1; b < NFR; b++) sacc += ids[I_NCOV + b] > 0 ? pv[b - 1] : 0.0;
-        if (q < 21) {
-          int i = 0;
-          while ((i + 1) * (i + 2) / 2 <= q) i++;
-          lds[L_S + roff(i) + (q - i * (i + 1) / 2)] = sacc;
-        } else if (q < 27) {
-          lds[M_G + (q - 21)] = sacc;
-        } else if (q < 69) {
-          lds[L_S + roff(MEX0 + (q - 27) / 6) + (q - 27) % 6] = sacc;
-        } else if (q < 97) {
-          const int k = q - 69;
-          int i = 0;
-          while ((i + 1) * (i + 2) / 2 <= k) i++;
-          lds[L_S + roff(MEX0 + i) + MEX0 + (k - i * (i + 1) / 2)] = sacc;
-        } else {
-          lds[M_G + MEX0 + (q - 97)] = sacc;
-        }
-      } else {
-        const int k = q - 104;
-#pragma unroll
-        for (int b = 1; b < NFR; b++)
-          if (ids[I_NCOV + b] > 0) lds[L_S + roff(MEX0 + k / 6) + 6 * b + k % 6] = pv[b - 1];
-      }
-    }
-    __syncthreads();
-    PROF(c, 18);
-    // ---- phase D: IMU factor 0
-    if (imu0) marg_imu0_gram();
-    PROF(c, 19);
-    // ---- phase E: old prior (MarginalizationFactor at the current state)
-    if (use_prior) {
-      const int* pidx = ids + I_PIDX;
-      prior_jtj_add_lds(c.pJ, c.ldp, c.pn, L_S);
-#ifdef AVM_TP
-      if (t < c.pn) lds[M_G + pidx[t]] += lds[L_DXP + t] + lds[L_DX2 + t];  // g += J0^T r_p (the two shares of phase A)
-#else
-      if (t < c.pn) lds[M_G + pidx[t]] += lds[L_DXP + t];  // g += J0^T r_p (left in lds[L_DXP] by phase A)
-#endif
-    }
-    __syncthreads();
-    PROF(c, 20);
-    // ---- phase F: eliminate the start-0 inverse depths (scalar pivots)
-    if (flag == AVM_MARGIN_OLD && nf0 > 0) {
-      if (t < MAXE) lds[L_HEE + t] = (t < nf0 && lds[L_HEE + t] > o.marg_eps) ? 1.0 / lds[L_HEE + t] : 0.0;  // 1 / E^T E in place
-      __syncthreads();
-      marg_schur_phase(nf0);
-    }
-    __syncthreads();
-    PROF(c, 21);
-    // ---- phase G: dropped / kept variable lists (ints at I_FSTART.. are dead now)
-    int* midx = ids + 0;       // [<=16]
-    int* kidx = ids + 16;      // [<=96]
-    int* kblk = ids + 120;     // [<=16] id of kept block k : pose f -> f, speedbias f -> 11+f, ex -> 22, td -> 23
-    int* cnts = ids + 140;     // m, n, nblk
-    __syncthreads();
-    if (t == 0) {
-      int present = 0;  // bit id
-      for (int k = 0; k < c.pnblk; k++) {
-        const int kind = ids[I_PBLK + k * 3], fr = ids[I_PBLK + k * 3 + 1];
-        present |= 1 << (kind == AVM_BLK_POSE ? fr : (kind == AVM_BLK_SPEEDBIAS ? 11 + fr : (kind == AVM_BLK_TD ? 23 : 22)));
-      }
-      if (!use_prior) present = 0;
-      int m = 0, n = 0, nb = 0;
-      if (flag == AVM_MARGIN_OLD) {
-        if (imu0) present |= (1 << 0) | (1 << 11) | (1 << 1) | (1 << 12);
-        if (nf0 > 0) present |= (1 << 0) | (1 << 22) | (c.est_td ? 1 << 23 : 0);  // ProjectionTdFactor keeps para_Td (estimator.cpp:880-883)
-        for (int b = 1; b < NFR; b++)
-          if (ids[I_NCOV + b] > 0) present |= 1 << b;
-        for (int q = 0; q < 6; q++) midx[m++] = q;
-        for (int q = 0; q < 9; q++) midx[m++] = SB0 + q;
-        present &= ~((1 << 0) | (1 << 11));
-      } else {
-        for (int q = 0; q < 6; q++) midx[m++] = 6 * (AVM_WINDOW_SIZE - 1) + q;
-        present &= ~(1 << (AVM_WINDOW_SIZE - 1));
-      }
-      for (int id = 0; id < 24; id++) {
-        if (!(present & (1 << id))) continue;
-        const int base = id < 11 ? 6 * id : (id < 22 ? SB0 + 9 * (id - 11) : (id == 23 ? MTD : MEX0));
-        const int sz = (id >= 11 && id < 22) ? 9 : (id == 23 ? 1 : 6);
-        if (n + sz > MAXKEEP || n + sz > PO.max_prior || nb >= MAXPBLK || nb >= PO.max_pblk) {
-          atomicMin(err, w);  // (lowest failing window) the host turns this into AVM_ERR_CAPACITY: a truncated kept set would silently lose information
-          break;
-        }
-        kblk[nb++] = id;
-        for (int q = 0; q < sz; q++) kidx[n++] = base + q;
-      }
-      cnts[0] = m, cnts[1] = n, cnts[2] = nb;
-    }
-    __syncthreads();
-    const int m = cnts[0], n = cnts[1], nblk = cnts[2];
-    // extract Amm (16x16 at EA), Arm (n x 16 at EB), Arr (n x n), b before the packed matrix is overwritten
-    auto Sget = [&](int i, int j) { return lds[L_S + roff(max(i, j)) + min(i, j)]; };
-    double* EA = lds + M_WCH;            // Amm 16 x 16, then its eigenvectors next to it
-    double* EV = EA + 256;               // 16 x 16
-    double* EB = EV + 256;               // Arm : n x 16   (n <= 96 -> 1536)  (M_WCH region holds 1920+; spills into the dead L_G.. vectors)
-    // (the 16x16 eigen-solver keeps its rotation records at L_HEE: hee / dxp / rp are dead by now)
-    double* BV = lds + L_FR + 198;       // b_m (16), b_r (96): the candidate-state frame slot is unused here
-    for (int idx = t; idx < 16 * 16; idx += NT) {
-      const int i = idx / 16, j = idx % 16;
-      EA[idx] = (i < m && j < m) ? 0.5 * (Sget(midx[i], midx[j]) + Sget(midx[j], midx[i])) : (i == j ? 1.0 : 0.0);
-    }
-    for (int idx = t; idx < n * 16; idx += NT) {
-      const int i = idx / 16, j = idx % 16;
-      EB[idx] = j < m ? Sget(kidx[i], midx[j]) : 0.0;
-    }
-    if (t < 16) BV[t] = t < m ? lds[M_G + midx[t]] : 0.0;
-    if (t >= 64 && t < 64 + n) BV[16 + t - 64] = lds[M_G + kidx[t - 64]];
-    __syncthreads();
-    PROF(c, 22);
-    // pseudo-inverse of Amm: Cholesky fast path when provably no eigenvalue is clamped, else the eigen-decomposition
-    if (t < 64) {
-      const bool fast = pinv16_cholesky(EA, EV, m, o.marg_eps);
-      if (t == 0) cnts[3] = fast ? 1 : 0;
-    }
-    __syncthreads();
-    if (!cnts[3]) {
-      if (t < 64) jacobi_eig_lds<64>(M_WCH, M_WCH + 256, 16, 16, L_HEE);  // 16 x 16: one wavefront, no block barriers
-      __syncthreads();
-    }
-    PROF(c, 23);
-    // Amm^+ = V diag(1/lambda > eps) V^T  -> EA (reuse) ; T = Arm Amm^+ ; A' = Arr - T Amr ; b' = br - T bm
-    {
-      // (1 / lambda once, by sixteen threads, through LDS - g_e's array is dead since phase F: every thread used to divide sixteen times)
-      double* lam_inv = lds + M_GE;
-      if (t < 16) lam_inv[t] = (t < m && EA[t * 16 + t] > o.marg_eps) ? 1.0 / EA[t * 16 + t] : 0.0;
-      __syncthreads();
-      if (t < 256) {
-        const int i = t / 16, j = t % 16;
-        double sacc = 0;
-        for (int k = 0; k < 16; k++) sacc += EV[i * 16 + k] * lam_inv[k] * EV[j * 16 + k];
-        EA[t] = (i < m && j < m) ? sacc : 0.0;
-      }
-      __syncthreads();
-    }
-    // T = Arm Amm^+ : n x 16, in the LDS range of the solve's gradient / scaling vectors (unused here; it was in the scratch slot:
-    // every entry of A' then waited for 16 trips to its memory)
-#ifndef AVM_TP
-    static_assert(MAXKEEP * 16 <= L_X - L_G, "T fits the dead vectors");
-#endif
-    static_assert(MAXKEEP <= 96, "T / Arm: 96 rows");
-    double* GT = lds + M_GT;
-    for (int idx = t; idx < n * 16; idx += NT) {
-      const int i = idx / 16, j = idx % 16;
-      double sacc = 0;
-      for (int k = 0; k < 16; k++) sacc += EB[i * 16 + k] * EA[k * 16 + j];
-      GT[idx] = sacc;
-    }
-    __syncthreads();
-    // A' and b' go to the output slots PO.J / PO.r; prior_eig_kernel (prior_eig.hip) turns them into
-    // linearized_jacobians / linearized_residuals in place
-    {
-      double* oJ = PO.J + (size_t)w * PO.max_prior * PO.max_prior;
-      double* orr = PO.r + (size_t)w * PO.max_prior;
-      // T Amr by 16 x 16 tiles on the matrix cores (K = the 16 dropped columns): lower tiles only - the eigen-solver reads the lower
-      // triangle only, as Eigen's SelfAdjointEigenSolver does - dealt to the wavefronts; operands straight from LDS (the scalar form
-      // read 32 LDS words per entry: 11 K cycles per window)
-      {
-        const int lr = lane & 15, lk = lane >> 4, ntl = (n + 15) >> 4;
-        for (int tile = wv; tile < ntl * (ntl + 1) / 2; tile += NT / 64) {
-          int ti = 0;
-          while ((ti + 1) * (ti + 2) / 2 <= tile) ti++;
-          const int tj = tile - ti * (ti + 1) / 2;
-          const int ra = min(16 * ti + lr, n - 1), rb = min(16 * tj + lr, n - 1);
-          d4 D = {0, 0, 0, 0};
-#pragma unroll
-          for (int mq = 0; mq < 4; mq++) D = __builtin_amdgcn_mfma_f64_16x16x4f64(GT[ra * 16 + lk + 4 * mq], EB[rb * 16 + lk + 4 * mq], D, 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const int i = 16 * ti + lk + 4 * r, j = 16 * tj + lr;
-            if (i < n && j <= i) {
-              const double arr = Sget(kidx[i], kidx[j]), sacc = D[r];
-              oJ[(size_t)i * PO.max_prior + j] = arr - sacc;
-              // The magnitude the diagonal entry was formed at (|Arr_ii| + |(Arm Amm^+ Amr)_ii|: the bias rows of the kept
-              // speed-bias block are differences of two numbers of size 1e10 .. 1e12) goes to the ctx's scale array:
-              // prior_eig_kernel's clamp measures an eigenvalue against the rounding noise of ITS variables (prior_eig.hip).
-              if (i == j) scale_out[(size_t)w * PO.max_prior + i] = fabs(arr) + fabs(sacc);
-            }
-          }
-        }
-      }
-      if (t < n) {
-        double sacc = 0;
-        for (int k = 0; k < 16; k++) sacc += GT[t * 16 + k] * BV[k];
-        orr[t] = BV[16 + t] - sacc;
-      }
-      PROF(c, 24);
-      if (t < nblk) {
-        const int id = kblk[t];
-        const int kind = id < 11 ? AVM_BLK_POSE : (id < 22 ? AVM_BLK_SPEEDBIAS : (id == 23 ? AVM_BLK_TD : AVM_BLK_EXPOSE));
-        int fr = id < 11 ? id : (id < 22 ? id - 11 : 0);
-        if (kind == AVM_BLK_POSE || kind == AVM_BLK_SPEEDBIAS) {
-          if (flag == AVM_MARGIN_OLD)
-            fr -= 1;  // addr_shift, estimator.cpp:904-909
-          else if (fr == AVM_WINDOW_SIZE)
-            fr -= 1;  // estimator.cpp:965-969
-        }
-        PO.blk_kind[(size_t)w * PO.max_pblk + t] = kind;
-        PO.blk_frame[(size_t)w * PO.max_pblk + t] = fr;
-        double* x0 = PO.x0 + ((size_t)w * PO.max_pblk + t) * 9;
-        const double* src = kind == AVM_BLK_POSE ? lds + L_X + id * 7
-                            : (kind == AVM_BLK_SPEEDBIAS ? lds + L_X + XSB + (id - 11) * 9 : lds + L_RIC + (kind == AVM_BLK_TD ? 19 : 12));
-        const int gs = kind == AVM_BLK_SPEEDBIAS ? 9 : (kind == AVM_BLK_TD ? 1 : 7);
-        for (int q = 0; q < 9; q++) x0[q] = q < gs ? src[q] : 0.0;
-      }
-      if (t == 0) PO.n[w] = n, PO.nblk[w] = nblk;
-    }
-    __syncthreads();
-    PROF(c, 26);
-    if (c.prof && t == 0) c.prof[30] += 1;
-  }
-}
-
-#ifndef AVM_TP
-// Per-factor evaluation at the input state (no solve): parity-test surface for A5/A6/A8.
-__global__ __launch_bounds__(NT) void eval_factors_kernel(EvalArgs A) {
-  lds_base_check();
-  double* lds = LDS();
-  int* ids = reinterpret_cast<int*>(lds + L_INT);
-  const int t = threadIdx.x;
-  const avm_options& o = lds_opt();
-  const avm_window_batch& B = A.b;
-  const int w = blockIdx.x;
-  WinCtx cl;
-  cl.sc = nullptr, cl.osf = nullptr, cl.w = w;
-  cl.nf = B.n_feat[w];
-  cl.obs = as_global(B.obs_xy + (size_t)w * B.max_obs * 2);
-  cl.pdelta = as_global(A.pre_delta + (size_t)w * 100), cl.pjac = as_global(A.pre_jac + (size_t)w * 2250), cl.psqrt = as_global(A.pre_sqrt + (size_t)w * 2250);
-  cl.psum = as_global(A.pre_sum_dt + (size_t)w * 10);
-  cl.lba = as_global(B.imu_lin_ba + (size_t)w * 30), cl.lbg = as_global(B.imu_lin_bg + (size_t)w * 30);
-  cl.pn = B.prior_n ? B.prior_n[w] : 0;
-  cl.pnblk = cl.pn > 0 ? B.prior_nblk[w] : 0;
-  cl.ldp = B.max_prior;
-  cl.pJ = as_global(B.prior_J + (size_t)w * B.max_prior * B.max_prior);
-  cl.pr = as_global(B.prior_r + (size_t)w * B.max_prior);
-  cl.px0 = as_global(B.prior_x0 + (size_t)w * B.max_pblk * 9);
-  cl.prof = nullptr, cl.cov = nullptr, cl.nobs_tot = 0;
-  lds_store_ctx(cl, A.opt);
-  __syncthreads();
-  const WinCtx& c = lds_ctx();
-  for (int i = t; i < 77; i += NT) lds[L_X + i] = B.pose[(size_t)w * 77 + i];
-  for (int i = t; i < 99; i += NT) lds[L_X + XSB + i] = B.speedbias[(size_t)w * 99 + i];
-  for (int i = t; i < MAXE; i += NT) lds[L_X + XLAM + i] = i < c.nf ? B.inv_depth[(size_t)w * B.max_feat + i] : 1.0;
-  for (int i = t; i < MAXPRIOR; i += NT) lds[L_DXP + i] = 0.0, lds[L_RP + i] = 0.0;
-  for (int i = t; i < 10 * 465; i += NT) lds[L_S + i] = 0.0;
-  if (t < 7) lds[L_RIC + 12 + t] = B.ex_pose[(size_t)w * 7 + t];
-  if (t == 0) {
-    const double* ex = B.ex_pose + (size_t)w * 7;
-    double R[9];
-    q2R(quat{ex[6], ex[3], ex[4], ex[5]}, R);
-    for (int k = 0; k < 9; k++) lds[L_RIC + k] = R[k];
-    for (int k = 0; k < 3; k++) lds[L_RIC + 9 + k] = ex[k];
-    int off = 0;
-    for (int k = 0; k < c.pnblk; k++) {
-      const int kind = B.prior_blk_kind[(size_t)w * B.max_pblk + k], fr = B.prior_blk_frame[(size_t)w * B.max_pblk + k];
-      ids[I_PBLK + k * 3] = kind, ids[I_PBLK + k * 3 + 1] = fr, ids[I_PBLK + k * 3 + 2] = off;
-      off += kind == AVM_BLK_SPEEDBIAS ? 9 : 6;
-    }
-  }
-  __syncthreads();
-  build_frames(L_X, 0);
-  __syncthreads();
-  Frames fr{lds + L_FR, lds + L_FR + 99};
-  const double sqi = o.focal_length / 1.5;
-  double acc = 0;
-  if (t >= NT - 64 && t < NT - 64 + 10) {
-    const int i = t - (NT - 64);
-    imu_raw<true>(lds + L_X, fr.R, o, c.pdelta + i * 10, c.pjac + i * 225, c.psum[i], c.lba + i * 3, c.lbg + i * 3, i, lds + L_S + i * 465);
-  }
-  for (int e = 0; e < c.nf; e++) {  // thread per observation of feature e
-    const int s0 = B.feat_obs_begin[(size_t)w * B.max_feat + e], no = B.feat_nobs[(size_t)w * B.max_feat + e];
-    const int fa = B.feat_start[(size_t)w * B.max_feat + e];
-    for (int k = 1 + t; k < no; k += NT) {
-      const int s = s0 + k;
-      double r[2], Ji[12], Jj[12], Je[2];
-      acc += proj_eval<true>(lds + L_X, fr, lds + L_RIC, lds + L_RIC + 9, c.obs[2 * s0], c.obs[2 * s0 + 1], c.obs[2 * s], c.obs[2 * s + 1],
-                             lds[L_X + XLAM + e], fa, fa + k, sqi, o.cauchy_a, A.apply_loss != 0, r, Ji, Jj, Je);
-      const size_t ob = (size_t)w * B.max_obs + s;
-      if (A.proj_r) A.proj_r[ob * 2] = r[0], A.proj_r[ob * 2 + 1] = r[1];
-      if (A.proj_J)
-        for (int rr = 0; rr < 2; rr++) {
-          for (int q = 0; q < 6; q++) A.proj_J[ob * 26 + rr * 13 + q] = Ji[rr * 6 + q], A.proj_J[ob * 26 + rr * 13 + 6 + q] = Jj[rr * 6 + q];
-          A.proj_J[ob * 26 + rr * 13 + 12] = Je[rr];
-        }
-    }
-  }
-  __syncthreads();
-  for (int idx = t; idx < 10 * 465; idx += NT) {
-    const int i = idx / 465, rc = idx % 465, r = rc / 31, cc = rc % 31;
-    double s = 0;
-    for (int k = r; k < 15; k++) s += c.psqrt[i * 225 + r * 15 + k] * lds[L_S + i * 465 + k * 31 + cc];
-    const size_t iv = (size_t)w * 10 + i;
-    if (cc == 0) {
-      if (A.imu_r) A.imu_r[iv * 15 + r] = s;
-      if (c.psum[i] <= o.max_sum_dt) acc += 0.5 * s * s;
-    } else if (A.imu_J) {
-      A.imu_J[(iv * 15 + r) * 30 + cc - 1] = s;
-    }
-  }
-  if (c.pn > 0) {
-    prior_residual_dev(c, L_X);
-    if (t < c.pn) {
-      acc += 0.5 * lds[L_RP + t] * lds[L_RP + t];
-      if (A.prior_res) A.prior_res[(size_t)w * B.max_prior + t] = lds[L_RP + t];
-    }
-  }
-  const double cost = block_sum<NT>(acc, lds + L_RED);
-  if (t == 0 && A.cost) A.cost[w] = cost;
-}
-#endif  // !AVM_TP
-
-#endif  // !AVM_X (marginalization: base and throughput build; per-factor evaluation kernel: base build only)
-
-#ifdef AVM_TP
-int window_solve_tp_lds_bytes() { return L_END * 8; }
-// the factorization's compile-time tables for the tests (tests/test_tp_pattern.py states them in numpy): out[0..120] = TPP.h, [121..241] = TPP.nz
-// (both [k][i]), [242..252] = tp_owner, [253 ..] = tp_perm of the 176 positions (-1: padding)
-int window_solve_tp_pattern(int* out) { return tp_pattern_export(out); }
-// workgroups of the throughput kernel the runtime says a CU can hold (2 is what the kernel is built for)
-int window_solve_tp_occupancy() {
-  int n = 0;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_solve_tp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, window_solve_tp_kernel, NT, L_END * 8) != hipSuccess) return -1;
-  return n;
-}
-
-// Throughput form of the solve (window_solve_tp.o): two 256-thread workgroups per CU, a.n_slots = 2 x CUs scratch slots.
-hipError_t launch_window_solve_tp(const SolveArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_solve_tp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int grid = a.b.n_windows < a.n_slots ? a.b.n_windows : a.n_slots;
-  hipLaunchKernelGGL(window_solve_tp_kernel, dim3(grid), dim3(NT), L_END * 8, stream, a);
-  return hipGetLastError();
-}
-
-// Throughput form of the marginalization: two 256-thread workgroups per CU, a.n_slots = 2 x CUs scratch slots (the solve's)
-hipError_t launch_marginalize_tp(const SolveArgs& a, const avm_prior_out& po, int* err, double* scale, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(marginalize_tp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int grid = a.b.n_windows < a.n_slots ? a.b.n_windows : a.n_slots;
-  hipLaunchKernelGGL(marginalize_tp_kernel, dim3(grid), dim3(NT), L_END * 8, stream, a, po, err, scale);
-  return hipGetLastError();
-}
-#elif !defined(AVM_X)
-int window_solve_lds_bytes() { return L_END * 8; }
-int window_solve_pattern(int* out) { return tp_pattern_export(out); }
-
-hipError_t launch_window_solve(const SolveArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int grid = a.b.n_windows < a.n_slots ? a.b.n_windows : a.n_slots;
-  hipLaunchKernelGGL(window_solve_kernel, dim3(grid), dim3(NT), L_END * 8, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_marginalize(const SolveArgs& a, const avm_prior_out& po, int* err, double* scale, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(marginalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int grid = a.b.n_windows < a.n_slots ? a.b.n_windows : a.n_slots;
-  hipLaunchKernelGGL(marginalize_kernel, dim3(grid), dim3(NT), L_END * 8, stream, a, po, err, scale);
-  return hipGetLastError();
-}
-
-hipError_t launch_eval_factors(const EvalArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(eval_factors_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(eval_factors_kernel, dim3(a.b.n_windows), dim3(NT), L_END * 8, stream, a);
-  return hipGetLastError();
-}
-#else
-int window_solve_x_lds_bytes() { return L_END * 8; }
-int window_solve_x_pattern(int* out) { return tp_pattern_export(out); }
-
-// the solve with ex_pose / td / relo_Pose as (optional) variables: 178 x 178 reduced system
-hipError_t launch_window_solve_x(const SolveArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(window_solve_x_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L_END * 8);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int grid = a.b.n_windows < a.n_slots ? a.b.n_windows : a.n_slots;
-  hipLaunchKernelGGL(window_solve_x_kernel, dim3(grid), dim3(NT), L_END * 8, stream, a);
-  return hipGetLastError();
-}
+#include "solve/eval_factors_kernel.hpp"
+#include "solve/launch.hpp"
 #endif
 
 }  // namespace avm

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction counts per SOURCE LINE of one function (companion of isa_mix.py): the -gline-tables-only build of a csrc file,
-disassembled with line info.  scripts/isa_lines.py window_solve.hip -DAVM_TP=1 --func eval_jac [--range 950:1200] [--top 40]"""
+disassembled with line info.  window_solve.hip includes csrc/solve/*.hpp, so rows read file:line:
+    scripts/isa_lines.py window_solve.hip -DAVM_TP=1 --func eval_jac [--file window_solve.hip] [--range 1150:1400] [--top 40]"""
 import argparse, collections, os, re, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_mix import classify, CSRC, LLVM
@@ -41,7 +42,9 @@ def main():
     rows = sorted(cnt.items())
     if args.range:
         lo, hi = map(int, args.range.split(":"))
-        rows = [r for r in rows if lo <= r[0][1] <= hi and (args.file is None or r[0][0] == args.file)]
+        rows = [r for r in rows if lo <= r[0][1] <= hi]
+    if args.file:
+        rows = [r for r in rows if r[0][0] == args.file]
     if args.top:
         rows = sorted(rows, key=lambda r: -sum(r[1].values()))[: args.top]
     tot = collections.Counter()

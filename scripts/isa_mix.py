@@ -63,10 +63,13 @@ def classify(op: str) -> str:
     return "other"
 
 
-def build_co(src, defs):
-    """csrc/Makefile's flags for the solve builds (IPRA for the base and throughput builds, not for -DAVM_X)."""
+def build_co(src, defs, csrc=CSRC):
+    """csrc/Makefile's flags on a toolchain that accepts all the options it probes for (FLAGS, and for the solve builds the sink option,
+    IPRA for the base and throughput builds, the SGPR-spill option for -DAVM_X); -Wno-pass-failed only silences a diagnostic.  The code
+    object is in a temporary directory of its own, which the caller may remove.  `csrc`: the directory to compile in (scripts/isa_same.py: a copy of another revision's)."""
     tmp = tempfile.mkdtemp()
-    flags = ["-O3", "-std=c++17", "-fconstexpr-steps=16000000", "--offload-arch=gfx950", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-pass-failed"]
+    flags = ["-O3", "-std=c++17", "-fconstexpr-steps=16000000", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
+             "-Wno-pass-failed"]
     if os.path.basename(src).startswith("window_solve"):
         flags += ["-mllvm", "-sink-insts-to-avoid-spills"]
         if not any(d.startswith("-DAVM_X") for d in defs):
@@ -74,7 +77,7 @@ def build_co(src, defs):
         else:
             flags += ["-mllvm", "-amdgpu-prealloc-sgpr-spill-vgprs"]
     bundle, co = os.path.join(tmp, "k.bundle"), os.path.join(tmp, "k.co")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + defs + ["--cuda-device-only", "-c", src, "-o", bundle], cwd=CSRC)
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + defs + ["--cuda-device-only", "-c", src, "-o", bundle], cwd=csrc)
     subprocess.check_call([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                            "--input=" + bundle, "--output=" + co])
     return co

@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Is the device code of the three solve builds the same as at another revision?  (cross-compiles, no GPU needed; needs the git history)
+
+    scripts/isa_same.py REV          (e.g. HEAD, HEAD~1, main)
+
+Builds window_solve.hip three ways (latency, -DAVM_X=1, -DAVM_TP=1; scripts/isa_mix.py's build_co(): csrc/Makefile's flags for that build
+plus --cuda-device-only) from `git archive REV` of csrc/ and include/ in a temporary directory and from the working tree, dumps the
+gfx950 code objects' .text, .rodata and .note sections (.note: every kernel's registers, spills, LDS and scratch) and prints one line
+per build and section with both sha256 hashes.  Exit status 1 on any difference.  (.dynstr / .strtab carry a string derived from the
+source file's name and are not compared.)
+
+The check of every refactor of these kernels: the compiler is deterministic and blind to how the source is cut into files, so a
+change that moves no instruction gives the same bytes.
+"""
+import concurrent.futures
+import hashlib
+import io
+import os
+import shutil
+import subprocess
+import sys
+import tarfile
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_mix import CSRC, LLVM, ROOT, build_co  # noqa: E402
+
+BUILDS = [("latency", []), ("extended", ["-DAVM_X=1"]), ("throughput", ["-DAVM_TP=1"])]
+SECTIONS = [".text", ".rodata", ".note"]
+
+
+def section_hashes(csrc, defs):
+    co = build_co("window_solve.hip", defs, csrc)
+    out = {}
+    for sec in SECTIONS:
+        dump = co + sec
+        subprocess.check_call([LLVM + "/llvm-objcopy", "--dump-section", "%s=%s" % (sec, dump), co])
+        with open(dump, "rb") as f:
+            out[sec] = hashlib.sha256(f.read()).hexdigest()
+    shutil.rmtree(os.path.dirname(co))  # build_co()'s temporary directory, the dumps with it
+    return out
+
+
+def main():
+    if len(sys.argv) != 2 or sys.argv[1].startswith("-"):
+        sys.exit(__doc__)
+    rev = sys.argv[1]
+    rel = os.path.relpath(CSRC, ROOT)
+    with tempfile.TemporaryDirectory() as tmp:
+        tar = subprocess.check_output(["git", "archive", rev, rel, "include"], cwd=ROOT)
+        tarfile.open(fileobj=io.BytesIO(tar)).extractall(tmp)
+        sides = [os.path.join(tmp, rel), CSRC]
+        with concurrent.futures.ThreadPoolExecutor(6) as ex:
+            jobs = {(b, i): ex.submit(section_hashes, side, defs) for b, defs in BUILDS for i, side in enumerate(sides)}
+            res = {k: j.result() for k, j in jobs.items()}
+    differ = 0
+    for b, _ in BUILDS:
+        for sec in SECTIONS:
+            old, new = res[(b, 0)][sec], res[(b, 1)][sec]
+            differ += old != new
+            print("%-10s %-7s %s %s %s" % (b, sec, old[:16], new[:16], "same" if old == new else "DIFFERENT"))
+    sys.exit(1 if differ else 0)
+
+
+if __name__ == "__main__":
+    main()

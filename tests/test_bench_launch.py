@@ -112,7 +112,9 @@ def test_self_launched_two_rank_bench_end_to_end_on_whatever_devices_there_are()
 def test_the_committed_rocprof_summary_belongs_to_the_kernel_sources_in_the_tree():
     """bench.py reports roofline.traffic / mfma_util / fabric_GBs from the newest profiles/*_pmc_traffic.json only if that summary was measured
     on the kernel sources that are in the tree now (sha256 of csrc/window_solve.hip, kernels.hpp, devmath.hpp, Makefile stored with it):
-    a kernel change without a re-profile (scripts/gpu_profile.sh + scripts/summarize_rocprof.py) fails here instead of reporting stale traffic."""
+    a kernel change without a re-profile (scripts/gpu_profile.sh + scripts/summarize_rocprof.py) fails here instead of reporting stale traffic.
+    window_solve.hip includes csrc/solve/*, which bench.py's hash does not see: their hash (scripts/solve_parts_sha256.py: names and contents) is stored in
+    the summary beside bench.py's and has to be the tree's as well."""
     import importlib.util
 
     spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
@@ -120,6 +122,11 @@ def test_the_committed_rocprof_summary_belongs_to_the_kernel_sources_in_the_tree
     spec.loader.exec_module(b)
     prof, name, err = b.committed_profile()
     assert err is None, err
+    spec = importlib.util.spec_from_file_location("solve_parts_sha256", os.path.join(ROOT, "scripts", "solve_parts_sha256.py"))
+    sp = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(sp)
+    want = sp.solve_parts_sha256()
+    assert prof.get("_solve_parts_sha256") == want, f"profiles/{name} was measured on other csrc/solve/ sources: re-run scripts/gpu_profile.sh + scripts/summarize_rocprof.py"
     sk = "window_solve_tp_kernel" if "window_solve_tp_kernel" in prof else "window_solve_kernel"  # (the form a 4096-window batch takes)
     assert prof[sk]["traffic_bytes_per_launch"] > 0 and 0 < prof[sk]["mfma_util"] < 1
 
