@@ -118,15 +118,67 @@ AVM_DEV void qleft_qright_br(quat a, quat b, double* M) {
       M[i * 3 + j] = av[i] * (-bv[j]) + La[i * 3] * Rb[j] + La[i * 3 + 1] * Rb[3 + j] + La[i * 3 + 2] * Rb[6 + j];
 }
 
+// ---- lane exchange with the pattern as an immediate --------------------------------------------------------------------------------
+// __shfl_xor is a ds_bpermute_b32 per 32 bits with the partner's byte address in a VGPR: the compiler keeps the six address registers
+// of a ladder live across the whole kernel, and in the solve kernels it spills them - every step of a reduction then began with a trip
+// to scratch memory.  The forms below carry the pattern in the instruction (DPP controls, the gfx950 row / half swaps): no address
+// register, no LDS pipe.  All of them are compiler builtins, so the hazard recognizer places the DPP wait states.
+template <int CTRL>
+AVM_DEV int dpp_mov(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+// the value of lane (lane ^ O), O = 1, 2, 4, 8 (inside the 16-lane rows); every lane of the wavefront active
+template <int O>
+AVM_DEV int lane_xor(int v) {
+  static_assert(O == 1 || O == 2 || O == 4 || O == 8, "inside a DPP row");
+  if constexpr (O == 1) return dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
+  if constexpr (O == 2) return dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
+  if constexpr (O == 4) return dpp_mov<0x1B>(dpp_mov<0x141>(v));  // row_half_mirror (lane ^ 7), then quad_perm [3,2,1,0] (lane ^ 3)
+  return dpp_mov<0x128>(v);                        // row_ror:8
+}
+template <int O>
+AVM_DEV double lane_xor(double v) {
+  return __hiloint2double(lane_xor<O>(__double2hiint(v)), lane_xor<O>(__double2loint(v)));
+}
+// Steps 32 and 16 of a butterfly whose operation commutes: v_permlane32_swap / v_permlane16_swap of v with itself leave v's lower
+// (even-row) copy in one register and its upper (odd-row) copy in the other, in both halves (rows of the pair) - op(a, b) is then
+// op(v[lane], v[lane ^ O]) in the lower lanes and op(v[lane ^ O], v[lane]) in the upper ones: the same value for + and fmax.
+struct dpair {
+  double a, b;
+};
+template <int O>
+AVM_DEV dpair lane_swap(double v) {
+  static_assert(O == 16 || O == 32, "row or half swap");
+  const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+  if constexpr (O == 32) {
+    const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return dpair{__hiloint2double(h[0], l[0]), __hiloint2double(h[1], l[1])};
+  } else {
+    const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return dpair{__hiloint2double(h[0], l[0]), __hiloint2double(h[1], l[1])};
+  }
+}
+
 // ---- wave / block reductions (fixed order => deterministic) ---------------------------
+// the butterfly of a __shfl_xor ladder: partner lane ^ o, o = 32, 16, 8, 4, 2, 1 in that order; the result in every lane
 AVM_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  dpair p = lane_swap<32>(v);
+  v = p.a + p.b;
+  p = lane_swap<16>(v);
+  v = p.a + p.b;
+  v += lane_xor<8>(v);
+  v += lane_xor<4>(v);
+  v += lane_xor<2>(v);
+  v += lane_xor<1>(v);
   return v;
 }
 AVM_DEV double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  dpair p = lane_swap<32>(v);
+  v = fmax(p.a, p.b);
+  p = lane_swap<16>(v);
+  v = fmax(p.a, p.b);
+  v = fmax(v, lane_xor<8>(v));
+  v = fmax(v, lane_xor<4>(v));
+  v = fmax(v, lane_xor<2>(v));
+  v = fmax(v, lane_xor<1>(v));
   return v;
 }
 // all threads get the result; red must hold >= 32 doubles; contains 2 __syncthreads

@@ -678,8 +678,7 @@ AVM_NOINL bool pinv16_cholesky(double* EA, double* EV, int m, double eps) {  // 
     }
   }
   tr = (idl && (r & 15) < m) ? tr : 0.0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) tr += __shfl_xor(tr, off, 64);
+  tr = wave_sum(tr);
   const bool fast = !bad && tr * eps < 1.0;  // (NaN compares false)
   if (fast) {
     if (idl) {

@@ -71,11 +71,24 @@ AVM_DEV void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// A value every lane of the wavefront holds alike, moved to scalar registers.  The trust-region loop's own scalars (radius, mu, norms,
+// costs) are live across every outlined phase; as vector registers the compiler parks them in scratch memory around the calls and each
+// use after a call starts with a reload, as scalar registers they are parked in lanes of a vector register (v_readlane, no memory).
+AVM_DEV double uni(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
 // Workgroup reductions of the solve kernel with ONE barrier each.  The partial sums of consecutive reductions go to alternating
 // halves of lds[L_RED]: a wavefront can only overwrite a half two reductions later, i.e. after a barrier that every wavefront
 // reaches with its reads of that half done.  Which half is next is a counter every wavefront keeps for itself in LDS (all
 // wavefronts run the same sequence of reductions, so the counters agree); red_init() zeroes it at kernel entry.
-AVM_DEV int* red_counter() { return reinterpret_cast<int*>(LDS() + L_RED_CNT) + (threadIdx.x >> 6); }
+// (The address from an opaque copy of the thread index: the compiler cannot hoist it, so every reduction computes it with two VALU
+//  instructions.  Computed once it was kept for the whole kernel, spilled, and every reduction began by reloading it from scratch memory.)
+AVM_DEV int* red_counter() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return reinterpret_cast<int*>(LDS() + L_RED_CNT) + (t >> 6);
+}
 AVM_DEV void red_init() {
   if ((threadIdx.x & 63) == 0) *red_counter() = 0;
 }
@@ -494,8 +507,8 @@ AVM_NOINL void prior_residual_dev(const WinCtx&, int xs_off) {
     double s = 0;
 #pragma unroll
     for (int j = 0; j < MAXPRIOR / 4; j++) s += (part + 4 * j < c.pn ? v[j] : 0.0) * lds[L_DXP + part + 4 * j];
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
+    s += lane_xor<1>(s);
+    s += lane_xor<2>(s);
     if (row < c.pn && part == 0) lds[L_RP + row] = r0 + s;
   }
   __syncthreads();
@@ -553,10 +566,10 @@ AVM_DEV double prior_wave(int xs_off, int rb, int re, int buf_off) {
       double sacc = 0;
 #pragma unroll
       for (int j = 0; j < NK; j++) sacc += v[u][j] * dxv[j];
-      sacc += __shfl_xor(sacc, 8, 64);
-      sacc += __shfl_xor(sacc, 4, 64);
-      sacc += __shfl_xor(sacc, 2, 64);
-      sacc += __shfl_xor(sacc, 1, 64);
+      sacc += lane_xor<8>(sacc);
+      sacc += lane_xor<4>(sacc);
+      sacc += lane_xor<2>(sacc);
+      sacc += lane_xor<1>(sacc);
       const int row = r0 + 4 * u + lg;
       const double rp = rr[u] + sacc;
       if (lr == 0 && row < re) {
@@ -2488,8 +2501,8 @@ AVM_NOINL double back_substitute(const WinCtx&, double mu) {
 #pragma unroll
       for (int j = 0; j < NQ4; j++) sacc += v[j] * ys[part + 4 * j];
     }
-    sacc += __shfl_xor(sacc, 1, 64);
-    sacc += __shfl_xor(sacc, 2, 64);
+    sacc += lane_xor<1>(sacc);
+    sacc += lane_xor<2>(sacc);
     if (e < c.nf && part == 0) {
       const double he = lds[L_HEE + e] + mu * lds[L_DD + NF + e] * lds[L_DD + NF + e];
       lds[L_Y + NF + e] = (lds[L_G + NF + e] - scl[NF + e] * sacc) / he;
@@ -2896,8 +2909,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
         const int own = (fc + 63) >> 6, with = (fc + bn + 63) >> 6;
         int key = (with << 16) | (own << 8) | t;
         if (t >= ASM_WAVES) key = 0x7fffffff;
-#pragma unroll
-        for (int o = 2; o > 0; o >>= 1) key = min(key, __shfl_xor(key, o, 64));
+        key = min(key, lane_xor<2>(key)), key = min(key, lane_xor<1>(key));
         const int bw = __builtin_amdgcn_readfirstlane(key) & 255;
         if (t == bw) fc += bn;
         if (t == 0) ids[I_FRW + bb] = bw;
@@ -2923,11 +2935,10 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
           if (!(done & (1 << f)) && n > bn) bn = n, bb = f;
         }
         const int own = (fc + 63) >> 6, with = (fc + bn + 63) >> 6;
-        const int partner = __shfl(own, t ^ 4, 64);
+        const int partner = lane_xor<4>(own);
         int key = ((with + partner + ((t & 3) == 2 ? 2 : ((t & 3) == 3 ? 1 : 0))) << 16) | (own << 8) | t;
         if (t >= ASM_WAVES) key = 0x7fffffff;
-#pragma unroll
-        for (int o = 4; o > 0; o >>= 1) key = min(key, __shfl_xor(key, o, 64));
+        key = min(key, lane_xor<4>(key)), key = min(key, lane_xor<2>(key)), key = min(key, lane_xor<1>(key));
         const int bw = __builtin_amdgcn_readfirstlane(key) & 255;
         if (t == bw) fc += bn;
         if (t == 0) ids[I_FRW + bb] = bw;
@@ -3054,14 +3065,14 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
         if (t == 402 && c.est_td) gm = fmax(gm, fabs(g[XC_TD]));
 #endif
       }
-      gradient_max_norm = block_max1(gm);
+      gradient_max_norm = uni(block_max1(gm));
       __syncthreads();
       if (c.prof && t == 0) c.prof[43] += clock64() - pt__;
       scale_system(c, was_first);
       PROF(c, 10);
     };
     auto evaluate_x = [&]() {
-      x_cost = eval_jac(c, o);
+      x_cost = uni(eval_jac(c, o));
       post_evaluate();
     };
     // eval_jac() stages the frame tasks' rows in the LDS range that also holds the Gauss-Newton step, the dogleg step
@@ -3095,7 +3106,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
     // the system at x, and switches speculation off until a step with rho > 0.75 comes by.
     bool speculate = A.speculate != 0;
 
-    x_norm = amb_norm(lds + L_X);
+    x_norm = uni(amb_norm(lds + L_X));
     evaluate_x();
     initial_cost = x_cost;
     double ref_cost = x_cost;
@@ -3155,7 +3166,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
 #endif
           g2 += v * v;
         }
-        gnorm = sqrt(block_sum1(g2));
+        gnorm = uni(sqrt(block_sum1(g2)));
         // Gauss-Newton step with mu retry (DoglegStrategy::ComputeGaussNewtonStep)
         solver_ok = false;
         bool rebuilt = true;
@@ -3181,7 +3192,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
           AVM_PRIO_LIGHT();
           PROF(c, 12);
           if (!ok) {
-            mu *= mu_inc;
+            mu = uni(mu * mu_inc);
             rebuilt = false;
             continue;
           }
@@ -3210,7 +3221,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
             PROF(c, 13);
           }
           if (!ok) {
-            mu *= mu_inc;
+            mu = uni(mu * mu_inc);
             rebuilt = false;
             continue;
           }
@@ -3218,7 +3229,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
           const double bad_y = back_substitute(c, mu);
           PROF(c, 14);
           if (bad_y > 0) {
-            mu *= mu_inc;
+            mu = uni(mu * mu_inc);
             rebuilt = false;
             continue;
           }
@@ -3234,8 +3245,8 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
             a2 += yv * lds[L_G + i];
           }
           block_sum1x2(a1, a2);
-          gn_norm = sqrt(a1);
-          ytg = a2;
+          gn_norm = uni(sqrt(a1));
+          ytg = uni(a2);
         }
       }
       bool step_is_valid = false;
@@ -3250,14 +3261,14 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
             for (int i = t; i < VEC; i += NT) lds[L_ST + i] = i < NF + c.nf ? DG(i) / lds[L_DD + i] : 0.0;
             __syncthreads();
             PROFQ(c, 33);
-            jusq = jac_times_vec_sq(c, o);
-            alpha = gnorm * gnorm / jusq;
+            jusq = uni(jac_times_vec_sq(c, o));
+            alpha = uni(gnorm * gnorm / jusq);
             have_alpha = true;
             __syncthreads();
             PROFQ(c, 34);
           }
           if (gnorm * alpha >= radius) {
-            k1 = radius / gnorm, k2 = 0;
+            k1 = uni(radius / gnorm), k2 = 0;
             dogleg_step_norm = radius;
           } else {
             // a = -alpha g/D, b = -D y
@@ -3267,13 +3278,13 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
             const double cc = b_dot_a - a2n;
             const double dd = sqrt(cc * cc + bma * (radius * radius - a2n));
             const double beta = (cc <= 0) ? (dd - cc) / bma : (radius * radius - a2n) / (dd + cc);
-            k1 = alpha * (1.0 - beta), k2 = beta;
+            k1 = uni(alpha * (1.0 - beta)), k2 = uni(beta);
             double s2 = 0;
             for (int i = t; i < NF + c.nf; i += NT) {
               const double v = -k1 * DG(i) - k2 * lds[L_DD + i] * lds[L_Y + i];
               s2 += v * v;
             }
-            dogleg_step_norm = sqrt(block_sum1(s2));
+            dogleg_step_norm = uni(sqrt(block_sum1(s2)));
           }
         }
         for (int i = t; i < VEC; i += NT)
@@ -3285,7 +3296,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
           const double uHy = utg - mu * ytg;                    // u^T (g - mu D^2 y)
           const double yHy = ytg - mu * yDy;
           const double sHs = k1 * k1 * (k1 != 0 ? jusq : 0.0) + 2 * k1 * k2 * uHy + k2 * k2 * yHy;
-          model_cost_change = (k1 * utg + k2 * ytg) - 0.5 * sHs;
+          model_cost_change = uni((k1 * utg + k2 * ytg) - 0.5 * sHs);
         }
         step_is_valid = model_cost_change > 0.0;
         if (step_is_valid) num_invalid = 0;
@@ -3296,7 +3307,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
           termination = AVM_TERM_FAILURE;
           break;
         }
-        mu *= mu_inc;  // StepIsInvalid
+        mu = uni(mu * mu_inc);  // StepIsInvalid
         reuse = false;
         evaluate_x();  // S holds a Cholesky factor: rebuild the normal equations for the retry
         continue;
@@ -3307,14 +3318,14 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
       state_plus();
       __syncthreads();
 #ifdef AVM_X
-      const double step_norm = sqrt(amb_sq(lds + L_X, lds + L_XC));
+      const double step_norm = uni(sqrt(amb_sq(lds + L_X, lds + L_XC)));
 #else
       double d2 = 0;
       for (int i = t; i < 176 + c.nf; i += NT) {
         const double d = lds[L_X + i] - lds[L_XC + i];
         d2 += d * d;
       }
-      const double step_norm = sqrt(block_sum1(d2));
+      const double step_norm = uni(sqrt(block_sum1(d2)));
 #endif
       // the last iteration the options allow: the minimizer stops right after it (the iteration limit is checked before
       // the gradient tolerance, trust_region_minimizer.cc FinalizeIterationAndCheckIfMinimizerCanContinue), so the
@@ -3325,12 +3336,12 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
       PROFQ(c, 35);
       if (spec) {
         spec_enter();  // x <- candidate; the current point and the GN step are parked in the slot
-        cand_cost = eval_jac(c, o);
+        cand_cost = uni(eval_jac(c, o));
         PROF(c, 15);
       } else {
         build_frames(L_XC, 1);
         __syncthreads();
-        cand_cost = eval_cost(c, o, L_XC, 1);
+        cand_cost = uni(eval_cost(c, o, L_XC, 1));
         PROF(c, 15);
       }
       PROFQ_T0();
@@ -3345,18 +3356,18 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
         termination = AVM_TERM_FUNCTION_TOL;
         break;
       }
-      const double rel = (ref_cost - cand_cost) / model_cost_change;
+      const double rel = uni((ref_cost - cand_cost) / model_cost_change);
       if (rel > o.min_relative_decrease) {
         if (spec) {
           // the system at the accepted point is already assembled
-          x_norm = amb_norm(lds + L_X);
+          x_norm = uni(amb_norm(lds + L_X));
           x_cost = cand_cost;
           post_evaluate();
         } else {
           __syncthreads();
           for (int i = t; i < XN; i += NT) lds[L_X + i] = lds[L_XC + i];
           __syncthreads();
-          x_norm = amb_norm(lds + L_X);
+          x_norm = uni(amb_norm(lds + L_X));
           if (last_iteration)
             x_cost = cand_cost;
           else
@@ -3364,9 +3375,9 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
         }
         speculate = A.speculate != 0 && rel > 0.75;
         step_ok = true;
-        if (rel < 0.25) radius *= 0.5;
-        if (rel > 0.75) radius = fmax(radius, 3.0 * dogleg_step_norm);
-        mu = fmax(min_mu, 2.0 * mu / mu_inc);
+        if (rel < 0.25) radius = uni(radius * 0.5);
+        if (rel > 0.75) radius = uni(fmax(radius, 3.0 * dogleg_step_norm));
+        mu = uni(fmax(min_mu, 2.0 * mu / mu_inc));
         reuse = false;
         ref_cost = cand_cost;
       } else {
@@ -3377,7 +3388,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
           spec_restore_gn_step();
         }
         speculate = false;
-        radius *= 0.5;
+        radius = uni(radius * 0.5);
         reuse = true;
       }
       PROFQ(c, 36);

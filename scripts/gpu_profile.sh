@@ -22,7 +22,10 @@ timeout -k 10 300 rocprofv3 --kernel-trace $KF --pmc WRITE_SIZE -d $OUT/pmc_writ
 timeout -k 10 300 rocprofv3 --kernel-trace $KF --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY -d $OUT/pmc_sq -o run -- $PMCCMD > /dev/null 2> $OUT/pmc_sq.log &&
 timeout -k 10 600 python bench.py --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.log &&
 timeout -k 10 300 python scripts/dev_prof.py 256 dense > $OUT/phase_breakdown_dense.txt 2>&1 &&
-timeout -k 10 300 python scripts/dev_prof.py 256 sparse > $OUT/phase_breakdown_sparse.txt 2>&1
+timeout -k 10 300 python scripts/dev_prof.py 256 sparse > $OUT/phase_breakdown_sparse.txt 2>&1 &&
+# the throughput form at the benchmark's batch size (256 windows take the latency form): its trust-region rows are PROFQ slots 32..36
+timeout -k 10 300 python scripts/dev_prof.py 4096 dense > $OUT/phase_breakdown_tp_dense_4096.txt 2>&1 &&
+timeout -k 10 300 python scripts/dev_prof.py 4096 sparse > $OUT/phase_breakdown_tp_sparse_4096.txt 2>&1
 rc=$?
 [ $rc -eq 0 ] && tail -1 $OUT/bench.json | cut -c1-400
 exit $rc
