@@ -812,7 +812,7 @@ int avm_debug_solve_tp_occupancy(int* out) {
   return 2;
 }
 
-// test hook (not in avm.h): the compile-time tables of the throughput solve's sparse factorization (window_solve.hip, chol_regs); out: >= 512 ints
+// test hook (not in avm.h): the compile-time tables of the throughput solve's sparse factorization (solve/chol_regs_tables.hpp; exported by solve/chol_regs.hpp); out: >= 512 ints
 int avm_debug_solve_tp_pattern(int* out) { return window_solve_tp_pattern(out); }
 // which = 0: throughput build, 1: latency build, 2: extended build
 int avm_debug_solve_pattern(int which, int* out) {

@@ -62,7 +62,7 @@ struct SolveArgs {
   avm_solve_summary* summary;                                 // [B] or null
   int n_slots;
   long long* prof;  // optional [n_slots][PROF_SLOTS] per-phase shader-clock accumulators (debug)
-  int speculate;    // 1: evaluate the Jacobian at the candidate directly while steps keep being accepted (window_solve.hip)
+  int speculate;    // 1: evaluate the Jacobian at the candidate directly while steps keep being accepted (solve/solve_kernel.hpp)
   long long time_cap_ticks;  // avm_options::max_solver_time_s in ticks of the device wall clock (wall_clock64); 0 = no cap
 };
 
@@ -142,7 +142,7 @@ __host__ __device__ inline int check_fsel_tables(const avm_fsel_batch& b, int p)
 }
 
 // The throughput form of the solve (window_solve_tp.o) keeps the speed-bias rows of the system in their structural form plus ONE strip
-// "the prior's speed-bias block x every pose" (window_solve.hip, s_off): a prior with more than one speed-bias block does not fit it.
+// "the prior's speed-bias block x every pose" (solve/lds.hpp, s_off): a prior with more than one speed-bias block does not fit it.
 // The reference never builds one (estimator.cpp:904-916 keeps para_SpeedBias[1] only); such a batch simply takes the other kernel.
 // The throughput form of the marginalization (marginalize_tp_kernel, round 5) holds the joint system over poses | speed-biases 0, 1 |
 // ex_pose | td only: a prior with a speed-bias block of a later frame does not fit it (the reference keeps frame 1's, as frame 0).
@@ -157,7 +157,7 @@ __host__ __device__ inline int window_prior_tp_misfit(const avm_window_batch& B,
       nsb++, late |= fr > 1, later |= fr > 0;
     }
   // (the throughput solve eliminates the speed-bias blocks last frame first, so that the one block the prior couples to every pose comes
-  //  last of them: window_solve.hip, chol_regs - a prior whose block is not frame 0's would fill the factor in)
+  //  last of them: solve/chol_regs_tables.hpp - a prior whose block is not frame 0's would fill the factor in)
   return (nsb > 1 || later ? 1 : 0) | (late ? 2 : 0);
 }
 

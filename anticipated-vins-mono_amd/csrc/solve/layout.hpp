@@ -78,6 +78,12 @@ constexpr int L_ACC = L_Y, ACCW = 152;
 static_assert(L_ACC + 6 * ACCW <= L_WCH, "the accumulators stay inside y | step | candidate state");
 constexpr int RICW = 20;           // lds[L_RIC]: ric 9, tic 3, current ex_pose 7 (+1 pad)
 constexpr int NPRIW = 2;           // wavefronts that share the prior: the second one's dx / J0^T r_p at L_DX2
+constexpr int IMUW = 2;            // eval_jac, phase A: the wavefront of the raw IMU Jacobians (every wavefront assembles; wavefronts 2 and 3 get fewer frames and take
+                                   // the raw IMU Jacobians and the prior afterwards)
+constexpr int NQB = 6;             // eval_jac, phase B: per-factor quantities summed per feature (E^T E and E^T r come out of the frame tasks' accumulators in LDS)
+constexpr int PT0 = 160;           // jac_times_vec_sq: first thread of the prior's rows (256 threads: they sit right behind the 150 IMU rows)
+constexpr int PBT0 = 160;          // window load: first thread that reads the prior's block table
+constexpr int L_GF = L_Y;          // rot_diff / origin_P0 of the gauge fix (the Gauss-Newton step is dead after the loop)
 constexpr int LDS_BUDGET = 81920;  // two workgroups per CU: 80 KB each
 #elif defined(AVM_X)
 // EXTENDED build (window_solve_x.o, -DAVM_X): every optional member of the problem (ex_pose / td / relocalization), 512 threads, one window per CU.
@@ -108,6 +114,11 @@ static_assert(L_ZV + TP_NPOS <= L_S + SROWS && TP_NWO * TP_NPOS <= TP_WSLOTS * 2
 constexpr int L_DD = L_G + VEC;    // D   (g / D is recomputed where it is needed: no room for a fourth vector next to the 178 x 178 system)
 constexpr int RICW = 24;           // lds[L_RIC]: [2][12]: ric 9, tic 3 of the current point / of the candidate
 constexpr int NPRIW = 1;           // the extended build keeps the prior on one wavefront
+constexpr int IMUW = ASM_WAVES;    // eval_jac, phase A: the wavefront of the raw IMU Jacobians, the first one that does not assemble
+constexpr int NQB = 15;            // eval_jac, phase B: per-factor quantities summed per feature, all NQ of them
+constexpr int PT0 = 192;           // jac_times_vec_sq: first thread of the prior's rows
+constexpr int PBT0 = 256;          // window load: first thread that reads the prior's block table
+constexpr int L_GF = L_Y;          // rot_diff / origin_P0 of the gauge fix (the Gauss-Newton step is dead after the loop)
 constexpr int LDS_BUDGET = 163840;
 #else
 // LATENCY build (window_solve.o): 512 threads, one window per CU.
@@ -137,6 +148,11 @@ constexpr int L_DG = L_G + VEC;    // g / D
 constexpr int L_DD = L_DG + VEC;   // D
 constexpr int RICW = 20;           // lds[L_RIC]: ric 9, tic 3, current ex_pose 7 (+1 pad)
 constexpr int NPRIW = 2;           // wavefronts that share the prior: the second one's dx / J0^T r_p at L_DX2
+constexpr int IMUW = ASM_WAVES;    // eval_jac, phase A: the wavefront of the raw IMU Jacobians, the first one that does not assemble
+constexpr int NQB = 8;             // eval_jac, phase B: per-factor quantities summed per feature, all NQ of them
+constexpr int PT0 = 192;           // jac_times_vec_sq: first thread of the prior's rows
+constexpr int PBT0 = 256;          // window load: first thread that reads the prior's block table
+constexpr int L_GF = L_DG;         // rot_diff / origin_P0 of the gauge fix (g / D is dead after the loop)
 constexpr int LDS_BUDGET = 163840;
 #endif
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction counts per SOURCE LINE of one function (companion of isa_mix.py): the -gline-tables-only build of a csrc file,
-disassembled with line info.  window_solve.hip includes csrc/solve/*.hpp, so rows read file:line:
-    scripts/isa_lines.py window_solve.hip -DAVM_TP=1 --func eval_jac [--file window_solve.hip] [--range 1150:1400] [--top 40]"""
+disassembled with line info.  window_solve.hip is a list of includes of csrc/solve/*.hpp, so rows read file:line with the part's name:
+    scripts/isa_lines.py window_solve.hip -DAVM_TP=1 --func eval_jac [--file eval_jac.hpp] [--top 40]
+(--file: rows of that part only, e.g. without what was inlined from other parts; --range LO:HI: lines of it)"""
 import argparse, collections, os, re, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_mix import classify, CSRC, LLVM

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Dependent trips to memory the compiler built: a global / scratch load followed at once (within a few instructions) by `s_waitcnt vmcnt(0)` - the
 next load of the same loop or sequence cannot be in flight meanwhile.  Per function and source line (-gline-tables-only build):
-    scripts/isa_serial_loads.py window_solve.hip -DAVM_TP=1 [--func eval_jac]          (rows read file:line: window_solve.hip or a file of csrc/solve/)"""
+    scripts/isa_serial_loads.py window_solve.hip -DAVM_TP=1 [--func eval_jac]          (rows read file:line, e.g. eval_jac.hpp:212: the files are the parts under csrc/solve/)"""
 import collections, os, re, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_lines import build

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a kernel reloads a SPILLED SGPR through scratch memory: `scratch_load_dword vN` followed by `v_readlane_b32 sX, vN` - the register that holds
 spilled SGPRs was spilled itself, so the predicate / address that needs the SGPR starts with a trip to memory.  Per source file and line (20-line buckets, e.g.
-window_solve.hip:4480.., or a file of csrc/solve/) of one kernel, from a -gline-tables-only build:   scripts/isa_sgpr_reloads.py window_solve.hip marginalize_tp_kernel -DAVM_TP=1"""
+marg_kernel.hpp:280..: the files are the parts under csrc/solve/) of one kernel, from a -gline-tables-only build:   scripts/isa_sgpr_reloads.py window_solve.hip marginalize_tp_kernel -DAVM_TP=1"""
 import collections, os, re, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_lines import build

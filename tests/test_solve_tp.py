@@ -167,7 +167,7 @@ def test_failed_factorizations_retry_like_the_latency_form(estimator, monkeypatc
 
 @pytest.mark.parametrize("extended", [False, True])
 def test_a_batch_mixing_priors_that_fit_the_sparse_factorization_and_priors_that_do_not(ctx, oracle, monkeypatch, extended):
-    """The latency and extended kernels choose the factorization PER WINDOW (I_CRFIT, window_solve.hip: chol_regs where the prior's only speed-bias
+    """The latency and extended kernels choose the factorization PER WINDOW (I_CRFIT, csrc/solve/solve_kernel.hpp: chol_regs where the prior's only speed-bias
     block is frame 0's, the left-looking factorization in LDS otherwise).  One call with both kinds of window - window 1's speed-bias block moved to
     frame 3 - gives the oracle's result for every window, and the windows that fit are bit-identical to a batch without the odd one."""
     import importlib

@@ -1,4 +1,4 @@
-"""The compile-time tables of the throughput solve's sparse factorization (window_solve.hip, chol_regs; round 6) against a numpy statement.
+"""The compile-time tables of the throughput solve's sparse factorization (csrc/solve/chol_regs_tables.hpp; round 6) against a numpy statement.
 
 The kernel eliminates the speed-bias blocks of frames 10 .. 6 and, beside them, those of frames 4 .. 0 (two pivot chains at a time; each set padded to
 three 16-column tiles), then frame 5's block, the poses and the right-hand side, and only ever touches the 16 x 16 tiles its table TPP.nz names.  A tile missing from that table would be a silently dropped part of the factor, so the table is stated a second time
