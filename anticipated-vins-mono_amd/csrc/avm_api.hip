@@ -1122,16 +1122,16 @@ int fsel_buffers(avm_ctx* c, const avm_fsel_batch* b, FselBuffers* w, bool may_s
 #define GET(field, type, count)                                                             \
   w->field = static_cast<type*>(pool_get(c, "fw_" #field, sizeof(type) * (count)));          \
   if (!w->field) return fail(c, AVM_ERR_HIP, "hipMalloc failed (selector work buffer)");
-  GET(C, double, 2 * P * T * T)  // (two buffers: csrc/fsel.hip, FselPar)
-  GET(dpp, double, 2 * P * T)  // (two buffers: csrc/fsel.hip, FselPar)
+  GET(C, double, 2 * P * T * T)  // (two buffers: csrc/fsel/pick.hpp, FselPar)
+  GET(dpp, double, 2 * P * T)  // (two buffers: csrc/fsel/pick.hpp, FselPar)
   GET(consts, double, P * 4)
   GET(delta, double, P * mc * T * T)
-  // (the solo form's packed copy - csrc/fsel.hip, FselDev::delta_pk - exists whenever avm_fsel_select_batch can choose that form: the rule is there)
+  // (the solo form's packed copy - csrc/fsel/args.hpp, FselDev::delta_pk - exists whenever avm_fsel_select_batch can choose that form: the rule is there)
   GET(delta_pk, double, may_solo ? P * mc * (T * (T + 1) / 2) : 1)
   GET(ddiag, double, (may_solo && T > 30) ? P * mc * T : 1)
   GET(delta_u, double, P * mu * T * T)
-  GET(fval, double, 2 * P * mc)  // (two buffers: csrc/fsel.hip, FselPar)
-  GET(ub, double, 2 * P * mc)  // (two buffers: csrc/fsel.hip, FselPar)
+  GET(fval, double, 2 * P * mc)  // (two buffers: csrc/fsel/pick.hpp, FselPar)
+  GET(ub, double, 2 * P * mc)  // (two buffers: csrc/fsel/pick.hpp, FselPar)
   GET(valid, int32_t, P * mc)
   GET(valid_u, int32_t, P * mu)
   GET(black, int32_t, P * mc)
@@ -1186,7 +1186,7 @@ int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, 
   }
   FselBuffers w;
   if ((rc = fsel_buffers(c, &d, &w, fsel_takes_solo(&d))) != AVM_OK) return rc;
-  // Every frame's greedy rounds in ONE launch (csrc/fsel.hip, fsel_frame_kernel): 2 = a team of workgroups per XCD, the teams
+  // Every frame's greedy rounds in ONE launch (csrc/fsel/frame_kernel.hpp, fsel_frame_kernel): 2 = a team of workgroups per XCD, the teams
   // take frames from a queue; 1 = one team over all XCDs (a single frame only); 0 = one launch per round.  A kernel that reports
   // a timed-out wait, or that did not finish every frame, is re-run one mode down, and the ctx stays there.
   // The downgrade is NOT sticky: a transient cause (an XCD busy with another ctx's solve, so that a team does not fill within

@@ -79,9 +79,9 @@ constexpr int FS_SYNC_INTS = 64 + 16 * 32 + 16 * 2 * 2 * 512 * 4;  // header, 16
 constexpr int FS_MAX_CLOUD = 4096;  // depth-cloud points per frame the kd-tree builder has LDS for (28 bytes each; the reference's cloud is the window's <= 150 landmarks)
 struct FselBuffers {
   double *C, *dpp, *consts, *delta, *delta_pk, *ddiag, *delta_u, *fval, *ub;
-  double* kd;  // [P][8 + 11 max_cloud] the frames' kd-trees over their depth clouds (csrc/fsel.hip, fsel_kdtree_kernel)
+  double* kd;  // [P][8 + 11 max_cloud] the frames' kd-trees over their depth clouds (csrc/fsel/kdtree.hpp, fsel_kdtree_kernel)
   int32_t *valid, *valid_u, *black, *nsel, *done, *live, *pos, *nlive;
-  int32_t* sync;  // [FS_SYNC_INTS] slot counter / failure flag / cycle trace / per-slot records of the single-frame kernel (csrc/fsel.hip)
+  int32_t* sync;  // [FS_SYNC_INTS] slot counter / failure flag / cycle trace / per-slot records of the single-frame kernel (csrc/fsel/frame_kernel.hpp)
 };
 
 // ---- table validation (every entry point that takes tables runs it before any kernel indexes with them) -----------
@@ -169,12 +169,19 @@ hipError_t lds_attr_once(int lds_bytes) {
   static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   return e;
 }
+// A kernel that is asked for another LDS size from call to call: the attribute once, to `lds_ceiling`, the largest size it can be asked
+// for (set from the first call's size, a later, larger call would fail); the launch with what this call needs (more than the ceiling: the
+// launch's own error).
 template <auto Kernel, class... Args>
-hipError_t launch_lds(int grid, int block, int lds_bytes, hipStream_t stream, const Args&... args) {
-  const hipError_t e = lds_attr_once<Kernel>(lds_bytes);
+hipError_t launch_lds_below(dim3 grid, dim3 block, int lds_ceiling, int lds_bytes, hipStream_t stream, const Args&... args) {
+  const hipError_t e = lds_attr_once<Kernel>(lds_ceiling);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds_bytes, stream, args...);
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
   return hipGetLastError();
+}
+template <auto Kernel, class... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args&... args) {
+  return launch_lds_below<Kernel>(grid, block, lds_bytes, lds_bytes, stream, args...);
 }
 
 // first_bad: TWO ints.  [0]: INT_MAX when every window / problem passes, else (index * 8 + rule) of the lowest failing index;

@@ -468,7 +468,7 @@ int avm_fsel_select_batch(avm_ctx* ctx, avm_mem mem, const avm_fsel_batch* batch
 int avm_fsel_select(avm_ctx* ctx, avm_mem mem, const avm_fsel_batch* frame, int32_t* selected_ids, int32_t* n_selected,
                     double* fvalues_opt);
 
-/* how often this ctx's select calls had to fall back from the all-rounds-in-one-launch kernel (csrc/fsel.hip): counters since
+/* how often this ctx's select calls had to fall back from the all-rounds-in-one-launch kernel (csrc/fsel/frame_kernel.hpp): counters since
  * avm_create.  out[0] = CALLS that had to be re-run in a slower mode (once per call), out[1] = LAUNCHES that reported a timed-out
  * wait or an unfinished frame (a call that falls two modes counts twice here), out[2] = the mode the next call starts in (2 = a
  * team per XCD, 1 = one team over all XCDs, 0 = one launch per round), out[3] = select calls so far.  A degraded call costs at most
@@ -482,7 +482,7 @@ int avm_fsel_fallback_stats(const avm_ctx* ctx, int64_t out[4]);
  * feature_selector.cpp:444).  depth [P][max_cand] (entries beyond n_cand: 0).  The same search runs inside
  * avm_fsel_select_batch / avm_fsel_information; this entry exists so that it can be checked against the reference's own nanoflann
  * (tests/golden/nanoflann_nn.npz, nanoflann_nn2.npz).  Round 5: the tree is built and walked as nanoflann builds and walks it
- * (csrc/fsel.hip: fsel_kdtree_kernel, kd_depth), so among cloud points at bit-identical distances the answer is nanoflann's too - the
+ * (csrc/fsel/kdtree.hpp: fsel_kdtree_kernel, kd_depth), so among cloud points at bit-identical distances the answer is nanoflann's too - the
  * point its traversal meets first; every query of the two fixtures is answered bit for bit.  max_cloud <= 4096 (the tree is built in LDS). */
 int avm_fsel_nn_depth(avm_ctx* ctx, avm_mem mem, const avm_fsel_batch* batch, double* depth);
 

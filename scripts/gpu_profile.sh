@@ -8,9 +8,10 @@ export TMPDIR=/tmp
 OUT=gpurun_out/prof_$1
 mkdir -p $OUT
 # what the numbers belong to: bench.py refuses a committed traffic figure whose kernel source has changed since; its hash covers
-# window_solve.hip, the hash beside it the files of csrc/solve/ that window_solve.hip includes (scripts/solve_parts_sha256.py)
+# window_solve.hip and fsel.hip, the hashes beside it the files of csrc/solve/ and csrc/fsel/ that those two include (scripts/solve_parts_sha256.py)
 python -c "import bench; print(bench.kernel_source_sha256())" > $OUT/kernel_source_sha256.txt &&
-python scripts/solve_parts_sha256.py > $OUT/solve_parts_sha256.txt || exit 1
+python scripts/solve_parts_sha256.py > $OUT/solve_parts_sha256.txt &&
+python scripts/solve_parts_sha256.py fsel > $OUT/fsel_parts_sha256.txt || exit 1
 # in-process input generation (forked workers under the profiler's signal handlers can hang) and, for the counter passes,
 # only the window kernels (the selector's thousands of small launches serialize under --pmc)
 CMD="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --fsel-problems 4 --gen-procs 1 --distinct 512"

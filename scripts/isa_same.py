@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Is the device code of the three solve builds the same as at another revision?  (cross-compiles, no GPU needed; needs the git history)
+"""Is the device code of the three solve builds and of the selector the same as at another revision?  (cross-compiles, no GPU needed; needs
+the git history)
 
     scripts/isa_same.py REV          (e.g. HEAD, HEAD~1, main)
 
-Builds window_solve.hip three ways (latency, -DAVM_X=1, -DAVM_TP=1; scripts/isa_mix.py's build_co(): csrc/Makefile's flags for that build
-plus --cuda-device-only) from `git archive REV` of csrc/ and include/ in a temporary directory and from the working tree, dumps the
+Builds window_solve.hip three ways (latency, -DAVM_X=1, -DAVM_TP=1) and fsel.hip (selector: the Makefile's plain FLAGS) with
+scripts/isa_mix.py's build_co() (csrc/Makefile's flags for that build plus --cuda-device-only) from `git archive REV` of csrc/ and include/ in a temporary directory and from the working tree, dumps the
 gfx950 code objects' .text, .rodata and .note sections (.note: every kernel's registers, spills, LDS and scratch) and prints one line
 per build and section with both sha256 hashes.  Exit status 1 on any difference.  (.dynstr / .strtab carry a string derived from the
 source file's name and are not compared.)
@@ -25,12 +26,13 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_mix import CSRC, LLVM, ROOT, build_co  # noqa: E402
 
-BUILDS = [("latency", []), ("extended", ["-DAVM_X=1"]), ("throughput", ["-DAVM_TP=1"])]
+BUILDS = [("latency", "window_solve.hip", []), ("extended", "window_solve.hip", ["-DAVM_X=1"]), ("throughput", "window_solve.hip", ["-DAVM_TP=1"]),
+          ("selector", "fsel.hip", [])]
 SECTIONS = [".text", ".rodata", ".note"]
 
 
-def section_hashes(csrc, defs):
-    co = build_co("window_solve.hip", defs, csrc)
+def section_hashes(csrc, src, defs):
+    co = build_co(src, defs, csrc)
     out = {}
     for sec in SECTIONS:
         dump = co + sec
@@ -50,11 +52,11 @@ def main():
         tar = subprocess.check_output(["git", "archive", rev, rel, "include"], cwd=ROOT)
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(tmp)
         sides = [os.path.join(tmp, rel), CSRC]
-        with concurrent.futures.ThreadPoolExecutor(6) as ex:
-            jobs = {(b, i): ex.submit(section_hashes, side, defs) for b, defs in BUILDS for i, side in enumerate(sides)}
+        with concurrent.futures.ThreadPoolExecutor(8) as ex:
+            jobs = {(b, i): ex.submit(section_hashes, side, src, defs) for b, src, defs in BUILDS for i, side in enumerate(sides)}
             res = {k: j.result() for k, j in jobs.items()}
     differ = 0
-    for b, _ in BUILDS:
+    for b, _, _ in BUILDS:
         for sec in SECTIONS:
             old, new = res[(b, 0)][sec], res[(b, 1)][sec]
             differ += old != new

@@ -88,6 +88,9 @@ if traffic and os.path.exists(hp):
 sp = os.path.join(src, "solve_parts_sha256.txt")  # csrc/solve/*, which window_solve.hip includes: bench.py's hash above does not see them
 if traffic and os.path.exists(sp):
     traffic["_solve_parts_sha256"] = open(sp).read().strip()
+fp = os.path.join(src, "fsel_parts_sha256.txt")  # ... and csrc/fsel/*, which fsel.hip includes
+if traffic and os.path.exists(fp):
+    traffic["_fsel_parts_sha256"] = open(fp).read().strip()
 if traffic:
     traffic["_command"] = "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --fsel-problems 4  (4096 windows, dense tracks, MARGIN_OLD)"
     json.dump(traffic, open(dst + "_pmc_traffic.json", "w"), indent=1)

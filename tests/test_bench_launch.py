@@ -114,7 +114,7 @@ def test_the_committed_rocprof_summary_belongs_to_the_kernel_sources_in_the_tree
     on the kernel sources that are in the tree now (sha256 of csrc/window_solve.hip, kernels.hpp, devmath.hpp, Makefile stored with it):
     a kernel change without a re-profile (scripts/gpu_profile.sh + scripts/summarize_rocprof.py) fails here instead of reporting stale traffic.
     window_solve.hip includes csrc/solve/*, which bench.py's hash does not see: their hash (scripts/solve_parts_sha256.py: names and contents) is stored in
-    the summary beside bench.py's and has to be the tree's as well."""
+    the summary beside bench.py's and has to be the tree's as well; so does fsel.hip with csrc/fsel/* (fsel_parts_sha256 of the same script)."""
     import importlib.util
 
     spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
@@ -127,6 +127,8 @@ def test_the_committed_rocprof_summary_belongs_to_the_kernel_sources_in_the_tree
     spec.loader.exec_module(sp)
     want = sp.solve_parts_sha256()
     assert prof.get("_solve_parts_sha256") == want, f"profiles/{name} was measured on other csrc/solve/ sources: re-run scripts/gpu_profile.sh + scripts/summarize_rocprof.py"
+    want = sp.fsel_parts_sha256()
+    assert prof.get("_fsel_parts_sha256") == want, f"profiles/{name} was measured on other csrc/fsel/ sources: re-run scripts/gpu_profile.sh + scripts/summarize_rocprof.py"
     sk = "window_solve_tp_kernel" if "window_solve_tp_kernel" in prof else "window_solve_kernel"  # (the form a 4096-window batch takes)
     assert prof[sk]["traffic_bytes_per_launch"] > 0 and 0 < prof[sk]["mfma_util"] < 1
 

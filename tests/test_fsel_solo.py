@@ -1,4 +1,4 @@
-"""GPU tier (-m gpu): the SOLO form of the selector (fsel_solo_kernel, csrc/fsel.hip: one workgroup per frame, lazy evaluation in the
+"""GPU tier (-m gpu): the SOLO form of the selector (fsel_solo_kernel, csrc/fsel/solo_kernel.hpp: one workgroup per frame, lazy evaluation in the
 sense of Minoux' accelerated greedy).
 
 A batch takes it on its own from 33 frames on (HORIZON <= 10); the selector tests of the other files use smaller batches and therefore

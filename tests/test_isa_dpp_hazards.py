@@ -1,8 +1,8 @@
-"""The DPP wait states of the selector's code object (CPU tier: cross-compiles csrc/fsel.hip for gfx950, no GPU needed).
+"""The DPP wait states of the selector's code object (CPU tier: cross-compiles csrc/fsel.hip, i.e. the parts under csrc/fsel/, for gfx950, no GPU needed).
 
 A DPP instruction reads its DPP source - its first source operand - correctly only if no VALU instruction has written that VGPR within the
 two wait states before it.  The compiler's hazard recognizer does not look inside inline assembly, and the selector's elimination issues
-its v_fmac_f64_dpp runs from inline assembly (fs_fmac_bcast, fsel.hip) with separate `s_nop 1` statements (fs_dpp_fence) for the wait
+its v_fmac_f64_dpp runs from inline assembly (fs_fmac_bcast, fsel/dpp.hpp) with separate `s_nop 1` statements (fs_dpp_fence) for the wait
 states: the scheduler may move other instructions between such a fence and its run, so only the compiled code can show that the rule holds.
 The scan is per basic block: `s_nop N` counts as N + 1 wait states, any other instruction as one.
 (window_solve.hip's back substitution carries its `s_nop 1` inside the same asm statement as each v_fmac_f64_dpp: safe by construction.)

@@ -8,7 +8,7 @@ EXACT TIES (dyadic grid points, queries at midpoints and cell centres: two resp.
 What is asserted: on EVERY query - the 78 exact ties included - the oracle's and the GPU's search return nanoflann's depth bit for
 bit, and the squared distance of the winner is bit-identical.  Which of several equidistant points wins is decided by the order in
 which the tree's traversal meets them, so both restate the tree: oracle/fsel.hpp `KdIndex` (divideTree / middleSplit_ / planeSplit /
-searchLevel as written in the header), csrc/fsel.hip `fsel_kdtree_kernel` + `kd_nearest` (the same tree built by one wavefront per
+searchLevel as written in the header), csrc/fsel/kdtree.hpp `fsel_kdtree_kernel` + `kd_nearest` (the same tree built by one wavefront per
 frame, searched with an explicit stack).  Depths in the fixture are distinct per cloud, so equal depth = equal index."""
 import os
 
