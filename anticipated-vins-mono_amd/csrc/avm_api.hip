@@ -8,6 +8,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <dlfcn.h>
@@ -73,13 +74,12 @@ struct avm_ctx {
   avm_solve_summary* d_summary = nullptr;
   long long* prof = nullptr;  // [n_slots][32], enabled by AVM_PROFILE=1
   size_t summary_cap = 0;
-  // staging pool for AVM_MEM_HOST calls: name -> (ptr, bytes)
+  // staging pool for AVM_MEM_HOST calls (pool_get): name -> (ptr, bytes), device memory ...
   std::map<std::string, std::pair<void*, size_t>> pool;
-  // pinned host staging (small AVM_MEM_HOST batches travel as one packed copy each way): name -> (ptr, bytes)
+  // ... and pinned host memory (small AVM_MEM_HOST batches travel as one packed copy each way)
   std::map<std::string, std::pair<void*, size_t>> pinned;
-  bool packed_in = false;  // the last stage_window_batch took the packed path (states are contiguous on the device)
   hipEvent_t ev[8];
-  hipEvent_t ev_flag = nullptr;  // recorded behind the copy of a table check's verdict (validate_windows_begin)
+  hipEvent_t ev_flag = nullptr;  // recorded behind the copy of a table check's verdict (flag_begin)
   std::map<std::string, float> last_ms;
   int last_fsel_mode = -1;  // the form the last avm_fsel_select_batch took (3: fsel_solo_kernel)
   int64_t last_fsel_evals = -1;  // candidate evaluations the last select executed on the device (solo form: counted by the kernel; else -1)
@@ -109,25 +109,17 @@ int fail(avm_ctx* c, int code, const char* msg) {
   return code;
 }
 
-void* pool_get(avm_ctx* c, const std::string& name, size_t bytes) {
-  auto& e = c->pool[name];
+// A buffer the ctx keeps under `name` and hands to every later call that asks for it by that name: device memory, or (PINNED) page-locked
+// host memory - the two kinds have name spaces of their own.  It grows, never shrinks; avm_debug_counters reports the (re)allocations.
+constexpr bool PINNED = true;
+void* pool_get(avm_ctx* c, const std::string& name, size_t bytes, bool pinned = false) {
+  auto& e = (pinned ? c->pinned : c->pool)[name];
   if (e.second < bytes || e.first == nullptr) {
     c->n_allocs++;
-    if (e.first) (void)hipFree(e.first);
+    if (e.first) (void)(pinned ? hipHostFree(e.first) : hipFree(e.first));
     e.first = nullptr;
-    if (hipMalloc(&e.first, bytes ? bytes : 8) != hipSuccess) return nullptr;
-    e.second = bytes;
-  }
-  return e.first;
-}
-
-void* pinned_get(avm_ctx* c, const std::string& name, size_t bytes) {
-  auto& e = c->pinned[name];
-  if (e.second < bytes || e.first == nullptr) {
-    c->n_allocs++;
-    if (e.first) (void)hipHostFree(e.first);
-    e.first = nullptr;
-    if (hipHostMalloc(&e.first, bytes ? bytes : 8, hipHostMallocDefault) != hipSuccess) return nullptr;
+    const size_t n = bytes ? bytes : 8;
+    if ((pinned ? hipHostMalloc(&e.first, n, hipHostMallocDefault) : hipMalloc(&e.first, n)) != hipSuccess) return nullptr;
     e.second = bytes;
   }
   return e.first;
@@ -151,92 +143,90 @@ int report_bad(avm_ctx* c, int first_bad, const char* unit) {
   return AVM_ERR_INVALID;
 }
 
-// Runs before any kernel indexes with the caller's tables: host tables are checked on the host, device-resident ones by a
-// one-thread-per-window kernel whose 4-byte verdict is read back (the only extra synchronization of a device-mode call).
+// ---- table checks ----
+// They run before any kernel indexes with the caller's tables: host tables are checked on the host, device-resident ones by a
+// one-thread-per-window (or per-frame) kernel.  Its verdict is a word that stays 0x7f7f7f7f while every table passes and otherwise names
+// the first window / frame that does not (8 * index + rule); the check of windows has a second word, tp_misfit.
+// flag_begin enqueues the check, the copy of its verdict into pinned memory and an event; flag_end waits for that event only.  What a
+// caller enqueues in between (the solve: its pre-integration, which clamps the one table entry it indexes with; the selector: the whole
+// select, whose kernels look at the device flag before they index with a table) runs while the host reads the verdict and prepares the next
+// launches, instead of the device idling through a blocking round trip.  On a failed check flag_end drains the stream before it reports,
+// so the caller's buffers are no longer being read when the error returns.
+struct FlagCheck {
+  int* dev = nullptr;   // non-null: a check is in flight
+  int* host = nullptr;  // pinned copy of the verdict, valid after flag_end
+};
+
+template <class Launch>
+int flag_begin(avm_ctx* c, int words, Launch launch, FlagCheck* f) {
+  int* dev = static_cast<int*>(pool_get(c, "v_flag", 2 * sizeof(int)));
+  f->host = static_cast<int*>(pool_get(c, "v_flag_h", 2 * sizeof(int), PINNED));
+  if (!dev || !f->host) return fail(c, AVM_ERR_HIP, "allocation failed (validation flag)");
+  HIPCHK(c, hipMemsetAsync(dev, 0x7f, sizeof(int), c->stream));
+  if (words > 1) HIPCHK(c, hipMemsetAsync(dev + 1, 0, sizeof(int), c->stream));
+  HIPCHK(c, launch(dev));
+  HIPCHK(c, hipMemcpyAsync(f->host, dev, words * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_flag, c->stream));
+  f->dev = dev;
+  return AVM_OK;
+}
+
+int flag_end(avm_ctx* c, const FlagCheck& f, const char* unit, int* tp_misfit = nullptr) {
+  HIPCHK(c, hipEventSynchronize(c->ev_flag));
+  if (tp_misfit) *tp_misfit = f.host[1];
+  if (f.host[0] == 0x7f7f7f7f) return AVM_OK;
+  (void)hipStreamSynchronize(c->stream);
+  return report_bad(c, f.host[0], unit);
+}
+
+int null_window_tables(avm_ctx* c, const avm_window_batch* b, int what) {
+  if ((what & CHK_TRACKS) && (!b->n_feat || !b->feat_start || !b->feat_nobs || !b->feat_obs_begin)) return fail(c, AVM_ERR_INVALID, "null feature table");
+  if ((what & CHK_IMU) && !b->imu_n) return fail(c, AVM_ERR_INVALID, "null imu_n");
+  if ((what & CHK_PRIOR) && b->prior_n && (!b->prior_nblk || !b->prior_blk_kind || !b->prior_blk_frame)) return fail(c, AVM_ERR_INVALID, "null prior table");
+  return AVM_OK;
+}
+
+int validate_windows_begin(avm_ctx* c, const avm_window_batch* b, int what, FlagCheck* f) {
+  const int rc = null_window_tables(c, b, what);
+  if (rc != AVM_OK) return rc;
+  return flag_begin(c, 2, [&](int* flag) { return launch_validate_windows(*b, what, flag, c->stream); }, f);
+}
+
 // tp_misfit (optional, with CHK_PRIOR): bit 0 set when some window's prior does not fit the throughput form of the solve, bit 1 when one
 // does not fit the throughput form of the marginalization (kernels.hpp, window_prior_tp_misfit)
 int validate_windows(avm_ctx* c, avm_mem mem, const avm_window_batch* b, int what, int* tp_misfit = nullptr) {
   if (tp_misfit) *tp_misfit = 0;
-  if ((what & CHK_TRACKS) && (!b->n_feat || !b->feat_start || !b->feat_nobs || !b->feat_obs_begin)) return fail(c, AVM_ERR_INVALID, "null feature table");
-  if ((what & CHK_IMU) && !b->imu_n) return fail(c, AVM_ERR_INVALID, "null imu_n");
-  if ((what & CHK_PRIOR) && b->prior_n && (!b->prior_nblk || !b->prior_blk_kind || !b->prior_blk_frame)) return fail(c, AVM_ERR_INVALID, "null prior table");
-  if (mem == AVM_MEM_HOST) {
-    for (int w = 0; w < b->n_windows; w++) {
-      const int rule = check_window_tables(*b, w, what);
-      if (rule) return report_bad(c, w * 8 + rule, "window");
-      if (tp_misfit && (what & CHK_PRIOR)) *tp_misfit |= window_prior_tp_misfit(*b, w);
-    }
-    return AVM_OK;
+  if (mem != AVM_MEM_HOST) {
+    FlagCheck f;
+    const int rc = validate_windows_begin(c, b, what, &f);
+    return rc != AVM_OK ? rc : flag_end(c, f, "window", tp_misfit);
   }
-  int* flag = static_cast<int*>(pool_get(c, "v_flag", 2 * sizeof(int)));
-  if (!flag) return fail(c, AVM_ERR_HIP, "hipMalloc failed (validation flag)");
-  HIPCHK(c, hipMemsetAsync(flag, 0x7f, sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(flag + 1, 0, sizeof(int), c->stream));
-  HIPCHK(c, launch_validate_windows(*b, what, flag, c->stream));
-  int h[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(h, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (tp_misfit) *tp_misfit = h[1];
-  return h[0] == 0x7f7f7f7f ? AVM_OK : report_bad(c, h[0], "window");
-}
-
-// The same check for a device-resident batch of avm_window_solve_batch, in two halves: _begin enqueues the check, the copy of its
-// verdict into pinned memory and an event; _end waits for that event only.  What the caller enqueues in between (the pre-integration,
-// which clamps the one table entry it indexes with) runs while the host reads the verdict and prepares the next launches, instead of
-// the device idling through a blocking round trip at the top of every call.  On a failed check _end drains the stream before it
-// reports, so the caller's buffers are no longer being read when the error returns.
-int validate_windows_begin(avm_ctx* c, const avm_window_batch* b, int what, int** host_flag) {
-  if ((what & CHK_TRACKS) && (!b->n_feat || !b->feat_start || !b->feat_nobs || !b->feat_obs_begin)) return fail(c, AVM_ERR_INVALID, "null feature table");
-  if ((what & CHK_IMU) && !b->imu_n) return fail(c, AVM_ERR_INVALID, "null imu_n");
-  if ((what & CHK_PRIOR) && b->prior_n && (!b->prior_nblk || !b->prior_blk_kind || !b->prior_blk_frame)) return fail(c, AVM_ERR_INVALID, "null prior table");
-  int* flag = static_cast<int*>(pool_get(c, "v_flag", 2 * sizeof(int)));
-  int* h = static_cast<int*>(pinned_get(c, "v_flag_h", 2 * sizeof(int)));
-  if (!flag || !h) return fail(c, AVM_ERR_HIP, "allocation failed (validation flag)");
-  HIPCHK(c, hipMemsetAsync(flag, 0x7f, sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(flag + 1, 0, sizeof(int), c->stream));
-  HIPCHK(c, launch_validate_windows(*b, what, flag, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_flag, c->stream));
-  *host_flag = h;
+  const int rc = null_window_tables(c, b, what);
+  if (rc != AVM_OK) return rc;
+  for (int w = 0; w < b->n_windows; w++) {
+    const int rule = check_window_tables(*b, w, what);
+    if (rule) return report_bad(c, w * 8 + rule, "window");
+    if (tp_misfit && (what & CHK_PRIOR)) *tp_misfit |= window_prior_tp_misfit(*b, w);
+  }
   return AVM_OK;
 }
-int validate_windows_end(avm_ctx* c, const int* host_flag, int* tp_misfit) {
-  HIPCHK(c, hipEventSynchronize(c->ev_flag));
-  if (tp_misfit) *tp_misfit = host_flag[1];
-  if (host_flag[0] == 0x7f7f7f7f) return AVM_OK;
-  (void)hipStreamSynchronize(c->stream);
-  return report_bad(c, host_flag[0], "window");
+
+int validate_fsel_begin(avm_ctx* c, const avm_fsel_batch* b, FlagCheck* f) {
+  if (!b->n_cand || !b->nr_imu) return fail(c, AVM_ERR_INVALID, "null n_cand / nr_imu");
+  return flag_begin(c, 1, [&](int* flag) { return launch_validate_fsel(*b, flag, c->stream); }, f);
 }
 
 int validate_fsel(avm_ctx* c, avm_mem mem, const avm_fsel_batch* b) {
+  if (mem != AVM_MEM_HOST) {
+    FlagCheck f;
+    const int rc = validate_fsel_begin(c, b, &f);
+    return rc != AVM_OK ? rc : flag_end(c, f, "frame");
+  }
   if (!b->n_cand || !b->nr_imu) return fail(c, AVM_ERR_INVALID, "null n_cand / nr_imu");
-  if (mem == AVM_MEM_HOST) {
-    for (int p = 0; p < b->n_problems; p++) {
-      const int rule = check_fsel_tables(*b, p);
-      if (rule) return report_bad(c, p * 8 + rule, "frame");
-    }
-    return AVM_OK;
+  for (int p = 0; p < b->n_problems; p++) {
+    const int rule = check_fsel_tables(*b, p);
+    if (rule) return report_bad(c, p * 8 + rule, "frame");
   }
-  int* flag = static_cast<int*>(pool_get(c, "v_flag", 2 * sizeof(int)));
-  if (!flag) return fail(c, AVM_ERR_HIP, "hipMalloc failed (validation flag)");
-  HIPCHK(c, hipMemsetAsync(flag, 0x7f, sizeof(int), c->stream));
-  HIPCHK(c, launch_validate_fsel(*b, flag, c->stream));
-  int h = 0;
-  HIPCHK(c, hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return h == 0x7f7f7f7f ? AVM_OK : report_bad(c, h, "frame");
-}
-
-template <class T>
-int stage_in(avm_ctx* c, const char* name, const T* host, size_t count, const T** dev) {
-  if (!host || count == 0) {
-    *dev = nullptr;
-    return AVM_OK;
-  }
-  void* d = pool_get(c, name, count * sizeof(T));
-  if (!d) return fail(c, AVM_ERR_HIP, "hipMalloc failed (staging)");
-  HIPCHK(c, hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
-  *dev = static_cast<const T*>(d);
   return AVM_OK;
 }
 
@@ -300,97 +290,254 @@ int check_window_batch(avm_ctx* c, const avm_options* opt, const avm_window_batc
   return AVM_OK;
 }
 
-// copy a host batch to the device; out = batch with device pointers
-// (field, element type, elements) of every table of an avm_window_batch; the four state arrays come first so that
-// the packed path can bring them back with one copy
-#define AVM_WINDOW_FIELDS(X, B, h)                                                                                        \
-  X(pose, double, (B) * 77) X(speedbias, double, (B) * 99) X(ex_pose, double, (B) * 7) X(inv_depth, double, (B) * (h)->max_feat) \
-  X(n_feat, int32_t, (B)) X(feat_start, int32_t, (B) * (h)->max_feat) X(feat_nobs, int32_t, (B) * (h)->max_feat)           \
-  X(feat_obs_begin, int32_t, (B) * (h)->max_feat) X(obs_xy, double, (B) * (h)->max_obs * 2) X(imu_n, int32_t, (B) * 10)    \
-  X(imu_dt, double, (B) * 10 * (h)->max_samp) X(imu_acc, double, (B) * 10 * ((h)->max_samp + 1) * 3)                       \
-  X(imu_gyr, double, (B) * 10 * ((h)->max_samp + 1) * 3) X(imu_lin_ba, double, (B) * 30) X(imu_lin_bg, double, (B) * 30)   \
-  X(prior_n, int32_t, (B)) X(prior_nblk, int32_t, (B)) X(prior_blk_kind, int32_t, (B) * (h)->max_pblk)                     \
-  X(prior_blk_frame, int32_t, (B) * (h)->max_pblk) X(prior_J, double, (B) * (h)->max_prior * (h)->max_prior)               \
-  X(prior_r, double, (B) * (h)->max_prior) X(prior_x0, double, (B) * (h)->max_pblk * 9)                                        \
-  X(obs_vel_td, double, (B) * (h)->max_obs * 4) X(td, double, (B)) X(relo_n, int32_t, (B)) X(relo_frame, int32_t, (B))            \
-  X(relo_feat, int32_t, (B) * (h)->max_feat) X(relo_xy, double, (B) * (h)->max_feat * 2) X(relo_pose, double, (B) * 7)           \
-  X(failure_occur, int32_t, (B)) X(last_pose0, double, (B) * 7)
+// ---- the arrays of the ABI structs, and how they travel ----
+// One descriptor per array: where its pointer sits in the struct, how many elements it has for the struct's dims, and which entry points
+// read it (in) and return it to the caller (out).  Every size is written here once; staging, packing and the copies back walk the tables.
+struct Field {
+  const char* pool;                                  // its staging buffer in the ctx's pool
+  size_t offset, elem;                               // the pointer member in the struct; bytes per element
+  size_t (*count)(const void* s, const void* dims);  // elements; dims: the batch struct the sizes of an output struct come from (else s itself)
+  unsigned in, out;                                  // masks of U_*
+  size_t bytes(const void* s, const void* dims) const { return elem * count(s, dims); }
+};
+struct Table {
+  const Field* first;
+  size_t n;
+  const Field* begin() const { return first; }
+  const Field* end() const { return first + n; }
+};
+template <size_t N>
+constexpr Table table_of(const Field (&f)[N]) {
+  return {f, N};
+}
+inline void* get_ptr(const void* s, const Field& f) {
+  void* p;
+  std::memcpy(&p, static_cast<const char*>(s) + f.offset, sizeof p);
+  return p;
+}
+inline void set_ptr(void* s, const Field& f, const void* p) { std::memcpy(static_cast<char*>(s) + f.offset, &p, sizeof p); }
 
-constexpr size_t PACK_LIMIT = 4u << 20;  // batches below 4 MiB (a few windows: the real-time use) travel packed
+// who uses an array: the calls that take the whole batch (solve, pre-integration, factor evaluation; struct-valued outputs), and the four
+// that take a subset of the window tables
+enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16 };
+constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE | U_SLIDE | U_PROP;
+
+// S: the struct of the member; D, nmember: the struct the dims come from (`d` in `count`) and its batch size (`N` in `count`)
+#define FIELD(S, D, nmember, pool, member, type, count, in, out)                                                              \
+  {pool, offsetof(S, member), sizeof(type),                                                                                   \
+   [](const void* sp, const void* dp) -> size_t {                                                                             \
+     static_assert(std::is_same<std::remove_cv_t<std::remove_pointer_t<decltype(S::member)>>, type>::value, #member);         \
+     const S& s = *static_cast<const S*>(sp);                                                                                 \
+     const D& d = *static_cast<const D*>(dp);                                                                                 \
+     const size_t N = d.nmember;                                                                                              \
+     return count;                                                                                                            \
+   },                                                                                                                         \
+   in, out},
+
+// avm_window_batch.  The four state arrays come first so that the packed path can bring them back with one copy (N_STATES).
+#define WIN(member, type, count, in, out) FIELD(avm_window_batch, avm_window_batch, n_windows, "w_" #member, member, type, count, in, out)
+const Field WINDOW_FIELDS[] = {
+    WIN(pose, double, N * 77, U_GEOM | U_PROP, U_WHOLE | U_SLIDE | U_PROP)
+    WIN(speedbias, double, N * 99, U_IMU, U_WHOLE | U_SLIDE | U_PROP)
+    WIN(ex_pose, double, N * 7, U_GEOM, U_WHOLE | U_SLIDE)
+    WIN(inv_depth, double, N * d.max_feat, U_GEOM, U_WHOLE | U_TRI | U_SLIDE)
+    WIN(n_feat, int32_t, N, U_GEOM, U_SLIDE)
+    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM, U_SLIDE)
+    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE, U_SLIDE)
+    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM, U_SLIDE)
+    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM, U_SLIDE)
+    WIN(imu_n, int32_t, N * 10, U_IMU, U_SLIDE)
+    WIN(imu_dt, double, N * 10 * d.max_samp, U_IMU, U_SLIDE)
+    WIN(imu_acc, double, N * 10 * (d.max_samp + 1) * 3, U_IMU, U_SLIDE)
+    WIN(imu_gyr, double, N * 10 * (d.max_samp + 1) * 3, U_IMU, U_SLIDE)
+    WIN(imu_lin_ba, double, N * 30, U_WHOLE | U_SLIDE, U_SLIDE)
+    WIN(imu_lin_bg, double, N * 30, U_WHOLE | U_SLIDE, U_SLIDE)
+    WIN(prior_n, int32_t, N, U_WHOLE, 0)
+    WIN(prior_nblk, int32_t, N, U_WHOLE, 0)
+    WIN(prior_blk_kind, int32_t, N * d.max_pblk, U_WHOLE, 0)
+    WIN(prior_blk_frame, int32_t, N * d.max_pblk, U_WHOLE, 0)
+    WIN(prior_J, double, N * d.max_prior * d.max_prior, U_WHOLE, 0)
+    WIN(prior_r, double, N * d.max_prior, U_WHOLE, 0)
+    WIN(prior_x0, double, N * d.max_pblk * 9, U_WHOLE, 0)
+    WIN(obs_vel_td, double, N * d.max_obs * 4, U_WHOLE, 0)
+    WIN(td, double, N, U_WHOLE, U_WHOLE)  // para_Td: in/out
+    WIN(relo_n, int32_t, N, U_WHOLE, 0)
+    WIN(relo_frame, int32_t, N, U_WHOLE, 0)
+    WIN(relo_feat, int32_t, N * d.max_feat, U_WHOLE, 0)
+    WIN(relo_xy, double, N * d.max_feat * 2, U_WHOLE, 0)
+    WIN(relo_pose, double, N * 7, U_WHOLE, U_WHOLE)  // relo_Pose: in/out
+    WIN(failure_occur, int32_t, N, U_WHOLE, 0)
+    WIN(last_pose0, double, N * 7, U_WHOLE, 0)};
+#undef WIN
+constexpr Table WINDOWS = table_of(WINDOW_FIELDS);
+constexpr int N_STATES = 4;  // pose | speedbias | ex_pose | inv_depth
+
+// avm_prior_out of a batch (one device block "po_pack" in host mode: one memset, and for small batches one copy back)
+#define PO(member, type, count) FIELD(avm_prior_out, avm_window_batch, n_windows, "po_" #member, member, type, count, 0, U_WHOLE)
+const Field PRIOR_OUT_FIELDS[] = {
+    PO(n, int32_t, N) PO(nblk, int32_t, N) PO(blk_kind, int32_t, N * s.max_pblk) PO(blk_frame, int32_t, N * s.max_pblk)
+    PO(J, double, N * s.max_prior * s.max_prior) PO(r, double, N * s.max_prior) PO(x0, double, N * s.max_pblk * 9)};
+#undef PO
+constexpr Table PRIOR_OUT = table_of(PRIOR_OUT_FIELDS);
+
+#define FS(member, type, count) FIELD(avm_fsel_batch, avm_fsel_batch, n_problems, "f_" #member, member, type, count, U_WHOLE, 0)
+const Field FSEL_FIELDS[] = {
+    FS(hor_pos, double, N * (d.horizon + 1) * 3) FS(hor_quat, double, N * (d.horizon + 1) * 4) FS(nr_imu, int32_t, N) FS(delta_imu, double, N)
+    FS(n_cand, int32_t, N) FS(cand_id, int32_t, N * d.max_cand) FS(cand_xy, double, N * d.max_cand * 2) FS(cand_prob, double, N * d.max_cand)
+    FS(n_used, int32_t, N) FS(used_id, int32_t, N * d.max_used) FS(used_xy, double, N * d.max_used * 2)
+    FS(n_cloud, int32_t, N) FS(cloud_xy, double, N * d.max_cloud * 2) FS(cloud_depth, double, N * d.max_cloud)};
+#undef FS
+constexpr Table FSEL = table_of(FSEL_FIELDS);
+
+#define FO(pool, member, type) FIELD(avm_fsel_out, avm_fsel_batch, n_problems, pool, member, type, N * d.max_features, 0, U_WHOLE)
+const Field FSEL_OUT_FIELDS[] = {FIELD(avm_fsel_out, avm_fsel_batch, n_problems, "fo_n", n_selected, int32_t, N, 0, U_WHOLE)
+                                 FO("fo_ids", selected_ids, int32_t) FO("fo_fv", fvalues, double) FO("fo_gap", min_gap, double)};
+#undef FO
+constexpr Table FSEL_OUT = table_of(FSEL_OUT_FIELDS);
+
+#define TD(member, per) FIELD(avm_td_factor_batch, avm_td_factor_batch, n, "td_" #member, member, double, N * per, U_WHOLE, 0)
+const Field TD_FIELDS[] = {TD(pose_i, 7) TD(pose_j, 7) TD(ex_pose, 7) TD(inv_depth, 1) TD(td, 1) TD(pts_i, 2) TD(pts_j, 2)
+                           TD(vel_i, 2) TD(vel_j, 2) TD(td_i, 1) TD(td_j, 1) TD(row_i, 1) TD(row_j, 1)};
+#undef TD
+constexpr Table TD_FACTORS = table_of(TD_FIELDS);
+
+#define HZ(member, type, per) FIELD(avm_fsel_horizon_in, avm_fsel_horizon_in, n_problems, "h_" #member, member, type, N * per, U_WHOLE, 0)
+const Field HORIZON_FIELDS[] = {HZ(k_pos, double, 3) HZ(k_quat, double, 4) HZ(k_ba, double, 3) HZ(k1_pos, double, 3) HZ(k1_vel, double, 3)
+                                HZ(k1_quat, double, 4) HZ(acc, double, 3) HZ(gyr, double, 3) HZ(nr_imu, int32_t, 1) HZ(delta_imu, double, 1)};
+#undef HZ
+constexpr Table HORIZON_IN = table_of(HORIZON_FIELDS);
+
+constexpr size_t PACK_LIMIT = 4u << 20;  // batches up to 4 MiB (a few windows: the real-time use) travel packed
 inline size_t pack_up(size_t n) { return (n + 63) & ~size_t(63); }
 
-// copy a host batch to the device; out = batch with device pointers.  Small batches go through one pinned buffer and
-// one copy (22 pageable copies of a few hundred bytes each cost more than the solve's pre-integration kernel).
-int stage_window_batch(avm_ctx* c, const avm_window_batch* h, avm_window_batch* d) {
-  *d = *h;
-  const size_t B = h->n_windows;
-  int rc;
+// one host array into the pool buffer `name`; a null or empty array gives a null device pointer
+int stage_array(avm_ctx* c, const char* name, const void* host, size_t bytes, const void** dev) {
+  *dev = nullptr;
+  if (!host || bytes == 0) return AVM_OK;
+  void* d = pool_get(c, name, bytes);
+  if (!d) return fail(c, AVM_ERR_HIP, "hipMalloc failed (staging)");
+  HIPCHK(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream));
+  *dev = d;
+  return AVM_OK;
+}
+
+// Copies the tables of the host struct *h that entry point `use` reads to the device and points *d (a copy of *h) at them.  pack: the pool
+// name of the one block - 64-byte aligned parts, in table order, absent tables left out - that the batch travels in when all of it fits
+// PACK_LIMIT: one pinned buffer and one copy (22 pageable copies of a few hundred bytes each cost more than the solve's pre-integration
+// kernel); nullptr: table by table, each into the pool buffer of its name.
+int stage(avm_ctx* c, Table t, unsigned use, const void* h, void* d, const char* pack, bool* packed) {
   size_t total = 0;
-#define SZ(field, type, count) total += h->field ? pack_up(sizeof(type) * (count)) : 0;
-  AVM_WINDOW_FIELDS(SZ, B, h)
-#undef SZ
-  c->packed_in = total <= PACK_LIMIT && h->pose && h->speedbias && h->ex_pose && h->inv_depth;
-  if (c->packed_in) {
-    char* hp = static_cast<char*>(pinned_get(c, "w_pack", total));
-    char* dp = static_cast<char*>(pool_get(c, "w_pack", total));
-    if (!hp || !dp) return fail(c, AVM_ERR_HIP, "allocation failed (packed staging)");
-    size_t off = 0;
-#define PK(field, type, count)                                             \
-  if (h->field) {                                                          \
-    std::memcpy(hp + off, h->field, sizeof(type) * (count));               \
-    *(const type**)&d->field = reinterpret_cast<const type*>(dp + off);    \
-    off += pack_up(sizeof(type) * (count));                                \
-  }
-    AVM_WINDOW_FIELDS(PK, B, h)
-#undef PK
-    HIPCHK(c, hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, c->stream));
+  for (const Field& f : t)
+    if ((f.in & use) && get_ptr(h, f)) total += pack_up(f.bytes(h, h));
+  const bool pk = pack && total <= PACK_LIMIT;
+  if (packed) *packed = pk;
+  if (!pk) {
+    for (const Field& f : t) {
+      if (!(f.in & use)) continue;
+      const void* dev;
+      const int rc = stage_array(c, f.pool, get_ptr(h, f), f.bytes(h, h), &dev);
+      if (rc != AVM_OK) return rc;
+      set_ptr(d, f, dev);
+    }
     return AVM_OK;
   }
-#define ST(field, type, count) \
-  if ((rc = stage_in<type>(c, "w_" #field, h->field, (count), (const type**)&d->field)) != AVM_OK) return rc;
-  AVM_WINDOW_FIELDS(ST, B, h)
-#undef ST
-  return AVM_OK;
-}
-
-// the four state arrays back to the caller (after the kernels, before the final synchronize)
-int unstage_window_states(avm_ctx* c, const avm_window_batch* h, const avm_window_batch* d, char** pinned_states) {
-  const size_t B = h->n_windows;
-  *pinned_states = nullptr;
-  if (c->packed_in) {
-    // pose | speedbias | ex_pose | inv_depth are the first four blocks of the packed buffer
-    const size_t bytes = pack_up(sizeof(double) * B * 77) + pack_up(sizeof(double) * B * 99) + pack_up(sizeof(double) * B * 7) +
-                         pack_up(sizeof(double) * B * h->max_feat);
-    char* hp = static_cast<char*>(pinned_get(c, "w_states", bytes));
-    if (!hp) return fail(c, AVM_ERR_HIP, "allocation failed (packed states)");
-    HIPCHK(c, hipMemcpyAsync(hp, d->pose, bytes, hipMemcpyDeviceToHost, c->stream));
-    *pinned_states = hp;
-    return AVM_OK;
-  }
-  HIPCHK(c, hipMemcpyAsync(h->pose, d->pose, sizeof(double) * B * 77, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->speedbias, d->speedbias, sizeof(double) * B * 99, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->ex_pose, d->ex_pose, sizeof(double) * B * 7, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h->inv_depth, d->inv_depth, sizeof(double) * B * h->max_feat, hipMemcpyDeviceToHost, c->stream));
-  return AVM_OK;
-}
-
-// the optional in/out members (para_Td, relo_Pose) back to the caller
-int unstage_window_extras(avm_ctx* c, const avm_window_batch* h, const avm_window_batch* d) {
-  const size_t B = h->n_windows;
-  if (h->td && d->td) HIPCHK(c, hipMemcpyAsync(h->td, d->td, sizeof(double) * B, hipMemcpyDeviceToHost, c->stream));
-  if (h->relo_pose && d->relo_pose) HIPCHK(c, hipMemcpyAsync(h->relo_pose, d->relo_pose, sizeof(double) * B * 7, hipMemcpyDeviceToHost, c->stream));
-  return AVM_OK;
-}
-
-// after the synchronize: scatter the packed states into the caller's arrays
-void finish_window_states(const avm_window_batch* h, const char* pinned_states) {
-  if (!pinned_states) return;
-  const size_t B = h->n_windows;
+  char* hp = static_cast<char*>(pool_get(c, pack, total, PINNED));
+  char* dp = static_cast<char*>(pool_get(c, pack, total));
+  if (!hp || !dp) return fail(c, AVM_ERR_HIP, "allocation failed (packed staging)");
   size_t off = 0;
-  std::memcpy(h->pose, pinned_states + off, sizeof(double) * B * 77), off += pack_up(sizeof(double) * B * 77);
-  std::memcpy(h->speedbias, pinned_states + off, sizeof(double) * B * 99), off += pack_up(sizeof(double) * B * 99);
-  std::memcpy(h->ex_pose, pinned_states + off, sizeof(double) * B * 7), off += pack_up(sizeof(double) * B * 7);
-  std::memcpy(h->inv_depth, pinned_states + off, sizeof(double) * B * h->max_feat);
+  for (const Field& f : t) {
+    const void* host = get_ptr(h, f);
+    if (!(f.in & use) || !host) continue;
+    std::memcpy(hp + off, host, f.bytes(h, h));
+    set_ptr(d, f, dp + off);
+    off += pack_up(f.bytes(h, h));
+  }
+  HIPCHK(c, hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, c->stream));
+  return AVM_OK;
+}
+
+// The caller's struct as the kernels take it: the struct itself (AVM_MEM_DEVICE), or staged (AVM_MEM_HOST).  The entry points that take
+// a subset of the window tables never pack.
+template <class S>
+int on_device(avm_ctx* c, avm_mem mem, Table t, unsigned use, const S* h, S* d, const char* pack = nullptr, bool* packed = nullptr) {
+  *d = *h;
+  if (packed) *packed = false;
+  return mem == AVM_MEM_HOST ? stage(c, t, use, h, d, pack, packed) : AVM_OK;
+}
+
+// the whole window batch: packed when it is small and has its four state arrays, the head of the block
+int windows_on_device(avm_ctx* c, avm_mem mem, const avm_window_batch* h, avm_window_batch* d, bool* packed = nullptr) {
+  const bool states = h->pose && h->speedbias && h->ex_pose && h->inv_depth;
+  return on_device(c, mem, WINDOWS, U_WHOLE, h, d, states ? "w_pack" : nullptr, packed);
+}
+
+// AVM_MEM_HOST: device arrays for the outputs the caller asked for (the non-null members of *h) in *d, a copy of *h - as parts of one
+// block `pack` (its size to *pack_bytes), or each under its own pool name
+int alloc_out(avm_ctx* c, Table t, const void* h, void* d, const void* dims, const char* pack = nullptr, size_t* pack_bytes = nullptr) {
+  size_t total = 0;
+  for (const Field& f : t)
+    if (get_ptr(h, f)) total += pack_up(f.bytes(h, dims));
+  char* block = pack ? static_cast<char*>(pool_get(c, pack, total)) : nullptr;
+  if (pack && !block) return AVM_ERR_HIP;
+  if (pack) *pack_bytes = total;
+  size_t off = 0;
+  for (const Field& f : t) {
+    void* dev = nullptr;
+    if (get_ptr(h, f)) {
+      dev = pack ? block + off : pool_get(c, f.pool, f.bytes(h, dims));
+      if (!dev) return AVM_ERR_HIP;
+      off += pack_up(f.bytes(h, dims));
+    }
+    set_ptr(d, f, dev);
+  }
+  return AVM_OK;
+}
+
+// what copy_back left in pinned memory for scatter
+struct PackedBack {
+  const char* pinned = nullptr;
+  int n = 0;
+};
+
+// AVM_MEM_HOST: the arrays entry point `use` returns, device -> host, enqueued behind the kernels.  The first n_packed of them are the
+// head of one packed block on the device: one copy takes them to the pinned buffer `pin`, and scatter() hands them out after the
+// synchronize.  The others go straight into the caller's arrays.
+int copy_back(avm_ctx* c, avm_mem mem, Table t, unsigned use, const void* h, const void* d, const void* dims, int n_packed = 0,
+              const char* pin = nullptr, PackedBack* back = nullptr) {
+  if (mem != AVM_MEM_HOST) return AVM_OK;
+  int k = 0;
+  size_t bytes = 0;
+  const void* head = nullptr;
+  for (const Field& f : t) {
+    void* host = get_ptr(h, f);
+    if (!(f.out & use) || !host) continue;
+    const void* dev = get_ptr(d, f);
+    if (k++ < n_packed) {
+      if (!head) head = dev;
+      bytes += pack_up(f.bytes(h, dims));
+      if (k < n_packed) continue;
+      char* hp = static_cast<char*>(pool_get(c, pin, bytes, PINNED));
+      if (!hp) return fail(c, AVM_ERR_HIP, "allocation failed (packed copy back)");
+      HIPCHK(c, hipMemcpyAsync(hp, head, bytes, hipMemcpyDeviceToHost, c->stream));
+      back->pinned = hp, back->n = n_packed;
+    } else if (dev) {
+      HIPCHK(c, hipMemcpyAsync(host, dev, f.bytes(h, dims), hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  return AVM_OK;
+}
+
+// after the synchronize: the packed arrays into the caller's own
+void scatter(Table t, unsigned use, const void* h, const void* dims, const PackedBack& back) {
+  int k = 0;
+  size_t off = 0;
+  for (const Field& f : t) {
+    void* host = get_ptr(h, f);
+    if (!(f.out & use) || !host) continue;
+    if (k++ == back.n) break;
+    std::memcpy(host, back.pinned + off, f.bytes(h, dims));
+    off += pack_up(f.bytes(h, dims));
+  }
 }
 
 int run_preint(avm_ctx* c, const avm_options* opt, const avm_window_batch* d) {
@@ -404,6 +551,112 @@ int run_preint(avm_ctx* c, const avm_options* opt, const avm_window_batch* d) {
   launch_preint(pa, c->stream);
   HIPCHK(c, hipGetLastError());
   return AVM_OK;
+}
+
+
+// ---- the steps of avm_window_solve_batch ----
+// Which forms of the kernels a batch takes.  The solve: the throughput form (two 256-thread workgroups per CU, window_solve_tp.o) for
+// batches that give every CU more than one window, the latency form (one 512-thread workgroup per CU) otherwise - and always for the
+// extended problem or a prior the structural form cannot hold (tp_misfit bit 0).  (Round 5: a wall-clock cap no longer forces the latency
+// form - both kernels check options.max_solver_time_in_seconds against a clock that starts with the window's own solve, and a batch that
+// is larger than the CU count is not a real-time call.  A window shares its CU there and runs 1.6 ms instead of 0.9: a cap between those
+// two durations ends it an iteration earlier than the latency form would - wall-clock semantics.)  AVM_SOLVE_TP=0 / 1 forces the choice
+// where both are possible (tests, A/B runs).
+// The marginalization follows the solve: its throughput form (two 256-thread workgroups per CU on the solve's 2 x CUs slots) for the
+// batches that took the throughput solve - and for a batch of the extended problem that is larger than the CU count (big_x): the
+// marginalization is the same problem whatever the solve estimated -, unless a prior keeps a speed-bias block beyond frame 1 (tp_misfit
+// bit 1; AVM_MARG_TP=0: never).
+// The environment is read on every call: tests flip it in-process.
+struct SolveForms {
+  bool tp, big_x, marg_tp;
+};
+SolveForms choose_forms(int n_windows, int n_slots, bool extended, bool marg, int tp_misfit) {
+  bool tp = n_windows > n_slots;
+  if (const char* e = getenv("AVM_SOLVE_TP")) tp = e[0] == '1' ? true : (e[0] == '0' ? false : tp);
+  tp = tp && !extended && (tp_misfit & 1) == 0;
+  const bool big_x = extended && marg && n_windows > n_slots;
+  bool marg_tp = (tp || big_x) && (tp_misfit & 2) == 0;
+  if (const char* e = getenv("AVM_MARG_TP")) marg_tp = marg_tp && e[0] != '0';
+  return {tp, big_x, marg_tp};
+}
+
+int check_prior_out(avm_ctx* c, const avm_prior_out* po) {
+  bool all = po != nullptr;
+  for (const Field& f : PRIOR_OUT) all = all && get_ptr(po, f);
+  if (!all) return fail(c, AVM_ERR_INVALID, "prior_out (or one of its arrays) is NULL but marginalization_flag != AVM_MARGIN_NONE");
+  if (po->max_prior > MAXPRIOR || po->max_prior < 1 || po->max_pblk < 1) return fail(c, AVM_ERR_CAPACITY, "prior_out dims");
+  return AVM_OK;
+}
+
+SolveArgs solve_args(const avm_ctx* c, const avm_options* opt, const avm_window_batch& d, avm_solve_summary* d_sum) {
+  SolveArgs sa;
+  sa.b = d, sa.opt = *opt;
+  sa.pre_delta = c->pre_delta, sa.pre_jac = c->pre_jac, sa.pre_sqrt = c->pre_sqrt, sa.pre_sum_dt = c->pre_sum;
+  sa.scratch = c->scratch, sa.iscratch = c->iscratch, sa.summary = d_sum, sa.n_slots = c->n_slots;
+  sa.prof = c->prof;
+  // (a cap that is not finite, or beyond 1e9 s, means "no cap": the conversion to device ticks must not overflow)
+  sa.time_cap_ticks = (opt->max_solver_time_s > 0.0 && opt->max_solver_time_s <= 1.0e9) ? (long long)(opt->max_solver_time_s * c->wall_clock_hz) + 1 : 0;
+  const char* ns = getenv("AVM_NO_SPECULATE");
+  sa.speculate = (ns && ns[0] == '1') ? 0 : 1;
+  return sa;
+}
+
+// the solve kernel in the chosen form; leaves sa.n_slots as the marginalization takes it (two workgroups per CU in its throughput form, else one)
+int run_solve(avm_ctx* c, SolveArgs& sa, bool extended, const SolveForms& forms) {
+  if (c->prof) HIPCHK(c, hipMemsetAsync(c->prof, 0, sizeof(long long) * PROF_SLOTS * 2 * c->n_slots, c->stream));
+  if (forms.tp) {
+    sa.n_slots = 2 * c->n_slots;
+    if (const char* e = getenv("AVM_TP_GRID")) sa.n_slots = std::max(1, std::min(atoi(e), 2 * c->n_slots));  // (experiments: fewer resident workgroups)
+    HIPCHK(c, launch_window_solve_tp(sa, c->stream));
+  } else {
+    // (ex_pose / td as variables, relocalization factors: the build of the solve kernel with the wider dense block)
+    HIPCHK(c, extended ? launch_window_solve_x(sa, c->stream) : launch_window_solve(sa, c->stream));
+  }
+  sa.n_slots = forms.marg_tp ? 2 * c->n_slots : c->n_slots;
+  c->last_solve_tp = forms.tp;
+  c->last_marg_tp = false;
+  return AVM_OK;
+}
+
+// Marginalization and the square root of the new prior, into prior_out (host mode: into the ctx's block, and the copy back enqueued).
+// *marg_err: the device flag the kernel raises when a window's kept set does not fit (prior_out->max_prior / max_pblk, or the 76 rows /
+// 16 blocks the eigen-solver holds): the call then fails with AVM_ERR_CAPACITY instead of returning a truncated prior.
+int run_marginalize(avm_ctx* c, const avm_options* opt, avm_mem mem, const SolveArgs& sa, bool marg_tp, avm_prior_out* prior_out, int** marg_err,
+                    PackedBack* back) {
+  const avm_window_batch* dims = &sa.b;
+  const size_t B = sa.b.n_windows;
+  avm_prior_out dpo = *prior_out;
+  size_t po_bytes = 0;
+  if (mem == AVM_MEM_HOST) {
+    if (alloc_out(c, PRIOR_OUT, prior_out, &dpo, dims, "po_pack", &po_bytes) != AVM_OK) return fail(c, AVM_ERR_HIP, "hipMalloc failed (prior out)");
+    HIPCHK(c, hipMemsetAsync(dpo.n, 0, po_bytes, c->stream));  // (n is the head of the block)
+  }
+  *marg_err = static_cast<int*>(pool_get(c, "marg_err", sizeof(int)));
+  if (!*marg_err) return fail(c, AVM_ERR_HIP, "hipMalloc failed (marginalization flag)");
+  HIPCHK(c, hipMemsetAsync(*marg_err, 0x7f, sizeof(int), c->stream));
+  // the magnitude every diagonal entry of A' was formed at (marginalize_kernel -> the eigenvalue clamp's noise test): the ctx's own array
+  double* marg_scale = static_cast<double*>(pool_get(c, "marg_scale", sizeof(double) * B * prior_out->max_prior));
+  if (!marg_scale) return fail(c, AVM_ERR_HIP, "hipMalloc failed (marginalization scales)");
+  HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+  HIPCHK(c, marg_tp ? launch_marginalize_tp(sa, dpo, *marg_err, marg_scale, c->stream) : launch_marginalize(sa, dpo, *marg_err, marg_scale, c->stream));
+  c->last_marg_tp = marg_tp;
+  HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
+  int* pe_done = static_cast<int*>(pool_get(c, "pe_done", sizeof(int) * B));
+  if (!pe_done) return fail(c, AVM_ERR_HIP, "hipMalloc failed (prior flags)");
+  const double noise_rel = (opt->marg_noise_rel > 0.0 && opt->marg_noise_rel < 1.0) ? opt->marg_noise_rel : 0.0;
+  HIPCHK(c, launch_prior_eig(dpo, B, opt->marg_eps, noise_rel, marg_scale, c->prof, pe_done, c->stream));
+  c->last_marg_windows = (int)B;
+  HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+  return copy_back(c, mem, PRIOR_OUT, U_WHOLE, prior_out, &dpo, dims, po_bytes <= PACK_LIMIT ? (int)PRIOR_OUT.n : 0, "po_pack", back);
+}
+
+void record_solve_timings(avm_ctx* c, bool marg) {
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->last_ms["preint"] = ms;
+  if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) c->last_ms["window_solve"] = ms;
+  c->last_ms["marginalize"] = 0.f, c->last_ms["prior_eig"] = 0.f;
+  if (marg && hipEventElapsedTime(&ms, c->ev[6], c->ev[7]) == hipSuccess) c->last_ms["marginalize"] = ms;
+  if (marg && hipEventElapsedTime(&ms, c->ev[7], c->ev[5]) == hipSuccess) c->last_ms["prior_eig"] = ms;
 }
 
 }  // namespace
@@ -578,179 +831,72 @@ int avm_window_solve_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, cons
   int rc = check_window_batch(c, opt, batch);
   if (rc != AVM_OK) return rc;
   const bool marg = opt->marginalization_flag != AVM_MARGIN_NONE;
-  if (marg) {
-    if (!prior_out || !prior_out->n || !prior_out->nblk || !prior_out->blk_kind || !prior_out->blk_frame || !prior_out->J || !prior_out->r ||
-        !prior_out->x0)
-      return fail(c, AVM_ERR_INVALID, "prior_out (or one of its arrays) is NULL but marginalization_flag != AVM_MARGIN_NONE");
-    if (prior_out->max_prior > MAXPRIOR || prior_out->max_prior < 1 || prior_out->max_pblk < 1) return fail(c, AVM_ERR_CAPACITY, "prior_out dims");
-  }
+  if (marg && (rc = check_prior_out(c, prior_out)) != AVM_OK) return rc;
   if (batch->n_windows == 0) return AVM_OK;
-  // table check: host tables on the host, now; device-resident ones by a kernel whose verdict is read while the pre-integration runs
+  // table check: host tables on the host, now; device-resident ones by a kernel whose verdict is read while the pre-integration runs.
+  // On the early error paths below a check in flight is drained before the caller may free its tables.
   int tp_misfit = 0;
-  int* vflag_host = nullptr;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &tp_misfit)) != AVM_OK) return rc;
-  } else {
-    if ((rc = validate_windows_begin(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &vflag_host)) != AVM_OK) return rc;
-  }
-  // Which form of the solve kernel: the throughput form (two 256-thread workgroups per CU, window_solve_tp.o) for batches that give
-  // every CU more than one window, the latency form (one 512-thread workgroup per CU) otherwise - and always for the extended
-  // problem or a prior the structural form cannot hold.  (Round 5: a wall-clock cap no longer forces the latency form - both kernels
-  // check options.max_solver_time_in_seconds against a clock that starts with the window's own solve, and a batch that is larger than
-  // the CU count is not a real-time call.  A window shares its CU there and runs 1.6 ms instead of 0.9: a cap between those two
-  // durations ends it an iteration earlier than the latency form would - wall-clock semantics.)
-  // AVM_SOLVE_TP=0 / 1 forces the choice where both are possible (tests, A/B runs).
+  FlagCheck check;
+  rc = mem == AVM_MEM_HOST ? validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &tp_misfit)
+                           : validate_windows_begin(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &check);
+  if (rc != AVM_OK) return rc;
+
+  // choose forms (the slots for the throughput forms are sized before the priors' verdict is in: a batch that then takes the latency forms uses half of them)
   const bool extended = opt->estimate_extrinsic != 0 || opt->estimate_td != 0 || batch->relo_n != nullptr;
-  bool use_tp = batch->n_windows > c->n_slots;
-  if (const char* e = getenv("AVM_SOLVE_TP")) use_tp = e[0] == '1' ? true : (e[0] == '0' ? false : use_tp);
-  use_tp = use_tp && !extended;
-  // (the marginalization is the same problem whatever the solve estimated: a large batch of the extended problem takes its throughput form too)
-  const bool big_x = extended && marg && batch->n_windows > c->n_slots;
-  // (the slots for the throughput forms are sized before the priors' verdict is in: a batch that then takes the latency forms uses half of them)
-  if ((rc = ensure_window_buffers(c, batch->n_windows, use_tp || big_x)) != AVM_OK) {
-    if (vflag_host) (void)hipStreamSynchronize(c->stream);
+  SolveForms forms = choose_forms(batch->n_windows, c->n_slots, extended, marg, 0);
+  if ((rc = ensure_window_buffers(c, batch->n_windows, forms.tp || forms.big_x)) != AVM_OK) {
+    if (check.dev) (void)hipStreamSynchronize(c->stream);
     return rc;
   }
+
+  // stage
   avm_window_batch d;
-  avm_solve_summary* d_sum = nullptr;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = stage_window_batch(c, batch, &d)) != AVM_OK) return rc;
-    if (summary) {
-      d_sum = static_cast<avm_solve_summary*>(pool_get(c, "w_summary", sizeof(avm_solve_summary) * batch->n_windows));
-      if (!d_sum) return fail(c, AVM_ERR_HIP, "hipMalloc failed (summary)");
-    }
-  } else {
-    d = *batch;
-    d_sum = summary;
+  bool packed;
+  if ((rc = windows_on_device(c, mem, batch, &d, &packed)) != AVM_OK) return rc;
+  avm_solve_summary* d_sum = summary;
+  if (mem == AVM_MEM_HOST && summary) {
+    d_sum = static_cast<avm_solve_summary*>(pool_get(c, "w_summary", sizeof(avm_solve_summary) * batch->n_windows));
+    if (!d_sum) return fail(c, AVM_ERR_HIP, "hipMalloc failed (summary)");
   }
+
+  // pre-integrate, and the verdict of the table check
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   if ((rc = run_preint(c, opt, &d)) != AVM_OK) {
-    if (vflag_host) (void)hipStreamSynchronize(c->stream);  // (the table check of a device-resident batch is still in flight: drain it before the caller may free its tables)
+    if (check.dev) (void)hipStreamSynchronize(c->stream);
     return rc;
   }
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  if (vflag_host && (rc = validate_windows_end(c, vflag_host, &tp_misfit)) != AVM_OK) return rc;
-  use_tp = use_tp && (tp_misfit & 1) == 0;
-  // ... and the marginalization follows the solve: its throughput form (two 256-thread workgroups per CU on the solve's 2 x CUs slots)
-  // for the batches that took the throughput solve - and for a batch of the extended problem that is larger than the CU count: the marginalization
-  // does not depend on what the solve estimated -, unless a prior keeps a speed-bias block beyond frame 1 (AVM_MARG_TP=0: never)
-  bool use_marg_tp = (use_tp || big_x) && (tp_misfit & 2) == 0;
-  if (const char* e = getenv("AVM_MARG_TP")) use_marg_tp = use_marg_tp && e[0] != '0';
-  SolveArgs sa;
-  sa.b = d, sa.opt = *opt;
-  sa.pre_delta = c->pre_delta, sa.pre_jac = c->pre_jac, sa.pre_sqrt = c->pre_sqrt, sa.pre_sum_dt = c->pre_sum;
-  sa.scratch = c->scratch, sa.iscratch = c->iscratch, sa.summary = d_sum, sa.n_slots = c->n_slots;
-  sa.prof = c->prof;
-  // (a cap that is not finite, or beyond 1e9 s, means "no cap": the conversion to device ticks must not overflow)
-  sa.time_cap_ticks = (opt->max_solver_time_s > 0.0 && opt->max_solver_time_s <= 1.0e9) ? (long long)(opt->max_solver_time_s * c->wall_clock_hz) + 1 : 0;
-  {
-    const char* ns = getenv("AVM_NO_SPECULATE");
-    sa.speculate = (ns && ns[0] == '1') ? 0 : 1;
-  }
-  if (c->prof) HIPCHK(c, hipMemsetAsync(c->prof, 0, sizeof(long long) * PROF_SLOTS * 2 * c->n_slots, c->stream));
-  // ex_pose / td as variables, relocalization factors: the build of the solve kernel with the wider dense block
-  if (use_tp) {
-    sa.n_slots = 2 * c->n_slots;
-    if (const char* e = getenv("AVM_TP_GRID")) sa.n_slots = std::max(1, std::min(atoi(e), 2 * c->n_slots));  // (experiments: fewer resident workgroups)
-    HIPCHK(c, launch_window_solve_tp(sa, c->stream));
-    sa.n_slots = use_marg_tp ? 2 * c->n_slots : c->n_slots;  // (the marginalization below: two workgroups per CU in its throughput form, else one)
-  } else {
-    HIPCHK(c, extended ? launch_window_solve_x(sa, c->stream) : launch_window_solve(sa, c->stream));
-    sa.n_slots = use_marg_tp ? 2 * c->n_slots : c->n_slots;
-  }
-  c->last_solve_tp = use_tp;
-  c->last_marg_tp = false;
+  if (check.dev && (rc = flag_end(c, check, "window", &tp_misfit)) != AVM_OK) return rc;
+  forms = choose_forms(batch->n_windows, c->n_slots, extended, marg, tp_misfit);
+
+  // solve
+  SolveArgs sa = solve_args(c, opt, d, d_sum);
+  if ((rc = run_solve(c, sa, extended, forms)) != AVM_OK) return rc;
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  avm_prior_out dpo;
+
+  // marginalize and take the square root
   int* marg_err = nullptr;
+  PackedBack prior_back;
+  if (marg && (rc = run_marginalize(c, opt, mem, sa, forms.marg_tp, prior_out, &marg_err, &prior_back)) != AVM_OK) return rc;
+
+  // return outputs: the states (a packed batch: its four head blocks as one copy), para_Td / relo_Pose, the summaries - one synchronize
+  PackedBack states_back;
+  if ((rc = copy_back(c, mem, WINDOWS, U_WHOLE, batch, &d, batch, packed ? N_STATES : 0, "w_states", &states_back)) != AVM_OK) return rc;
+  if (mem == AVM_MEM_HOST && summary)
+    HIPCHK(c, hipMemcpyAsync(summary, d_sum, sizeof(avm_solve_summary) * batch->n_windows, hipMemcpyDeviceToHost, c->stream));
   int marg_err_host = 0x7f7f7f7f;
-  char* po_pinned = nullptr;
-  size_t po_offsets[7] = {0, 0, 0, 0, 0, 0, 0};
-  if (marg) {
-    const size_t B = batch->n_windows, mp = prior_out->max_prior, mb = prior_out->max_pblk;
-    dpo = *prior_out;
-    char* po_dev = nullptr;
-    size_t po_bytes = 0, po_off[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (mem == AVM_MEM_HOST) {
-      // one device block n | nblk | blk_kind | blk_frame | J | r | x0: one memset, and (small batches) one copy back
-      const size_t sz[7] = {sizeof(int32_t) * B, sizeof(int32_t) * B, sizeof(int32_t) * B * mb, sizeof(int32_t) * B * mb,
-                            sizeof(double) * B * mp * mp, sizeof(double) * B * mp, sizeof(double) * B * mb * 9};
-      for (int k = 0; k < 7; k++) po_off[k] = po_bytes, po_bytes += pack_up(sz[k]);
-      po_dev = static_cast<char*>(pool_get(c, "po_pack", po_bytes));
-      if (!po_dev) return fail(c, AVM_ERR_HIP, "hipMalloc failed (prior out)");
-      dpo.n = reinterpret_cast<int32_t*>(po_dev + po_off[0]), dpo.nblk = reinterpret_cast<int32_t*>(po_dev + po_off[1]);
-      dpo.blk_kind = reinterpret_cast<int32_t*>(po_dev + po_off[2]), dpo.blk_frame = reinterpret_cast<int32_t*>(po_dev + po_off[3]);
-      dpo.J = reinterpret_cast<double*>(po_dev + po_off[4]), dpo.r = reinterpret_cast<double*>(po_dev + po_off[5]);
-      dpo.x0 = reinterpret_cast<double*>(po_dev + po_off[6]);
-      HIPCHK(c, hipMemsetAsync(po_dev, 0, po_bytes, c->stream));
-    }
-    // raised by the kernel when a window's kept set does not fit (prior_out->max_prior / max_pblk, or the 76 rows /
-    // 16 blocks the eigen-solver holds): the call then fails with AVM_ERR_CAPACITY instead of returning a truncated prior
-    marg_err = static_cast<int*>(pool_get(c, "marg_err", sizeof(int)));
-    if (!marg_err) return fail(c, AVM_ERR_HIP, "hipMalloc failed (marginalization flag)");
-    HIPCHK(c, hipMemsetAsync(marg_err, 0x7f, sizeof(int), c->stream));
-    // the magnitude every diagonal entry of A' was formed at (marginalize_kernel -> the eigenvalue clamp's noise test): the ctx's own array
-    double* marg_scale = static_cast<double*>(pool_get(c, "marg_scale", sizeof(double) * B * mp));
-    if (!marg_scale) return fail(c, AVM_ERR_HIP, "hipMalloc failed (marginalization scales)");
-    HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(c, use_marg_tp ? launch_marginalize_tp(sa, dpo, marg_err, marg_scale, c->stream) : launch_marginalize(sa, dpo, marg_err, marg_scale, c->stream));
-    c->last_marg_tp = use_marg_tp;
-    HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
-    int* pe_done = static_cast<int*>(pool_get(c, "pe_done", sizeof(int) * B));
-    if (!pe_done) return fail(c, AVM_ERR_HIP, "hipMalloc failed (prior flags)");
-    const double noise_rel = (opt->marg_noise_rel > 0.0 && opt->marg_noise_rel < 1.0) ? opt->marg_noise_rel : 0.0;
-    HIPCHK(c, launch_prior_eig(dpo, B, opt->marg_eps, noise_rel, marg_scale, c->prof, pe_done, c->stream));
-    c->last_marg_windows = (int)B;
-    HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
-    if (mem == AVM_MEM_HOST) {
-      if (po_bytes <= PACK_LIMIT) {
-        po_pinned = static_cast<char*>(pinned_get(c, "po_pack", po_bytes));
-        if (!po_pinned) return fail(c, AVM_ERR_HIP, "allocation failed (packed prior out)");
-        HIPCHK(c, hipMemcpyAsync(po_pinned, po_dev, po_bytes, hipMemcpyDeviceToHost, c->stream));
-        for (int k = 0; k < 7; k++) po_offsets[k] = po_off[k];
-      } else {
-        HIPCHK(c, hipMemcpyAsync(prior_out->n, dpo.n, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(prior_out->nblk, dpo.nblk, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(prior_out->blk_kind, dpo.blk_kind, sizeof(int32_t) * B * mb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(prior_out->blk_frame, dpo.blk_frame, sizeof(int32_t) * B * mb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(prior_out->J, dpo.J, sizeof(double) * B * mp * mp, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(prior_out->r, dpo.r, sizeof(double) * B * mp, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(prior_out->x0, dpo.x0, sizeof(double) * B * mb * 9, hipMemcpyDeviceToHost, c->stream));
-      }
-    }
-  }
-  char* pinned_states = nullptr;
-  if (mem == AVM_MEM_HOST) {
-    const size_t B = batch->n_windows;
-    if ((rc = unstage_window_states(c, batch, &d, &pinned_states)) != AVM_OK) return rc;
-    if ((rc = unstage_window_extras(c, batch, &d)) != AVM_OK) return rc;
-    if (summary) HIPCHK(c, hipMemcpyAsync(summary, d_sum, sizeof(avm_solve_summary) * B, hipMemcpyDeviceToHost, c->stream));
-  }
   if (marg_err) HIPCHK(c, hipMemcpyAsync(&marg_err_host, marg_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (mem == AVM_MEM_HOST) finish_window_states(batch, pinned_states);  // (also before a capacity error: the states WERE solved)
+  scatter(WINDOWS, U_WHOLE, batch, batch, states_back);  // (also before a capacity error: the states WERE solved)
   if (marg_err_host != 0x7f7f7f7f) {
     c->err = "window " + std::to_string(marg_err_host) +
              ": the new prior does not fit (prior_out->max_prior / max_pblk too small, or more than 76 rows / 16 blocks to keep); "
              "the states were solved, prior_out is not valid";
     return AVM_ERR_CAPACITY;
   }
-  if (po_pinned) {
-    const size_t B = batch->n_windows, mp = prior_out->max_prior, mb = prior_out->max_pblk;
-    std::memcpy(prior_out->n, po_pinned + po_offsets[0], sizeof(int32_t) * B);
-    std::memcpy(prior_out->nblk, po_pinned + po_offsets[1], sizeof(int32_t) * B);
-    std::memcpy(prior_out->blk_kind, po_pinned + po_offsets[2], sizeof(int32_t) * B * mb);
-    std::memcpy(prior_out->blk_frame, po_pinned + po_offsets[3], sizeof(int32_t) * B * mb);
-    std::memcpy(prior_out->J, po_pinned + po_offsets[4], sizeof(double) * B * mp * mp);
-    std::memcpy(prior_out->r, po_pinned + po_offsets[5], sizeof(double) * B * mp);
-    std::memcpy(prior_out->x0, po_pinned + po_offsets[6], sizeof(double) * B * mb * 9);
-  }
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->last_ms["preint"] = ms;
-  if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) c->last_ms["window_solve"] = ms;
-  c->last_ms["marginalize"] = 0.f, c->last_ms["prior_eig"] = 0.f;
-  if (marg && hipEventElapsedTime(&ms, c->ev[6], c->ev[7]) == hipSuccess) c->last_ms["marginalize"] = ms;
-  if (marg && hipEventElapsedTime(&ms, c->ev[7], c->ev[5]) == hipSuccess) c->last_ms["prior_eig"] = ms;
+  if (marg) scatter(PRIOR_OUT, U_WHOLE, prior_out, batch, prior_back);
+
+  record_solve_timings(c, marg);
   return AVM_OK;
 }
 
@@ -771,11 +917,7 @@ int avm_imu_preintegrate_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, 
   if ((rc = validate_windows(c, mem, batch, CHK_IMU)) != AVM_OK) return rc;
   if ((rc = ensure_window_buffers(c, batch->n_windows)) != AVM_OK) return rc;
   avm_window_batch d;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = stage_window_batch(c, batch, &d)) != AVM_OK) return rc;
-  } else {
-    d = *batch;
-  }
+  if ((rc = windows_on_device(c, mem, batch, &d)) != AVM_OK) return rc;
   if ((rc = run_preint(c, opt, &d)) != AVM_OK) return rc;
   const size_t iv = (size_t)batch->n_windows * 10;
   const hipMemcpyKind kind = mem == AVM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -813,11 +955,11 @@ int avm_debug_solve_tp_occupancy(int* out) {
 }
 
 // test hook (not in avm.h): the compile-time tables of the throughput solve's sparse factorization (solve/chol_regs_tables.hpp; exported by solve/chol_regs.hpp); out: >= 512 ints
-int avm_debug_solve_tp_pattern(int* out) { return window_solve_tp_pattern(out); }
 // which = 0: throughput build, 1: latency build, 2: extended build
 int avm_debug_solve_pattern(int which, int* out) {
   return which == 0 ? window_solve_tp_pattern(out) : (which == 1 ? window_solve_pattern(out) : window_solve_x_pattern(out));
 }
+int avm_debug_solve_tp_pattern(int* out) { return avm_debug_solve_pattern(0, out); }
 
 // test / bench hook (not in avm.h): out[0] = device / pinned (re)allocations of this ctx so far, out[1] = windows of the last
 // marginalization whose square root the one-wavefront kernel (prior_chol_kernel) finished, out[2] = windows of that marginalization
@@ -867,37 +1009,16 @@ int avm_triangulate_batch(avm_ctx* c, avm_mem mem, avm_window_batch* batch, doub
   if (!c) return AVM_ERR_INVALID;
   (void)hipSetDevice(c->device);
   if (!batch || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
-  {
-    const int crc = check_wide_strides(c, batch);  // (the API's table contract: the kernel runs one thread per feature, any count)
-    if (crc != AVM_OK) return crc;
-  }
+  int rc = check_wide_strides(c, batch);  // (the API's table contract: the kernel runs one thread per feature, any count)
+  if (rc != AVM_OK) return rc;
   if (batch->n_windows == 0) return AVM_OK;
-  {
-    const int vrc = validate_windows(c, mem, batch, CHK_TRACKS);
-    if (vrc != AVM_OK) return vrc;
-  }
-  const size_t B = batch->n_windows;
-  avm_window_batch d = *batch;
-  if (mem == AVM_MEM_HOST) {
-    // only the fields the triangulation reads travel
-    int rc;
-#define ST(field, type, count)                                                                                        \
-  if ((rc = stage_in<type>(c, "w_" #field, batch->field, (count), (const type**)&d.field)) != AVM_OK) return rc;
-    ST(pose, double, B * 77)
-    ST(ex_pose, double, B * 7)
-    ST(inv_depth, double, B * batch->max_feat)
-    ST(n_feat, int32_t, B)
-    ST(feat_start, int32_t, B * batch->max_feat)
-    ST(feat_nobs, int32_t, B * batch->max_feat)
-    ST(feat_obs_begin, int32_t, B * batch->max_feat)
-    ST(obs_xy, double, B * batch->max_obs * 2)
-#undef ST
-  }
+  if ((rc = validate_windows(c, mem, batch, CHK_TRACKS)) != AVM_OK) return rc;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_TRI, batch, &d)) != AVM_OK) return rc;
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
   HIPCHK(c, launch_triangulate(d, init_depth, c->stream));
   HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
-  if (mem == AVM_MEM_HOST)
-    HIPCHK(c, hipMemcpyAsync(batch->inv_depth, d.inv_depth, sizeof(double) * B * batch->max_feat, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = copy_back(c, mem, WINDOWS, U_TRI, batch, &d, batch)) != AVM_OK) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["triangulate"] = ms;
@@ -910,39 +1031,17 @@ int avm_slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, int32_t f
   if (!batch || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (flag != AVM_MARGIN_OLD && flag != AVM_MARGIN_SECOND_NEW) return fail(c, AVM_ERR_INVALID, "marginalization_flag must be MARGIN_OLD or MARGIN_SECOND_NEW");
   if (batch->n_windows == 0) return AVM_OK;
-  {
-    const int vrc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU);
-    if (vrc != AVM_OK) return vrc;
-  }
-  const size_t B = batch->n_windows;
-  avm_window_batch d = *batch;
-  // (field, element type, elements) of everything the roll reads or rewrites
-#define AVM_SLIDE_FIELDS(X)                                                                                              \
-  X(pose, double, B * 77) X(speedbias, double, B * 99) X(ex_pose, double, B * 7) X(inv_depth, double, B * batch->max_feat)    \
-  X(n_feat, int32_t, B) X(feat_start, int32_t, B * batch->max_feat) X(feat_nobs, int32_t, B * batch->max_feat)                \
-  X(feat_obs_begin, int32_t, B * batch->max_feat) X(obs_xy, double, B * batch->max_obs * 2) X(imu_n, int32_t, B * 10)         \
-  X(imu_dt, double, B * 10 * batch->max_samp) X(imu_acc, double, B * 10 * (batch->max_samp + 1) * 3)                          \
-  X(imu_gyr, double, B * 10 * (batch->max_samp + 1) * 3) X(imu_lin_ba, double, B * 30) X(imu_lin_bg, double, B * 30)
-  if (mem == AVM_MEM_HOST) {
-    int rc;
-#define ST(field, type, count) \
-  if ((rc = stage_in<type>(c, "w_" #field, batch->field, (count), (const type**)&d.field)) != AVM_OK) return rc;
-    AVM_SLIDE_FIELDS(ST)
-#undef ST
-  }
+  int rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU);
+  if (rc != AVM_OK) return rc;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_SLIDE, batch, &d)) != AVM_OK) return rc;
   int* derr = static_cast<int*>(pool_get(c, "slide_err", sizeof(int)));
   if (!derr) return fail(c, AVM_ERR_HIP, "hipMalloc failed (slide flag)");
   HIPCHK(c, hipMemsetAsync(derr, 0, sizeof(int), c->stream));
   HIPCHK(c, launch_slide_window(d, flag, shift_depth, init_depth, derr, c->stream));
   int herr = 0;
   HIPCHK(c, hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (mem == AVM_MEM_HOST) {
-#define BK(field, type, count) \
-  HIPCHK(c, hipMemcpyAsync(const_cast<type*>(batch->field), d.field, sizeof(type) * (count), hipMemcpyDeviceToHost, c->stream));
-    AVM_SLIDE_FIELDS(BK)
-#undef BK
-  }
-#undef AVM_SLIDE_FIELDS
+  if ((rc = copy_back(c, mem, WINDOWS, U_SLIDE, batch, &d, batch)) != AVM_OK) return rc;  // (everything the roll rewrites)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (herr) return fail(c, AVM_ERR_CAPACITY, "MARGIN_SECOND_NEW: interval 8 + interval 9 exceed max_samp samples");
   return AVM_OK;
@@ -953,29 +1052,12 @@ int avm_imu_propagate_batch(avm_ctx* c, avm_mem mem, avm_window_batch* batch, co
   (void)hipSetDevice(c->device);
   if (!batch || !g || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (batch->n_windows == 0) return AVM_OK;
-  {
-    const int vrc = validate_windows(c, mem, batch, CHK_IMU);
-    if (vrc != AVM_OK) return vrc;
-  }
-  const size_t B = batch->n_windows;
-  avm_window_batch d = *batch;
-  if (mem == AVM_MEM_HOST) {
-    int rc;
-#define ST(field, type, count)                                                                                        \
-  if ((rc = stage_in<type>(c, "w_" #field, batch->field, (count), (const type**)&d.field)) != AVM_OK) return rc;
-    ST(pose, double, B * 77)
-    ST(speedbias, double, B * 99)
-    ST(imu_n, int32_t, B * 10)
-    ST(imu_dt, double, B * 10 * batch->max_samp)
-    ST(imu_acc, double, B * 10 * (batch->max_samp + 1) * 3)
-    ST(imu_gyr, double, B * 10 * (batch->max_samp + 1) * 3)
-#undef ST
-  }
+  int rc = validate_windows(c, mem, batch, CHK_IMU);
+  if (rc != AVM_OK) return rc;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_PROP, batch, &d)) != AVM_OK) return rc;
   HIPCHK(c, launch_imu_propagate(d, g, c->stream));
-  if (mem == AVM_MEM_HOST) {
-    HIPCHK(c, hipMemcpyAsync(batch->pose, d.pose, sizeof(double) * B * 77, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(batch->speedbias, d.speedbias, sizeof(double) * B * 99, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = copy_back(c, mem, WINDOWS, U_PROP, batch, &d, batch)) != AVM_OK) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return AVM_OK;
 }
@@ -986,16 +1068,11 @@ int avm_projection_td_eval(avm_ctx* c, avm_mem mem, const avm_td_factor_batch* f
   if (!f || !residual || f->n < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (f->n == 0) return AVM_OK;
   const size_t n = f->n;
-  avm_td_factor_batch d = *f;
+  avm_td_factor_batch d;
+  const int rc = on_device(c, mem, TD_FACTORS, U_WHOLE, f, &d);
+  if (rc != AVM_OK) return rc;
   double *dr = residual, *dj = jac;
   if (mem == AVM_MEM_HOST) {
-    int rc;
-#define ST(field, count)                                                                                          \
-  if ((rc = stage_in<double>(c, "td_" #field, f->field, (count), (const double**)&d.field)) != AVM_OK) return rc;
-    ST(pose_i, n * 7) ST(pose_j, n * 7) ST(ex_pose, n * 7) ST(inv_depth, n) ST(td, n)
-    ST(pts_i, n * 2) ST(pts_j, n * 2) ST(vel_i, n * 2) ST(vel_j, n * 2)
-    ST(td_i, n) ST(td_j, n) ST(row_i, n) ST(row_j, n)
-#undef ST
     dr = static_cast<double*>(pool_get(c, "td_res", sizeof(double) * n * 2));
     dj = jac ? static_cast<double*>(pool_get(c, "td_jac", sizeof(double) * n * 40)) : nullptr;
     if (!dr || (jac && !dj)) return fail(c, AVM_ERR_HIP, "hipMalloc failed (td factor out)");
@@ -1019,6 +1096,7 @@ int avm_window_eval_factors(avm_ctx* c, const avm_options* opt, avm_mem mem, con
   if ((rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR)) != AVM_OK) return rc;
   if ((rc = ensure_window_buffers(c, batch->n_windows)) != AVM_OK) return rc;
   avm_window_batch d;
+  if ((rc = windows_on_device(c, mem, batch, &d)) != AVM_OK) return rc;
   const size_t B = batch->n_windows;
   EvalArgs ea;
   struct Out {
@@ -1030,19 +1108,13 @@ int avm_window_eval_factors(avm_ctx* c, const avm_options* opt, avm_mem mem, con
   Out outs[6] = {{&ea.proj_r, proj_r, B * batch->max_obs * 2, "e_pr"},   {&ea.proj_J, proj_J, B * batch->max_obs * 26, "e_pJ"},
                  {&ea.imu_r, imu_r, B * 150, "e_ir"},                      {&ea.imu_J, imu_J, B * 4500, "e_iJ"},
                  {&ea.prior_res, prior_res, B * batch->max_prior, "e_pres"}, {&ea.cost, cost, B, "e_cost"}};
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = stage_window_batch(c, batch, &d)) != AVM_OK) return rc;
-    for (auto& o : outs) {
-      *o.dst = nullptr;
-      if (o.host) {
-        *o.dst = static_cast<double*>(pool_get(c, o.name, o.n * sizeof(double)));
-        if (!*o.dst) return fail(c, AVM_ERR_HIP, "hipMalloc failed (eval out)");
-        HIPCHK(c, hipMemsetAsync(*o.dst, 0, o.n * sizeof(double), c->stream));
-      }
+  for (auto& o : outs) {
+    *o.dst = o.host;
+    if (mem == AVM_MEM_HOST && o.host) {
+      *o.dst = static_cast<double*>(pool_get(c, o.name, o.n * sizeof(double)));
+      if (!*o.dst) return fail(c, AVM_ERR_HIP, "hipMalloc failed (eval out)");
+      HIPCHK(c, hipMemsetAsync(*o.dst, 0, o.n * sizeof(double), c->stream));
     }
-  } else {
-    d = *batch;
-    for (auto& o : outs) *o.dst = o.host;
   }
   if ((rc = run_preint(c, opt, &d)) != AVM_OK) return rc;
   ea.b = d, ea.opt = *opt, ea.apply_loss = apply_loss;
@@ -1062,45 +1134,6 @@ int check_fsel(avm_ctx* c, const avm_fsel_batch* b) {
   if (!fsel_horizon_supported(b->horizon)) return fail(c, AVM_ERR_UNSUPPORTED, "horizon must be one of 2,3,5,10,13");
   if (b->max_cand <= 0 || b->max_features < 0) return fail(c, AVM_ERR_INVALID, "bad max_cand / max_features");
   if (b->n_cloud && b->max_cloud > FS_MAX_CLOUD) return fail(c, AVM_ERR_UNSUPPORTED, "max_cloud above 4096 (the kd-tree of the depth cloud is built in LDS)");
-  return AVM_OK;
-}
-
-#define AVM_FSEL_FIELDS(X, P, H1, h)                                                                                  \
-  X(hor_pos, double, (P) * (H1) * 3) X(hor_quat, double, (P) * (H1) * 4) X(nr_imu, int32_t, (P)) X(delta_imu, double, (P))   \
-  X(n_cand, int32_t, (P)) X(cand_id, int32_t, (P) * (h)->max_cand) X(cand_xy, double, (P) * (h)->max_cand * 2)            \
-  X(cand_prob, double, (P) * (h)->max_cand) X(n_used, int32_t, (P)) X(used_id, int32_t, (P) * (h)->max_used)              \
-  X(used_xy, double, (P) * (h)->max_used * 2) X(n_cloud, int32_t, (P)) X(cloud_xy, double, (P) * (h)->max_cloud * 2)      \
-  X(cloud_depth, double, (P) * (h)->max_cloud)
-
-// like stage_window_batch: a frame or a few travel as one pinned copy
-int stage_fsel(avm_ctx* c, const avm_fsel_batch* h, avm_fsel_batch* d) {
-  *d = *h;
-  const size_t P = h->n_problems, H1 = h->horizon + 1;
-  int rc;
-  size_t total = 0;
-#define SZ(field, type, count) total += h->field ? pack_up(sizeof(type) * (count)) : 0;
-  AVM_FSEL_FIELDS(SZ, P, H1, h)
-#undef SZ
-  if (total <= PACK_LIMIT) {
-    char* hp = static_cast<char*>(pinned_get(c, "f_pack", total));
-    char* dp = static_cast<char*>(pool_get(c, "f_pack", total));
-    if (!hp || !dp) return fail(c, AVM_ERR_HIP, "allocation failed (packed staging)");
-    size_t off = 0;
-#define PK(field, type, count)                                             \
-  if (h->field) {                                                          \
-    std::memcpy(hp + off, h->field, sizeof(type) * (count));               \
-    *(const type**)&d->field = reinterpret_cast<const type*>(dp + off);    \
-    off += pack_up(sizeof(type) * (count));                                \
-  }
-    AVM_FSEL_FIELDS(PK, P, H1, h)
-#undef PK
-    HIPCHK(c, hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, c->stream));
-    return AVM_OK;
-  }
-#define ST(field, type, count) \
-  if ((rc = stage_in<type>(c, "f_" #field, h->field, (count), (const type**)&d->field)) != AVM_OK) return rc;
-  AVM_FSEL_FIELDS(ST, P, H1, h)
-#undef ST
   return AVM_OK;
 }
 
@@ -1156,34 +1189,16 @@ int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, 
   if (!out || !out->n_selected || !out->selected_ids) return fail(c, AVM_ERR_INVALID, "null output");
   if (batch->n_problems == 0) return AVM_OK;
   // Host tables are checked on the host.  Device-resident ones by a kernel that runs AHEAD of the select on the same stream:
-  // every kernel of the select looks at its flag before it indexes with a table, and the host reads the flag with the results
-  // (no extra synchronization for the check).
-  int* vflag = nullptr;
-  int32_t* hflag = nullptr;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = validate_fsel(c, mem, batch)) != AVM_OK) return rc;
-  } else {
-    if (!batch->n_cand || !batch->nr_imu) return fail(c, AVM_ERR_INVALID, "null n_cand / nr_imu");
-    vflag = static_cast<int*>(pool_get(c, "v_flag", sizeof(int)));
-    hflag = static_cast<int32_t*>(pinned_get(c, "v_flag_h", sizeof(int32_t)));
-    if (!vflag || !hflag) return fail(c, AVM_ERR_HIP, "allocation failed (validation flag)");
-    HIPCHK(c, hipMemsetAsync(vflag, 0x7f, sizeof(int), c->stream));
-    HIPCHK(c, launch_validate_fsel(*batch, vflag, c->stream));
-  }
+  // every kernel of the select looks at its flag before it indexes with a table, and the host reads the verdict behind the
+  // synchronization that brings the results (no extra round trip for the check).
+  FlagCheck check;
+  if ((rc = mem == AVM_MEM_HOST ? validate_fsel(c, mem, batch) : validate_fsel_begin(c, batch, &check)) != AVM_OK) return rc;
+  int* const vflag = check.dev;
   avm_fsel_batch d;
-  avm_fsel_out dout;
+  if ((rc = on_device(c, mem, FSEL, U_WHOLE, batch, &d, "f_pack")) != AVM_OK) return rc;
+  avm_fsel_out dout = *out;
+  if (mem == AVM_MEM_HOST && alloc_out(c, FSEL_OUT, out, &dout, batch) != AVM_OK) return fail(c, AVM_ERR_HIP, "hipMalloc failed (selector out)");
   const size_t P = batch->n_problems, mf = batch->max_features;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = stage_fsel(c, batch, &d)) != AVM_OK) return rc;
-    dout.n_selected = static_cast<int32_t*>(pool_get(c, "fo_n", sizeof(int32_t) * P));
-    dout.selected_ids = static_cast<int32_t*>(pool_get(c, "fo_ids", sizeof(int32_t) * P * (mf ? mf : 1)));
-    dout.fvalues = out->fvalues ? static_cast<double*>(pool_get(c, "fo_fv", sizeof(double) * P * (mf ? mf : 1))) : nullptr;
-    dout.min_gap = out->min_gap ? static_cast<double*>(pool_get(c, "fo_gap", sizeof(double) * P * (mf ? mf : 1))) : nullptr;
-    if (!dout.n_selected || !dout.selected_ids) return fail(c, AVM_ERR_HIP, "hipMalloc failed (selector out)");
-  } else {
-    d = *batch;
-    dout = *out;
-  }
   FselBuffers w;
   if ((rc = fsel_buffers(c, &d, &w, fsel_takes_solo(&d))) != AVM_OK) return rc;
   // Every frame's greedy rounds in ONE launch (csrc/fsel/frame_kernel.hpp, fsel_frame_kernel): 2 = a team of workgroups per XCD, the teams
@@ -1205,7 +1220,7 @@ int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, 
   // workgroups, so it cannot time out and is never re-run.  AVM_FSEL_SOLO=0/1 overrides the batch-size rule (tests, measurements).
   if (fsel_takes_solo(&d)) mode = 3;
   c->last_fsel_mode = mode;
-  int32_t* hsync = mode ? static_cast<int32_t*>(pinned_get(c, "f_sync", sizeof(int32_t) * 64)) : nullptr;
+  int32_t* hsync = mode ? static_cast<int32_t*>(pool_get(c, "f_sync", sizeof(int32_t) * 64, PINNED)) : nullptr;
   if (mode && !hsync) mode = 0;
   for (;;) {
     HIPCHK(c, hipMemsetAsync(dout.n_selected, 0, sizeof(int32_t) * P, c->stream));
@@ -1214,15 +1229,9 @@ int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, 
     HIPCHK(c, launch_fsel(d, w, dout, nullptr, true, mode, vflag, c->stream));
     HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
     if (mode) HIPCHK(c, hipMemcpyAsync(hsync, w.sync, sizeof(int32_t) * 64, hipMemcpyDeviceToHost, c->stream));
-    if (mem == AVM_MEM_HOST) {
-      HIPCHK(c, hipMemcpyAsync(out->n_selected, dout.n_selected, sizeof(int32_t) * P, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(out->selected_ids, dout.selected_ids, sizeof(int32_t) * P * mf, hipMemcpyDeviceToHost, c->stream));
-      if (out->fvalues) HIPCHK(c, hipMemcpyAsync(out->fvalues, dout.fvalues, sizeof(double) * P * mf, hipMemcpyDeviceToHost, c->stream));
-      if (out->min_gap) HIPCHK(c, hipMemcpyAsync(out->min_gap, dout.min_gap, sizeof(double) * P * mf, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (vflag) HIPCHK(c, hipMemcpyAsync(hflag, vflag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = copy_back(c, mem, FSEL_OUT, U_WHOLE, out, &dout, batch)) != AVM_OK) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (the one synchronization of the call)
-    if (vflag && *hflag != 0x7f7f7f7f) return report_bad(c, *hflag, "frame");  // (no kernel of the select has touched a table)
+    if (vflag && (rc = flag_end(c, check, "frame")) != AVM_OK) return rc;  // (no kernel of the select has touched a table)
     if (!mode) break;
     if (getenv("AVM_FSEL_TRACE")) {  // (cycle counters of a -DFS_TRACE_EVAL build of fsel.hip; zeros otherwise)
       const long long* q = reinterpret_cast<const long long*>(hsync + 32);
@@ -1276,23 +1285,11 @@ int avm_fsel_horizon_imu(avm_ctx* c, avm_mem mem, const avm_fsel_horizon_in* in,
   if (!in || !hor_pos || !hor_quat || in->n_problems < 0 || in->horizon < 1) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (in->n_problems == 0) return AVM_OK;
   const size_t P = in->n_problems, H1 = (size_t)in->horizon + 1;
-  avm_fsel_horizon_in d = *in;
+  avm_fsel_horizon_in d;
+  const int rc = on_device(c, mem, HORIZON_IN, U_WHOLE, in, &d);
+  if (rc != AVM_OK) return rc;
   double *dp = hor_pos, *dq = hor_quat;
   if (mem == AVM_MEM_HOST) {
-    int rc;
-#define ST(field, type, count)                                                                                     \
-  if ((rc = stage_in<type>(c, "h_" #field, in->field, (count), (const type**)&d.field)) != AVM_OK) return rc;
-    ST(k_pos, double, P * 3)
-    ST(k_quat, double, P * 4)
-    ST(k_ba, double, P * 3)
-    ST(k1_pos, double, P * 3)
-    ST(k1_vel, double, P * 3)
-    ST(k1_quat, double, P * 4)
-    ST(acc, double, P * 3)
-    ST(gyr, double, P * 3)
-    ST(nr_imu, int32_t, P)
-    ST(delta_imu, double, P)
-#undef ST
     dp = static_cast<double*>(pool_get(c, "h_pos", sizeof(double) * P * H1 * 3));
     dq = static_cast<double*>(pool_get(c, "h_quat", sizeof(double) * P * H1 * 4));
     if (!dp || !dq) return fail(c, AVM_ERR_HIP, "hipMalloc failed (horizon out)");
@@ -1313,29 +1310,17 @@ int avm_fsel_build_cloud(avm_ctx* c, avm_mem mem, const avm_window_batch* window
   if (!windows || !k1_pos || !k1_quat || !n_cloud || !cloud_xy || !cloud_depth || windows->n_windows < 0 || max_cloud < 1)
     return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (windows->n_windows == 0) return AVM_OK;
-  {
-    const int vrc = validate_windows(c, mem, windows, CHK_TRACKS);
-    if (vrc != AVM_OK) return vrc;
-  }
+  int rc = validate_windows(c, mem, windows, CHK_TRACKS);
+  if (rc != AVM_OK) return rc;
   const size_t B = windows->n_windows;
-  avm_window_batch d = *windows;
-  const double *dp = k1_pos, *dq = k1_quat;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_CLOUD, windows, &d)) != AVM_OK) return rc;
+  const void *dp = k1_pos, *dq = k1_quat;
   int32_t* dn = n_cloud;
   double *dxy = cloud_xy, *ddep = cloud_depth;
   if (mem == AVM_MEM_HOST) {
-    int rc;
-#define ST(field, type, count)                                                                                          \
-  if ((rc = stage_in<type>(c, "w_" #field, windows->field, (count), (const type**)&d.field)) != AVM_OK) return rc;
-    ST(pose, double, B * 77)
-    ST(ex_pose, double, B * 7)
-    ST(inv_depth, double, B * windows->max_feat)
-    ST(n_feat, int32_t, B)
-    ST(feat_start, int32_t, B * windows->max_feat)
-    ST(feat_obs_begin, int32_t, B * windows->max_feat)
-    ST(obs_xy, double, B * windows->max_obs * 2)
-#undef ST
-    if ((rc = stage_in<double>(c, "c_k1p", k1_pos, B * 3, &dp)) != AVM_OK) return rc;
-    if ((rc = stage_in<double>(c, "c_k1q", k1_quat, B * 4, &dq)) != AVM_OK) return rc;
+    if ((rc = stage_array(c, "c_k1p", k1_pos, sizeof(double) * B * 3, &dp)) != AVM_OK) return rc;
+    if ((rc = stage_array(c, "c_k1q", k1_quat, sizeof(double) * B * 4, &dq)) != AVM_OK) return rc;
     dn = static_cast<int32_t*>(pool_get(c, "c_n", sizeof(int32_t) * B));
     dxy = static_cast<double*>(pool_get(c, "c_xy", sizeof(double) * B * max_cloud * 2));
     ddep = static_cast<double*>(pool_get(c, "c_dep", sizeof(double) * B * max_cloud));
@@ -1343,7 +1328,7 @@ int avm_fsel_build_cloud(avm_ctx* c, avm_mem mem, const avm_window_batch* window
     HIPCHK(c, hipMemsetAsync(dxy, 0, sizeof(double) * B * max_cloud * 2, c->stream));
     HIPCHK(c, hipMemsetAsync(ddep, 0, sizeof(double) * B * max_cloud, c->stream));
   }
-  HIPCHK(c, launch_fsel_build_cloud(d, dp, dq, max_cloud, dn, dxy, ddep, c->stream));
+  HIPCHK(c, launch_fsel_build_cloud(d, static_cast<const double*>(dp), static_cast<const double*>(dq), max_cloud, dn, dxy, ddep, c->stream));
   if (mem == AVM_MEM_HOST) {
     HIPCHK(c, hipMemcpyAsync(n_cloud, dn, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cloud_xy, dxy, sizeof(double) * B * max_cloud * 2, hipMemcpyDeviceToHost, c->stream));
@@ -1362,11 +1347,7 @@ int avm_fsel_nn_depth(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, doub
   if (batch->n_problems == 0) return AVM_OK;
   if ((rc = validate_fsel(c, mem, batch)) != AVM_OK) return rc;
   avm_fsel_batch d;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = stage_fsel(c, batch, &d)) != AVM_OK) return rc;
-  } else {
-    d = *batch;
-  }
+  if ((rc = on_device(c, mem, FSEL, U_WHOLE, batch, &d, "f_pack")) != AVM_OK) return rc;
   const size_t n = (size_t)batch->n_problems * batch->max_cand;
   double* dd = mem == AVM_MEM_HOST ? static_cast<double*>(pool_get(c, "fi_nn", sizeof(double) * n)) : depth;
   if (!dd) return fail(c, AVM_ERR_HIP, "hipMalloc failed (nn depth)");
@@ -1387,11 +1368,7 @@ int avm_fsel_information(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, d
   if (batch->n_problems == 0) return AVM_OK;
   if ((rc = validate_fsel(c, mem, batch)) != AVM_OK) return rc;
   avm_fsel_batch d;
-  if (mem == AVM_MEM_HOST) {
-    if ((rc = stage_fsel(c, batch, &d)) != AVM_OK) return rc;
-  } else {
-    d = *batch;
-  }
+  if ((rc = on_device(c, mem, FSEL, U_WHOLE, batch, &d, "f_pack")) != AVM_OK) return rc;
   FselBuffers w;
   if ((rc = fsel_buffers(c, &d, &w, false)) != AVM_OK) return rc;
   const size_t P = batch->n_problems, N = 9 * ((size_t)batch->horizon + 1), T = 3 * (size_t)batch->horizon, mc = batch->max_cand;
