@@ -1,8 +1,11 @@
-// devmath.hpp — device-side FP64 helpers for the gfx950 kernels (wave = 64 lanes).
+// devmath.hpp — device-side FP64 helpers for the gfx950 kernels (wave = 64 lanes): quaternions and 3 x 3 blocks, then the wave
+// primitives every kernel shares, one definition each - lane exchange (dpp_mov, dpp_d, dpp_keep_d, readlane_d, lane_xor, lane_swap), the
+// wave / block reductions, and wave_lds_sync, sfor, d4, fast_rcp / fast_rsqrt.
 // Quaternion/rotation conventions follow vins_estimator/src/utility/utility.h:12-64 and the
 // Eigen behaviours listed in SURVEY.md Appendix B (storage order in parameter blocks: x,y,z,w).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <utility>
 
 #define AVM_DEV __device__ __forceinline__
 
@@ -123,8 +126,27 @@ AVM_DEV void qleft_qright_br(quat a, quat b, double* M) {
 // of a ladder live across the whole kernel, and in the solve kernels it spills them - every step of a reduction then began with a trip
 // to scratch memory.  The forms below carry the pattern in the instruction (DPP controls, the gfx950 row / half swaps): no address
 // register, no LDS pipe.  All of them are compiler builtins, so the hazard recognizer places the DPP wait states.
-template <int CTRL>
-AVM_DEV int dpp_mov(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+template <int CTRL, int ROW_MASK = 0xf>
+AVM_DEV int dpp_mov(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, true); }
+// A double through one DPP control (two 32-bit moves), bound_ctrl and the full bank mask: a lane without a source, or in a row that
+// ROW_MASK leaves out, gets 0 - what a sum wants, and no "old value" register has to be set up in front of every move.
+template <int CTRL, int ROW_MASK = 0xf>
+AVM_DEV double dpp_d(double v) {
+  return __hiloint2double(dpp_mov<CTRL, ROW_MASK>(__double2hiint(v)), dpp_mov<CTRL, ROW_MASK>(__double2loint(v)));
+}
+// ... the keep-old-value form: such a lane keeps its own v (what a maximum wants: fmax(v, v) = v)
+template <int CTRL, int ROW_MASK = 0xf>
+AVM_DEV double dpp_keep_d(double v) {
+  const int hi = __double2hiint(v), lo = __double2loint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false));
+}
+// one lane's double to the whole wavefront through SGPRs (two v_readlane_b32)
+AVM_DEV double readlane_d(double v, int srclane) {  // srclane must be wave-uniform
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_readlane(lo, srclane);
+  hi = __builtin_amdgcn_readlane(hi, srclane);
+  return __hiloint2double(hi, lo);
+}
 // the value of lane (lane ^ O), O = 1, 2, 4, 8 (inside the 16-lane rows); every lane of the wavefront active
 template <int O>
 AVM_DEV int lane_xor(int v) {
@@ -158,7 +180,8 @@ AVM_DEV dpair lane_swap(double v) {
 }
 
 // ---- wave / block reductions (fixed order => deterministic) ---------------------------
-// the butterfly of a __shfl_xor ladder: partner lane ^ o, o = 32, 16, 8, 4, 2, 1 in that order; the result in every lane
+// Two ladders, two summation orders: which one a kernel uses is part of its bit-exact result.
+// The butterfly of a __shfl_xor ladder: partner lane ^ o, o = 32, 16, 8, 4, 2, 1 in that order; the result in every lane.
 AVM_DEV double wave_sum(double v) {
   dpair p = lane_swap<32>(v);
   v = p.a + p.b;
@@ -170,7 +193,7 @@ AVM_DEV double wave_sum(double v) {
   v += lane_xor<1>(v);
   return v;
 }
-AVM_DEV double wave_max(double v) {
+AVM_DEV double wave_max(double v) {  // the same butterfly; the result in every lane
   dpair p = lane_swap<32>(v);
   v = fmax(p.a, p.b);
   p = lane_swap<16>(v);
@@ -180,6 +203,27 @@ AVM_DEV double wave_max(double v) {
   v = fmax(v, lane_xor<2>(v));
   v = fmax(v, lane_xor<1>(v));
   return v;
+}
+// The shift ladder (prior_eig.hip): lane i takes lane i - 1, - 2, - 4, - 8 of its 16-lane row in that order (lane 15 then holds its row:
+// ((15 + 14) + (13 + 12)) + ... ), then row 0 goes to row 1 and row 2 to row 3, then row 1 to rows 2 and 3; lane 63 holds the wavefront
+// and is read through SGPRs: the result is uniform.  No LDS.
+AVM_DEV double wave_sum_shr(double v) {
+  v += dpp_d<0x111>(v);       // row_shr:1
+  v += dpp_d<0x112>(v);       // row_shr:2
+  v += dpp_d<0x114>(v);       // row_shr:4
+  v += dpp_d<0x118>(v);       // row_shr:8   -> lane 15 of every row holds the row sum
+  v += dpp_d<0x142, 0xa>(v);  // row_bcast:15 -> rows 1 and 3
+  v += dpp_d<0x143, 0xc>(v);  // row_bcast:31 -> rows 2 and 3: lane 63 holds the sum
+  return readlane_d(v, 63);
+}
+AVM_DEV double wave_max_shr(double v) {  // the same ladder (any pairing will do for a maximum); the result uniform
+  v = fmax(v, dpp_keep_d<0x111>(v));
+  v = fmax(v, dpp_keep_d<0x112>(v));
+  v = fmax(v, dpp_keep_d<0x114>(v));
+  v = fmax(v, dpp_keep_d<0x118>(v));
+  v = fmax(v, dpp_keep_d<0x142, 0xa>(v));
+  v = fmax(v, dpp_keep_d<0x143, 0xc>(v));
+  return readlane_d(v, 63);
 }
 // all threads get the result; red must hold >= 32 doubles; contains 2 __syncthreads
 template <int NT>
@@ -205,6 +249,44 @@ AVM_DEV double block_max(double v, double* red) {
 #pragma unroll
   for (int i = 1; i < NT / 64; i++) s = fmax(s, red[i]);
   return s;
+}
+
+// ---- what else every kernel shares: the wave-level LDS fence, the compile-time loop, d4, rcp / rsqrt ----------------------------------
+// a wavefront's own LDS traffic put in order (its stores before the barrier visible to its loads after it); no other wavefront is waited for
+AVM_DEV void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// compile-time loop, f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>): a register tile's index and the lane index of a
+// DPP operand have to be constants (the one is part of the instruction, the other keeps the tile array out of scratch memory)
+template <class F, int... Is>
+AVM_DEV void sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, class F>
+AVM_DEV void sfor(F&& f) {
+  sfor_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+typedef double d4 __attribute__((ext_vector_type(4)));  // the accumulator of v_mfma_f64_16x16x4
+
+// reciprocal / reciprocal square root from the hardware estimate + two Newton steps (about one ulp; the library forms spend
+// two to three times as long on range handling that the operands here - depths, squared norms >= 1 - never need)
+AVM_DEV double fast_rcp(double x) {
+  double y = __builtin_amdgcn_rcp(x), e = fma(-x, y, 1.0);
+  y = fma(y, e, y);
+  e = fma(-x, y, 1.0);
+  return fma(y, e, y);
+}
+// raw v_rsq_f64 + two Newton steps (the library rsqrt spends ~3x as long in range handling we do not need:
+// pivots of an SPD matrix are normal positive numbers)
+AVM_DEV double fast_rsqrt(double x) {
+  double y = __builtin_amdgcn_rsq(x);
+  y = y * (1.5 - (0.5 * x) * y * y);
+  y = y * (1.5 - (0.5 * x) * y * y);
+  return y;
 }
 
 }  // namespace avm

@@ -31,7 +31,7 @@ namespace avm {
 namespace {
 
 #include "fsel/args.hpp"           // FS_NT, FS_CPW, FS_TABLES_GUARD, FselDev: the argument block of every kernel
-#include "fsel/dpp.hpp"            // fs_readlane_d, fs_rowbcast_k, fs_dpp_fence, fs_fmac_bcast, fs_sfor, fs_dpp_d, fs_row_sum, fs_wave_max
+#include "fsel/dpp.hpp"            // fs_rowbcast_k, fs_dpp_fence, fs_fmac_bcast, fs_row_sum, fs_wave_max
 #include "fsel/kdtree.hpp"         // findNNDepth: KdNode, fsel_kdtree_kernel (nanoflann's build), kd_depth (its search, stackless)
 #include "fsel/feature_delta.hpp"  // feature_front, feature_front4, feature_pair, feature_delta: Delta_ell of one feature
 #include "fsel/setup_kernel.hpp"   // slerp_eigen, fsel_setup_kernel: Omega, its partial Cholesky, every feature's Delta

@@ -1,13 +1,6 @@
-// fsel/dpp.hpp - lane exchange inside a wavefront: readlane, DPP broadcasts and the v_fmac_f64_dpp run, compile-time loops, row sum, wave maximum
+// fsel/dpp.hpp - the selector's own lane exchange: the row broadcast and the v_fmac_f64_dpp run with its fence, row sum, wave maximum
+// (written with devmath.hpp's dpp_d / readlane_d / sfor)
 // Part of fsel.hip, which includes it inside namespace avm; no translation unit of its own.
-
-// one lane's double to the whole wavefront through SGPRs
-AVM_DEV double fs_readlane_d(double v, int srclane) {  // srclane must be wave-uniform
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, srclane);
-  hi = __builtin_amdgcn_readlane(hi, srclane);
-  return __hiloint2double(hi, lo);
-}
 
 // FOUR candidates per wavefront: candidate g lives in the 16-lane DPP row g of the wave.  The T x T matrix is cut into NB block
 // rows of BS <= 16 rows (T = 30: 2 x 15, T = 39: 3 x 13); lane r of the row holds row r of EVERY block row in registers
@@ -20,11 +13,7 @@ AVM_DEV double fs_readlane_d(double v, int srclane) {  // srclane must be wave-u
 // logdet = sum_j log(d_j) and the Hadamard bound (sortedlogDetUB) are summed in one fixed association for every candidate, so
 // mirror-image candidates still get bit-identical bounds (the std::map rule of the pick depends on that).
 template <int K>
-AVM_DEV double fs_rowbcast_k(double v) {  // lane K of every 16-lane row -> the whole row (row_newbcast:K = dpp_ctrl 0x150 + K)
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x150 + K, 0xf, 0xf, true);
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x150 + K, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
+AVM_DEV double fs_rowbcast_k(double v) { return dpp_d<0x150 + K>(v); }  // lane K of every 16-lane row -> the whole row (row_newbcast:K = dpp_ctrl 0x150 + K)
 
 // acc += (lane k of src's 16-lane row) * nmul in ONE instruction: v_fmac_f64_dpp with row_newbcast (the FP64 ALU of gfx90a+ takes a DPP operand
 // of that one kind).  Round 6, scripts/ubench/dpp2.hip: 5.8 cycles an issue against 4.8 for a plain v_fmac_f64.  (The pre-round-6 form - two 32-bit
@@ -40,48 +29,32 @@ template <int K>
 AVM_DEV void fs_fmac_bcast(double& acc, double src, double nmul) {
   asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(nmul), "n"(K));
 }
-// compile-time loops (the lane index of a DPP operand is part of the instruction)
-template <class F, int... Is>
-AVM_DEV void fs_sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-AVM_DEV void fs_sfor(F&& f) {
-  fs_sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// a double through one DPP control (two 32-bit moves): what the ladders below and the kd-tree's (kdtree.hpp) exchange with
-template <int CTRL>
-AVM_DEV double fs_dpp_d(double v) {
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
 // Sum over the 16 lanes of a DPP row, in every lane of the row: the same four exchange steps as fs_wave_max (a fixed
-// association, the same for every candidate - mirror-image candidates keep bit-identical Hadamard bounds).
+// association, the same for every candidate - mirror-image candidates keep bit-identical Hadamard bounds): pairs, quads, the two
+// quads of a half (mirrored), the two halves (mirrored).
 AVM_DEV double fs_row_sum(double v) {
-  v += fs_dpp_d<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += fs_dpp_d<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += fs_dpp_d<0x141>(v);  // row_half_mirror
-  v += fs_dpp_d<0x140>(v);  // row_mirror
+  v += dpp_d<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_d<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_d<0x141>(v);  // row_half_mirror
+  v += dpp_d<0x140>(v);  // row_mirror
   return v;
 }
 // Maximum over the wavefront, in every lane: four DPP exchange steps inside the 16-lane rows (lane ^ 1, lane ^ 2, mirror of 8,
-// mirror of 16 - any pairing of already-reduced groups will do for a maximum), then the four row results through SGPRs.
+// mirror of 16 - any pairing of already-reduced groups will do for a maximum), then the four row results through SGPRs: uniform.
 // (__shfl_xor is a ds_bpermute per 32 bits and step: the lexicographic argmax of the pick took 30 of them, 2 K cycles.)
 AVM_DEV double fs_wave_max(double v) {
-  v = fmax(v, fs_dpp_d<0xB1>(v));   // quad_perm [1,0,3,2]
-  v = fmax(v, fs_dpp_d<0x4E>(v));   // quad_perm [2,3,0,1]
-  v = fmax(v, fs_dpp_d<0x141>(v));  // row_half_mirror
-  v = fmax(v, fs_dpp_d<0x140>(v));  // row_mirror
-  const double r0 = fs_readlane_d(v, 0), r1 = fs_readlane_d(v, 16), r2 = fs_readlane_d(v, 32), r3 = fs_readlane_d(v, 48);
+  v = fmax(v, dpp_d<0xB1>(v));   // quad_perm [1,0,3,2]
+  v = fmax(v, dpp_d<0x4E>(v));   // quad_perm [2,3,0,1]
+  v = fmax(v, dpp_d<0x141>(v));  // row_half_mirror
+  v = fmax(v, dpp_d<0x140>(v));  // row_mirror
+  const double r0 = readlane_d(v, 0), r1 = readlane_d(v, 16), r2 = readlane_d(v, 32), r3 = readlane_d(v, 48);
   return fmax(fmax(r0, r1), fmax(r2, r3));
 }
 AVM_DEV int fs_wave_max(int v) {
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true));
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true));
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true));
-  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true));
+  v = max(v, dpp_mov<0xB1>(v));
+  v = max(v, dpp_mov<0x4E>(v));
+  v = max(v, dpp_mov<0x141>(v));
+  v = max(v, dpp_mov<0x140>(v));
   return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }

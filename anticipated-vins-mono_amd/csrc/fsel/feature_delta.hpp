@@ -125,9 +125,7 @@ AVM_DEV bool feature_front4(const avm_fsel_batch& b, const double* kd, int p, co
   }
   const unsigned long long bal = __ballot(vis);
   const bool ok = have && ((bal >> (lane & 48)) & 0xffffull) != 0;  // numVisible > 1
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   // E in feature_front's order: frames 2 .. H as the loop met them (an invisible frame adds an exact zero), then frame 1
   double E[6];
 #pragma unroll

@@ -28,17 +28,17 @@ constexpr int KD_HDR = 8;  // doubles: root box low0 high0 low1 high1 | n_nodes,
 __host__ __device__ constexpr size_t kd_stride(int max_cloud) { return KD_HDR + (size_t)11 * max_cloud; }  // header | 2 mc nodes (4 doubles each) | xy[mc][2] | depth[mc], in tree order
 constexpr int KD_MAXW = 64;  // path words of 64 levels each beyond the first (a tree of n points is at most n - 10 deep)
 
-// minimum / maximum over the wavefront, the result in every lane: four DPP exchange steps inside the 16-lane rows (fs_dpp_d, dpp.hpp: two
+// minimum / maximum over the wavefront, the result in every lane: four DPP exchange steps inside the 16-lane rows (dpp_d, devmath.hpp: two
 // 32-bit moves each), then the four row results through SGPRs - a __shfl_xor ladder is twelve dependent ds_bpermute per double (1.5 K
 // cycles; the tree of a 150-point cloud takes ~90 of these reductions).  kd_wave_max is fs_wave_max's ladder, but reads each pair of row
 // results right before it compares them; written either way for both users, the compiler schedules one of them differently.
 AVM_DEV double kd_wave_min(double v) {
-  v = fmin(v, fs_dpp_d<0xB1>(v)), v = fmin(v, fs_dpp_d<0x4E>(v)), v = fmin(v, fs_dpp_d<0x141>(v)), v = fmin(v, fs_dpp_d<0x140>(v));
-  return fmin(fmin(fs_readlane_d(v, 0), fs_readlane_d(v, 16)), fmin(fs_readlane_d(v, 32), fs_readlane_d(v, 48)));
+  v = fmin(v, dpp_d<0xB1>(v)), v = fmin(v, dpp_d<0x4E>(v)), v = fmin(v, dpp_d<0x141>(v)), v = fmin(v, dpp_d<0x140>(v));
+  return fmin(fmin(readlane_d(v, 0), readlane_d(v, 16)), fmin(readlane_d(v, 32), readlane_d(v, 48)));
 }
 AVM_DEV double kd_wave_max(double v) {
-  v = fmax(v, fs_dpp_d<0xB1>(v)), v = fmax(v, fs_dpp_d<0x4E>(v)), v = fmax(v, fs_dpp_d<0x141>(v)), v = fmax(v, fs_dpp_d<0x140>(v));
-  return fmax(fmax(fs_readlane_d(v, 0), fs_readlane_d(v, 16)), fmax(fs_readlane_d(v, 32), fs_readlane_d(v, 48)));
+  v = fmax(v, dpp_d<0xB1>(v)), v = fmax(v, dpp_d<0x4E>(v)), v = fmax(v, dpp_d<0x141>(v)), v = fmax(v, dpp_d<0x140>(v));
+  return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
 }
 
 // initKDTree (feature_selector.cpp:380-432, the buildIndex part): one wavefront per frame.  LDS: x[mc] y[mc] (doubles), vind[mc], two
@@ -73,14 +73,7 @@ __global__ __launch_bounds__(64) void fsel_kdtree_kernel(FselDev A) {
     lo0 = fmin(lo0, x), hi0 = fmax(hi0, x), lo1 = fmin(lo1, y), hi1 = fmax(hi1, y);
   }
   lo0 = kd_wave_min(lo0), hi0 = kd_wave_max(hi0), lo1 = kd_wave_min(lo1), hi1 = kd_wave_max(hi1);  // computeBoundingBox
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  auto sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
+  wave_lds_sync();
   auto coord = [&](int pos, int dim) { return dim == 0 ? X[vi[pos]] : Y[vi[pos]]; };
   // min / max of one coordinate over the index range [l, r)
   auto minmax = [&](int l, int r, int dim, double& mn, double& mx) {
@@ -110,14 +103,14 @@ __global__ __launch_bounds__(64) void fsel_kdtree_kernel(FselDev A) {
       if (mr) lmr[nmr + __popcll(br & lt)] = q;
       nml += __popcll(bl), nmr += __popcll(br);
     }
-    sync();
+    wave_lds_sync();
     // Hoare's swaps: the i-th misplaced index from the left with the i-th from the right (nml == nmr)
     for (int i = lane; i < nml; i += 64) {
       const int qa = l + lml[i], qb = l + lmr[nml - 1 - i];
       const int t = vi[qa];
       vi[qa] = vi[qb], vi[qb] = t;
     }
-    sync();
+    wave_lds_sync();
     return nl;
   };
   int nn = 1, sp = 0, maxdepth = 0;
@@ -178,7 +171,7 @@ __global__ __launch_bounds__(64) void fsel_kdtree_kernel(FselDev A) {
       e.bb[left_now ? 2 * cutfeat : 2 * cutfeat + 1] = cutval;
     }
     sp++;
-    sync();
+    wave_lds_sync();
     if (left_now) r = l + idx, bb[2 * cutfeat + 1] = cutval, slot = c1;
     else l = l + idx, bb[2 * cutfeat] = cutval, slot = c2;
     depth++;

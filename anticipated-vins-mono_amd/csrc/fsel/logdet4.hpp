@@ -13,10 +13,7 @@ AVM_DEV double fs_log(double x) {
   m = lo ? m + m : m;
   k = lo ? k - 1 : k;
   const double f = m - 1.0, d = 2.0 + f;
-  double r = __builtin_amdgcn_rcp(d), e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
+  const double r = fast_rcp(d);
   double sq = f * r;
   sq = fma(fma(-d, sq, f), r, sq);                  // s = f / (2 + f)
   const double z = sq * sq, w = z * z;
@@ -100,10 +97,10 @@ AVM_DEV bool fsel_logdet4(const double* sC, const double* sdpp, const double* D,
   bool bad = false;
   // m[bi][gk] += A[gk][gj] * (-mult[bi]) with A[gk][gj] = lane k of m[bk][gj], taken by the multiply-add itself (fs_fmac_bcast): one instruction per
   // (pivot, column, block row) where it was two 32-bit DPP moves per (pivot, column) and a multiply-add per block row - the same product, the same rounding
-  fs_sfor<NB>([&](auto BJ) {
+  sfor<NB>([&](auto BJ) {
     constexpr int bj = BJ;
     dkeep[bj] = 1.0;
-    fs_sfor<BS>([&](auto J) {
+    sfor<BS>([&](auto J) {
       constexpr int j = J, gj = bj * BS + j;
       const double djj = fs_rowbcast_k<j>(m[bj][gj]);
       if (!(djj > 0.0)) bad = true;
@@ -116,11 +113,11 @@ AVM_DEV bool fsel_logdet4(const double* sC, const double* sdpp, const double* D,
 #pragma unroll
       for (int bi = bj; bi < NB; bi++) nmult[bi] = -(m[bi][gj] * y);
       fs_dpp_fence();
-      fs_sfor<NB - bj>([&](auto BKK) {
+      sfor<NB - bj>([&](auto BKK) {
         constexpr int bk = bj + BKK, k0 = bk == bj ? j + 1 : 0;
-        fs_sfor<BS - k0>([&](auto KK) {
+        sfor<BS - k0>([&](auto KK) {
           constexpr int k = k0 + KK, gk = bk * BS + k;
-          fs_sfor<NB - bk>([&](auto BII) {
+          sfor<NB - bk>([&](auto BII) {
             constexpr int bi = bk + BII;
             fs_fmac_bcast<k>(m[bi][gk], m[bk][gj], nmult[bi]);
           });

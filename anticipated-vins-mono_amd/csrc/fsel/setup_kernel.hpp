@@ -130,9 +130,7 @@ __global__ __launch_bounds__(FS_NT) void fsel_setup_kernel(FselDev A, int slice_
     if (k0 >= b.n_cand[p]) return;  // (wave-uniform)
     const int ku = k0 + (lane >> 4);
     const bool oku = feature_front4(b, A.kd, p, cam, ku, ku < b.n_cand[p], H, wl0 + (lane >> 4) * WS);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     for (int u = 0; u < FS_CPW; u++) {
       const int k = k0 + u;
       if (k >= b.n_cand[p]) break;  // (wave-uniform)
@@ -147,9 +145,7 @@ __global__ __launch_bounds__(FS_NT) void fsel_setup_kernel(FselDev A, int slice_
           while (rem >= H - j + 1) rem -= H - j + 1, j++;
           feature_pair(wl, wl + 6 * H, j + rem, j, T, tile);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         for (int idx = lane; idx < T * T; idx += 64) out[idx] = tile[idx];
         if (A.delta_pk) {  // ... and the lower triangle by columns, for the solo form
           double* opk = A.delta_pk + ((size_t)p * b.max_cand + k) * (T * (T + 1) / 2);

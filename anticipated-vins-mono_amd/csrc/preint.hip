@@ -25,9 +25,7 @@ constexpr int PG = 4;  // intervals per wavefront
 
 // every wavefront works on its own intervals: only wave-level ordering of its LDS traffic is needed
 AVM_DEV void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   __builtin_amdgcn_sched_barrier(0);  // keep the phases of a sample from being interleaved (register pressure)
 }
 
@@ -41,14 +39,6 @@ struct PreLds {
   double Vi[9 * VS];  // rows p, theta, v of V, noise columns 0..11 (the reference's order); the rows ba, bg are zero there
   double m[72];       // Rd, Rr, Ra0, Ra1, IRw (I - Rw*dt), T1=Rd*Ra0, T2=Rr*Ra1, T3=T2*IRw
 };
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-AVM_DEV double readlane_f64(double v, int srclane) {  // srclane must be wave-uniform
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, srclane);
-  hi = __builtin_amdgcn_readlane(hi, srclane);
-  return __hiloint2double(hi, lo);
-}
 }  // namespace
 
 // The 15 x 15 state matrices never leave registers: with v_mfma_f64_16x16x4 the accumulator layout
@@ -209,7 +199,7 @@ __global__ __launch_bounds__(64 * PW) void preint_kernel(PreintArgs a) {
     for (int g = 0; g < PG; g++) {
       if (s >= nsg[g]) continue;  // (wave-uniform)
       const PreLds& G = Lw[g];
-      const double dtg = readlane_f64(dt, 16 * g);
+      const double dtg = readlane_d(dt, 16 * g);
       double fa[3], va[3];
 #pragma unroll
       for (int m = 0; m < 3; m++) fa[m] = G.Fi[lic * FS + lk + 4 * m];

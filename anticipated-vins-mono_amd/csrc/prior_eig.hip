@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include "devmath.hpp"
 #include "kernels.hpp"
 
 namespace avm {
@@ -56,63 +57,11 @@ constexpr int P_D0 = P_PIV + NMAX / 2 + 4;     // the diagonal of A' as it came 
 constexpr int P_END = P_D0 + NMAX;
 static_assert(3 * P_END * 8 <= 163840, "three workgroups per CU");
 
-__device__ __forceinline__ double nrm_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  return y;
-}
-
 // Wavefront shifts with bound_ctrl: a lane without a source gets 0 - exactly what the column exchange wants (the lanes
 // beyond the last pair hold zero columns), and no "old value" register has to be set up in front of every DPP move.
-// lane i <- lane i+1 (the last lane gets 0)
-__device__ __forceinline__ double shl_d(double v) {
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-// lane i <- lane i-1 (lane 0 gets 0)
-__device__ __forceinline__ double shr_d(double v) {
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
-// max over the wavefront of a non-negative double, result uniform (DPP row shifts + row broadcasts, no LDS)
-__device__ __forceinline__ double wave_max_pos(double v) {
-#define AVM_DPP_MAX(ctrl, rmask)                                                                               \
-  {                                                                                                            \
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), ctrl, rmask, 0xf, false); \
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), ctrl, rmask, 0xf, false); \
-    v = fmax(v, __hiloint2double(hi, lo));                                                                     \
-  }
-  AVM_DPP_MAX(0x111, 0xf)  // row_shr:1
-  AVM_DPP_MAX(0x112, 0xf)  // row_shr:2
-  AVM_DPP_MAX(0x114, 0xf)  // row_shr:4
-  AVM_DPP_MAX(0x118, 0xf)  // row_shr:8   -> lane 15 of every row holds the row maximum
-  AVM_DPP_MAX(0x142, 0xa)  // row_bcast:15 -> rows 1 and 3
-  AVM_DPP_MAX(0x143, 0xc)  // row_bcast:31 -> rows 2 and 3: lane 63 holds the maximum
-#undef AVM_DPP_MAX
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-
-// sum over the wavefront, result uniform (same DPP ladder as wave_max_pos; the order of the additions is fixed)
-__device__ __forceinline__ double wave_sum(double v) {
-#define AVM_DPP_ADD(ctrl, rmask)                                                                \
-  {                                                                                             \
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, rmask, 0xf, true);   \
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rmask, 0xf, true);   \
-    v += __hiloint2double(hi, lo);                                                              \
-  }
-  AVM_DPP_ADD(0x111, 0xf)
-  AVM_DPP_ADD(0x112, 0xf)
-  AVM_DPP_ADD(0x114, 0xf)
-  AVM_DPP_ADD(0x118, 0xf)
-  AVM_DPP_ADD(0x142, 0xa)
-  AVM_DPP_ADD(0x143, 0xc)
-#undef AVM_DPP_ADD
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
+AVM_DEV double shl_d(double v) { return dpp_d<0x130>(v); }  // wave_shl:1, lane i <- lane i+1 (the last lane gets 0)
+AVM_DEV double shr_d(double v) { return dpp_d<0x138>(v); }  // wave_shr:1, lane i <- lane i-1 (lane 0 gets 0)
+// (the reductions of both kernels are devmath.hpp's shift ladder, wave_sum_shr / wave_max_shr: result uniform, no LDS)
 
 // ---- the well-conditioned case on ONE wavefront (round 3) ------------------------------------------------------------------------
 // Most windows of a run - every window whose prior already pins all its directions - leave an A' that is positive definite with
@@ -149,16 +98,7 @@ constexpr int PC_S = 17, PC_B = 16 * PC_S;                // row stride / size o
                                                           // SQ_LDS_BANK_CONFLICT was 11 cycles per LDS instruction of this kernel)
 constexpr int PC_LDS = PC_B + PC_T * PC_B + 6 * 80 + PC_B; // doubles: the diagonal patch | L_kk^-1 of every block | b', y, s, a 16-vector, a column of J, the pivots' thresholds | a 16 x 16 identity
 constexpr int PC_MAXDEL = 8;                            // deleted pivots per window
-typedef double pd4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ constexpr int pc_ti(int k, int i) { return k * PC_T - k * (k - 1) / 2 + (i - k); }
-__device__ __forceinline__ double pc_readlane(double v, int src) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-__device__ __forceinline__ void pc_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // what counts as zero for entry (i, j) of A' given the magnitudes s_i, s_j its two diagonal entries were formed at: 4000 unit roundoffs of
 // sqrt(s_i s_j) - plain formation noise - or, for the small magnitudes, 1e-7 (s_i s_j)^1/4: the level the eigen path's own noise test
 // works at (it drops S when S^2 <= 1e-16 g^T diag(s) g, i.e. S <= 1e-8 sqrt(s) for a coordinate direction; a factor 10 on top because
@@ -200,7 +140,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
   double* vthr = vc + 80;               // pc_zero(s_j, s_j): what counts as a zero pivot (three square roots each: once per window, not once per block)
   double* ident = vthr + 80;            // [16][16] identity: the rows the lanes 16..31 of the pivot chain start from
   // ---- load: upper tiles (A' is symmetric and stored as its lower triangle), identity on the pad
-  pd4 U[PC_NT];
+  d4 U[PC_NT];
   {
     // (entry (row, col) of an upper tile lies at [col][row] of the stored lower triangle; off the diagonal tiles row < col also after
     //  the clamp to n - 1, so one product per tile column and one add per entry address it: written with max / min of the two clamped
@@ -254,7 +194,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
 #pragma unroll
     for (int q = 0; q < 4; q++) ident[((lane + 64 * q) >> 4) * PC_S + ((lane + 64 * q) & 15)] = ((lane + 64 * q) >> 4) == ((lane + 64 * q) & 15) ? 1.0 : 0.0;
   }
-  pc_sync();
+  wave_lds_sync();
   bool bad = false;
   unsigned long long dm0 = 0, dm1 = 0;  // the deleted pivots, a bit each (wave-uniform; no branch inside the pivot chain)
   // ---- factorization
@@ -262,7 +202,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
   for (int k = 0; k < PC_T; k++) {
 #pragma unroll
     for (int r = 0; r < 4; r++) blk[(lk + 4 * r) * PC_S + lr] = U[pc_ti(k, k)][r];
-    pc_sync();
+    wave_lds_sync();
     {
       // lane = row (lanes 0..15), lanes 16..31: the rows of the identity (they end as the rows of L_kk^-T); the others carry junk
       // (lanes 32..63 repeat lanes 0..31 - same loads, same arithmetic, same stores -, so that no store below is conditional)
@@ -274,14 +214,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
       const double thr_l = vthr[16 * k + lr];  // (off the pivot chain: lane j holds pivot j's threshold)
 #pragma unroll
       for (int j = 0; j < 16; j++) {
-        const double pj = pc_readlane(a[j], j);
-        const double thr = pc_readlane(thr_l, j);
+        const double pj = readlane_d(a[j], j);
+        const double thr = readlane_d(thr_l, j);
         const bool del = fabs(pj) <= thr;  // zero up to formation noise: the direction is dropped (pads: s = 0, pivot 1)
-        a[j] *= del ? 0.0 : nrm_rsqrt(pj);
+        a[j] *= del ? 0.0 : fast_rsqrt(pj);
 #pragma unroll
-        for (int c = j + 1; c < 16; c++) a[c] = fma(-a[j], pc_readlane(a[j], c), a[c]);
+        for (int c = j + 1; c < 16; c++) a[c] = fma(-a[j], readlane_d(a[j], c), a[c]);
       }
-      pc_sync();  // (every lane has read its row of the patch)
+      wave_lds_sync();  // (every lane has read its row of the patch)
       // Row lr of L_kk goes back into the patch as COLUMN lr (the patch then holds L_kk^T = J_kk), row i of L_kk^-T (lane 16 + i) as column
       // i of L_kk^-1: both with stride 16, sixteen unconditional stores at constant offsets.  The entries c > lr of a matrix lane are
       // leftovers of the elimination, masked where the patch is read; those c < i of an identity lane are exact zeros already.
@@ -289,7 +229,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
 #pragma unroll
       for (int c = 0; c < 16; c++) dst[c * PC_S] = a[c];
     }
-    pc_sync();
+    wave_lds_sync();
     {
       // What became of the sixteen pivots, read off L_kk's diagonal (in the chain this bookkeeping was twelve scalar instructions per pivot
       // on values the compiler then kept in spilled SGPRs: 2 K of the kernel's 12.8 K instructions): a deleted pivot left an exact zero
@@ -309,7 +249,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
       for (int r = 0; r < 4; r++) ao[r] = Linv[k * PC_B + lr * PC_S + lk + 4 * r];
 #pragma unroll
       for (int i = k + 1; i < PC_T; i++) {
-        pd4 W = {0, 0, 0, 0};
+        d4 W = {0, 0, 0, 0};
 #pragma unroll
         for (int r = 0; r < 4; r++) W = __builtin_amdgcn_mfma_f64_16x16x4f64(ao[r], U[pc_ti(k, i)][r], W, 0, 0, 0);
         U[pc_ti(k, i)] = W;  // = L_ik^T = block (k, i) of J
@@ -322,7 +262,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
           for (int r = 0; r < 4; r++)
             U[pc_ti(j, i)] = __builtin_amdgcn_mfma_f64_16x16x4f64(-U[pc_ti(k, j)][r], U[pc_ti(k, i)][r], U[pc_ti(j, i)], 0, 0, 0);
     }
-    pc_sync();  // (the patch is rewritten by the next block column)
+    wave_lds_sync();  // (the patch is rewritten by the next block column)
   }
   // ---- y = L^-1 b' by blocks: v_k = b_k - sum_{i < k} L_ki y_i with L_ki = (J block (i, k))^T, then y_k = L_kk^-1 v_k
 #pragma unroll
@@ -335,18 +275,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
     p += __shfl_xor(p, 16, 64);
     p += __shfl_xor(p, 32, 64);
     if (lk == 0) vt[lr] = vb[16 * k + lr] - p;
-    pc_sync();
+    wave_lds_sync();
     double acc = 0.0;
 #pragma unroll
     for (int q = 0; q < 16; q++) acc = fma(Linv[k * PC_B + lr * PC_S + q], vt[q], acc);
     if (lk == 0) vy[16 * k + lr] = acc;
-    pc_sync();
+    wave_lds_sync();
   }
   // ---- |L^-1|_F^2 and |L^-1 diag(s)^1/2|_F^2 from the explicit inverse, one column block at a time
   double f2 = 0.0, fs2 = 0.0;
 #pragma unroll
   for (int kk = 0; kk < PC_T; kk++) {
-    pd4 X[PC_T];  // X[i] = (L^-1) block (i, kk), i >= kk
+    d4 X[PC_T];  // X[i] = (L^-1) block (i, kk), i >= kk
     const double sc = vs[16 * kk + lr];
     const bool cin = 16 * kk + lr < n;
 #pragma unroll
@@ -357,12 +297,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
     }
 #pragma unroll
     for (int i = kk + 1; i < PC_T; i++) {
-      pd4 Sacc = {0, 0, 0, 0};
+      d4 Sacc = {0, 0, 0, 0};
 #pragma unroll
       for (int j = kk; j < i; j++)
 #pragma unroll
         for (int r = 0; r < 4; r++) Sacc = __builtin_amdgcn_mfma_f64_16x16x4f64(U[pc_ti(j, i)][r], X[j][r], Sacc, 0, 0, 0);  // L_ij X_j
-      pd4 Xi = {0, 0, 0, 0};
+      d4 Xi = {0, 0, 0, 0};
 #pragma unroll
       for (int r = 0; r < 4; r++) Xi = __builtin_amdgcn_mfma_f64_16x16x4f64(-Linv[i * PC_B + lr * PC_S + lk + 4 * r], Sacc[r], Xi, 0, 0, 0);
       X[i] = Xi;
@@ -373,7 +313,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
       }
     }
   }
-  f2 = wave_sum(f2), fs2 = wave_sum(fs2);
+  f2 = wave_sum_shr(f2), fs2 = wave_sum_shr(fs2);
   const int ndel = __popcll(dm0) + __popcll(dm1);
   // (the noise test is certified at PC_CERT_NOISE, not at noise_rel: see pc_cert_noise)
   bool ok = !__any(bad) && ndel <= PC_MAXDEL && f2 * (1000.0 * eps) < 1.0 && fs2 * (4.0 * pc_cert_noise(noise_rel)) < 1.0;  // (NaN compares false)
@@ -387,7 +327,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
     const int kd = d >> 4, cd = d & 15;
     // column d of J into LDS: J[row][d], rows < d (row d itself is zero, the rows below are below the diagonal)
     for (int c = lane; c < 80; c += 64) vc[c] = 0.0;
-    pc_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int k = 0; k < PC_T; k++)
       if (k <= kd && lr == cd) {
@@ -398,7 +338,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
             for (int r = 0; r < 4; r++) vc[16 * k + lk + 4 * r] = U[pc_ti(k, i)][r];
           }
       }
-    pc_sync();
+    wave_lds_sync();
     const double sd = vs[d];
     bool viol = false;
 #pragma unroll
@@ -417,7 +357,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AVM_PC_WAVES
       }
     }
     ok = ok && !__any(viol);
-    pc_sync();
+    wave_lds_sync();
   }
   if (!ok) return;
   // ---- the prior: linearized_jacobians = J = L^T (upper triangular), linearized_residuals = y
@@ -503,13 +443,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
       if (col1 < NMAX && !((done_hi >> lane) & 1ull) && v1 > 0.0)
         key = fmax(key, __longlong_as_double((__double_as_longlong(v1) & ~0x7fll) | (long long)(127 - col1)));
     }
-    key = wave_max_pos(key);
+    key = wave_max_shr(key);
     if (!(key > 0.0)) break;
     const int p = 127 - (int)(__double_as_longlong(key) & 0x7fll);
     const double bv = dgl[p];
     if (j == 0) dmax0 = bv;
     if (!(bv > (double)NMAX * 2.3e-16 * dmax0)) break;  // rank reached (uniform: every lane has the same pivot)
-    const double isq = nrm_rsqrt(bv);
+    const double isq = fast_rsqrt(bv);
     double* g = A + p * LD;
     if (wv == (p & (NW - 1))) {  // the wavefront that owns row p publishes g = row p / sqrt(pivot), 0 on eliminated columns
       const int qp = p >> 2;
@@ -584,7 +524,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         for (int j = 0; j < nr; j++) {
           const int pj = piv[j];
           const double a0 = i0 < j ? A[pi0 * LD + pj] : 0.0, a1 = i1 < j ? A[pi1 * LD + pj] : 0.0;
-          const double sacc = wv == 0 ? wave_sum(a0 * y0 + a1 * y1) : wave_sum(fabs(a0) * y0 + fabs(a1) * y1);
+          const double sacc = wv == 0 ? wave_sum_shr(a0 * y0 + a1 * y1) : wave_sum_shr(fabs(a0) * y0 + fabs(a1) * y1);
           const double d = A[pj * LD + pj];
           const double rhs = wv == 1 ? 1.0 : sqrt(lds[P_D0 + pj]);
           const double yj = wv == 0 ? (lds[P_B + pj] - sacc) / d : (rhs + sacc) / fabs(d);
@@ -594,7 +534,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
           if (i0 < n) gr[i0] = y0;  // (zero beyond the rank: the rows of J there are zero)
           if (i1 < n) gr[i1] = y1;
         } else {
-          const double m = wave_max_pos(fmax(i0 < nr ? y0 : 0.0, i1 < nr ? y1 : 0.0));
+          const double m = wave_max_shr(fmax(i0 < nr ? y0 : 0.0, i1 < nr ? y1 : 0.0));
           if (lane == 0) verdict[wv == 1 ? 0 : 2] = m;
         }
       } else {
@@ -602,13 +542,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         for (int j = nr - 1; j >= 0; j--) {
           const int pj = piv[j];
           const double a0 = (i0 > j && i0 < nr) ? fabs(A[pj * LD + pi0]) : 0.0, a1 = (i1 > j && i1 < nr) ? fabs(A[pj * LD + pi1]) : 0.0;
-          const double sacc = wave_sum(a0 * y0 + a1 * y1);
+          const double sacc = wave_sum_shr(a0 * y0 + a1 * y1);
           const double yj = (1.0 + sacc) / fabs(A[pj * LD + pj]);
           y0 = i0 == j ? yj : y0, y1 = i1 == j ? yj : y1;
         }
-        const double m = wave_max_pos(fmax(i0 < nr ? y0 : 0.0, i1 < nr ? y1 : 0.0));  // >= |L11^-T|_inf = |L11^-1|_1
+        const double m = wave_max_shr(fmax(i0 < nr ? y0 : 0.0, i1 < nr ? y1 : 0.0));  // >= |L11^-T|_inf = |L11^-1|_1
         // (the transposed solve of the row-scaled factor is this one with its solution weighted by sqrt(s_p))
-        const double ms = wave_max_pos(fmax(i0 < nr ? y0 * sqrt(lds[P_D0 + pi0]) : 0.0, i1 < nr ? y1 * sqrt(lds[P_D0 + pi1]) : 0.0));
+        const double ms = wave_max_shr(fmax(i0 < nr ? y0 * sqrt(lds[P_D0 + pi0]) : 0.0, i1 < nr ? y1 * sqrt(lds[P_D0 + pi1]) : 0.0));
         if (lane == 0) verdict[1] = m, verdict[3] = ms;
       }
     }
@@ -681,7 +621,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
       const double d = nH - nL;
       const double h = __builtin_amdgcn_sqrt(d * d + 4.0 * g * g);
       const double tt = (d >= 0 ? 2.0 : -2.0) * g * __builtin_amdgcn_rcp(fabs(d) + h);  // tan of the rotation angle
-      cs = nrm_rsqrt(1.0 + tt * tt);
+      cs = fast_rsqrt(1.0 + tt * tt);
       sn = tt * cs;
       nl = nH + tt * g, nh = nL - tt * g;
       rotated = true;

@@ -75,30 +75,14 @@ AVM_DEV void tp_diag_chain(int nb, int patch, int buf, int stamp) {
 #endif
 }
 
-// sum over the 16 lanes of a DPP row; the result is valid in lane 15 of every row (row_shr with bound_ctrl: a lane without a source adds 0)
+// Sum over the 16 lanes of a DPP row: lane i adds lane i - 1, - 2, - 4, - 8 in that order; the result is valid in lane 15 of every row
+// (row_shr with bound_ctrl: a lane without a source adds 0).  wave_sum_shr's (devmath.hpp) first four steps.
 AVM_DEV double tp_row_sum(double v) {
-#define AVM_DPP_ADD(ctrl)                                                                      \
-  {                                                                                            \
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xf, 0xf, true);    \
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xf, 0xf, true);    \
-    v += __hiloint2double(hi, lo);                                                             \
-  }
-  AVM_DPP_ADD(0x111)
-  AVM_DPP_ADD(0x112)
-  AVM_DPP_ADD(0x114)
-  AVM_DPP_ADD(0x118)
-#undef AVM_DPP_ADD
+  v += dpp_d<0x111>(v);
+  v += dpp_d<0x112>(v);
+  v += dpp_d<0x114>(v);
+  v += dpp_d<0x118>(v);
   return v;
-}
-
-// compile-time loops: every tile index below has to be a constant, or the tile array would live in scratch memory
-template <class F, int... Is>
-AVM_DEV void tp_sfor_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-AVM_DEV void tp_sfor(F&& f) {
-  tp_sfor_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 // Factor the assembled system and solve it: (H' + mu D^2) y = g', y -> lds[L_Y .. L_Y + NF).  Returns false on a non-positive pivot
@@ -129,10 +113,10 @@ AVM_NOINL bool chol_regs() {
   // per tile before the next: 13 trips to the L2 in a row), then the entries.
   typedef unsigned short us4 __attribute__((ext_vector_type(4)));
   us4 off[NTL];
-  tp_sfor<TPT>([&](auto I) {
+  sfor<TPT>([&](auto I) {
     constexpr int i = I;
     if constexpr (tp_owner(i) == WV) {
-      tp_sfor<i + 1>([&](auto K) {
+      sfor<i + 1>([&](auto K) {
         constexpr int k = K;
         if constexpr (tp_nz(k, i) && TPP.h[k][i])
           off[TPI(k, i)] = *reinterpret_cast<const __attribute__((address_space(1))) us4*>(
@@ -141,10 +125,10 @@ AVM_NOINL bool chol_regs() {
     }
   });
   __builtin_amdgcn_sched_barrier(0);
-  tp_sfor<TPT>([&](auto I) {
+  sfor<TPT>([&](auto I) {
     constexpr int i = I;
     if constexpr (tp_owner(i) == WV) {
-      tp_sfor<i + 1>([&](auto K) {
+      sfor<i + 1>([&](auto K) {
         constexpr int k = K;
         if constexpr (tp_nz(k, i)) {
           d4& t = T[TPI(k, i)];
@@ -187,12 +171,12 @@ AVM_NOINL bool chol_regs() {
     for (int r = 0; r < 4; r++) D[r] = lds[L_PATCH + tp_slot_of(k) * (16 * TP_PS) + lr * TP_PS + lk + 4 * r];
     CPROF(0);
   };
-  tp_sfor<2>([&](auto A) {
+  sfor<2>([&](auto A) {
     constexpr int k = tp_step_piv(0, A);
     if constexpr (tp_owner(k) == WV) run_chain(std::integral_constant<int, k>{});
   });
   bool failed = false;
-  tp_sfor<TP_NSTEP>([&](auto TT) {
+  sfor<TP_NSTEP>([&](auto TT) {
     constexpr int t = TT;
     if (failed) return;  // (uniform)
     CPROF(4);
@@ -208,7 +192,7 @@ AVM_NOINL bool chol_regs() {
       }
     }
     // (c) W(k, i) = L_kk^-1 U(k, i) for this wavefront's columns i > k: the final factor tiles, published for the others' updates
-    tp_sfor<tp_step_np(t)>([&](auto A) {
+    sfor<tp_step_np(t)>([&](auto A) {
       constexpr int k = tp_step_piv(t, A);
       constexpr int nb = k == TPT - 1 ? TP_NBL : 16;
       if constexpr (tp_row_held(WV, k) || (k == TPT - 1 && tp_owner(k) == WV)) {
@@ -231,7 +215,7 @@ AVM_NOINL bool chol_regs() {
           for (int r = 0; r < 4; r++)
             if (lr == TP_NBL && lk + 4 * r < TP_NBL) lds[L_ZV + 16 * k + lk + 4 * r] = (Za[r] + Zb[r]) * isq4[r];
         }
-        tp_sfor<TPT - 1 - k>([&](auto II) {
+        sfor<TPT - 1 - k>([&](auto II) {
           constexpr int i = k + 1 + II;
           if constexpr (tp_owner(i) == WV && tp_nz(k, i)) {
             d4& U = T[TPI(k, i)];
@@ -257,11 +241,11 @@ AVM_NOINL bool chol_regs() {
     if constexpr (t < TP_NSTEP - 1) {
       // the owner of a pivot column q of the next step needs nothing but its own W(k, q) for tile (q, q): it is updated and staged in the
       // patch before the count, while the wavefronts with more tiles in this step's rows still solve; the chain starts right behind it
-      tp_sfor<tp_step_np(t + 1)>([&](auto B) {
+      sfor<tp_step_np(t + 1)>([&](auto B) {
         constexpr int q = tp_step_piv(t + 1, B);
         if constexpr (tp_owner(q) == WV) {
           d4& U = T[TPI(q, q)];
-          tp_sfor<tp_step_np(t)>([&](auto A) {
+          sfor<tp_step_np(t)>([&](auto A) {
             constexpr int k = tp_step_piv(t, A);
             if constexpr (tp_nz(k, q)) {
               const d4& Wd = T[TPI(k, q)];
@@ -284,7 +268,7 @@ AVM_NOINL bool chol_regs() {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       };
       if constexpr (tp_owns_piv(WV, t + 1)) {
-        tp_sfor<tp_step_np(t + 1)>([&](auto B) {
+        sfor<tp_step_np(t + 1)>([&](auto B) {
           constexpr int q = tp_step_piv(t + 1, B);
           if constexpr (tp_owner(q) == WV) run_chain(std::integral_constant<int, q>{});
         });
@@ -293,13 +277,13 @@ AVM_NOINL bool chol_regs() {
       CPROF(3);
       // (e) trailing update U(j, i) -= W(k, j)^T W(k, i), k < j <= i, over the tiles of this step's rows that exist (the next step's diagonal
       // tiles have theirs already), while the next chains run on their owners
-      tp_sfor<tp_step_np(t)>([&](auto A) {
+      sfor<tp_step_np(t)>([&](auto A) {
         constexpr int k = tp_step_piv(t, A);
-        tp_sfor<TPT - 1 - k>([&](auto II) {
+        sfor<TPT - 1 - k>([&](auto II) {
           constexpr int i = k + 1 + II;
           if constexpr (tp_owner(i) == WV && tp_nz(k, i)) {
             const d4& Wi = T[TPI(k, i)];
-            tp_sfor<i - k>([&](auto JJ) {
+            sfor<i - k>([&](auto JJ) {
               constexpr int j = k + 1 + JJ;
               if constexpr (tp_nz(k, j) && !(j == i && tp_is_piv(t + 1, i))) {
                 static_assert(tp_nz(j, i), "the pattern is closed under the elimination's fill");
@@ -331,9 +315,9 @@ AVM_NOINL bool chol_regs() {
   d4 E[TPT - 1];  // E[k] += U(k, i) .* x_i over this wavefront's columns i > k (element-wise: reduced once, when block k is due)
 #pragma unroll
   for (int k = 0; k < TPT - 1; k++) E[k] = d4{0, 0, 0, 0};
-  tp_sfor<TP_NSTEP>([&](auto TR) {
+  sfor<TP_NSTEP>([&](auto TR) {
     constexpr int t = TP_NSTEP - 1 - TR;
-    tp_sfor<tp_step_np(t)>([&](auto A) {
+    sfor<tp_step_np(t)>([&](auto A) {
       constexpr int i = tp_step_piv(t, A);
       constexpr int nb = i == TPT - 1 ? TP_NBL : 16;
       constexpr int PB = L_PATCH + tp_slot_of(i) * (16 * TP_PS);
@@ -358,7 +342,7 @@ AVM_NOINL bool chol_regs() {
         // x_jj is lane jj's bv; every lane subtracts colv[jj] x_jj - the broadcast as the multiply-add's own DPP operand (v_fmac_f64_dpp row_newbcast: no trip
         // through the scalar registers; the s_nop is the two wait states a DPP read needs behind the VALU write of the same register).  Round 6: bit-identical
         // to the 2 v_readlane_b32 + v_fma_f64 per step it replaced, solve 9.29 -> 9.21 ms; commit 24fd667 is the last that has that form.
-        tp_sfor<nb>([&](auto JR) {
+        sfor<nb>([&](auto JR) {
           constexpr int jj = nb - 1 - JR;
           xout = lr == jj ? bv : xout;
           const double nc = -colv[jj];
@@ -372,7 +356,7 @@ AVM_NOINL bool chol_regs() {
         wave_lds_sync();
         // fold x_i into the element-wise accumulators of the blocks above (lane (lk, lr): column lr of every tile)
         const double xl = lr < nb ? lds[L_ZV + 16 * i + min(lr, nb - 1)] : 0.0;
-        tp_sfor<i>([&](auto K) {
+        sfor<i>([&](auto K) {
           constexpr int k = K;
           if constexpr (tp_nz(k, i)) {
             const d4& U = T[TPI(k, i)];
@@ -385,7 +369,7 @@ AVM_NOINL bool chol_regs() {
     if constexpr (t > 0) {
       // every wavefront that holds a tile of a row the next step solves: its share of that block is complete (all its columns beyond it have been
       // folded in); the others' partial sums stay the zeros they were set to
-      tp_sfor<tp_step_np(t - 1)>([&](auto B) {
+      sfor<tp_step_np(t - 1)>([&](auto B) {
         constexpr int p = tp_step_piv(t - 1, B);
         if constexpr (tp_row_held(WV, p)) {
 #pragma unroll

@@ -1,4 +1,4 @@
-// solve/jac_times_vec.hpp - jac_times_vec_sq: |J' u|^2 for the Cauchy point; readlane_d
+// solve/jac_times_vec.hpp - jac_times_vec_sq: |J' u|^2 for the Cauchy point
 // Part of window_solve.hip, which includes it inside namespace avm; no translation unit of its own.
 
 // || J' u ||^2 with J' the Jacobi-scaled Jacobian, u in lds[L_ST] (scaled space), at state lds[L_X].
@@ -125,11 +125,4 @@ AVM_NOINL double jac_times_vec_sq(const WinCtx&, const avm_options&) {
     }
   }
   return block_sum1(acc);
-}
-
-AVM_DEV double readlane_d(double v, int srclane) {  // srclane must be wave-uniform
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_readlane(lo, srclane);
-  hi = __builtin_amdgcn_readlane(hi, srclane);
-  return __hiloint2double(hi, lo);
 }

@@ -187,7 +187,6 @@ static_assert(I_END <= 720, "int carve");
 constexpr int L_ZERO = L_INT + 340, L_ONE = L_INT + 341;  // the constants 0.0 and 1.0 of chol_regs' tile load, in the unused tail of the int carve (set by schur_reduce)
 static_assert(2 * 340 >= I_END, "the constants sit behind the int carve");
 #endif
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // Issue priority of the calling wavefront (throughput build only).  Two windows share every SIMD there, one wavefront each: while one
 // of them streams MFMAs / factor arithmetic (the frame tasks, the Schur tiles, the trailing updates of the factorization: AVM_PRIO_BULK)

@@ -1,4 +1,4 @@
-// solve/lds.hpp - the workgroup's LDS and what every phase uses: LDS(), the profiling stopwatches, each build's layout, workgroup reductions, roff / s_off, fast_rcp / fast_rsqrt
+// solve/lds.hpp - the workgroup's LDS and what every phase uses: LDS(), the profiling stopwatches, each build's layout, workgroup reductions, roff / s_off
 // Part of window_solve.hip, which includes it inside namespace avm; no translation unit of its own.
 
 // the workgroup's dynamic LDS, always reached through the shared symbol (never through a generic pointer that
@@ -26,12 +26,6 @@ AVM_DEV void lds_base_check() {
 #define PROFQ(c, k) do { if ((c).prof && threadIdx.x == 0) { long long n__ = clock64(); (c).prof[k] += n__ - pq__; pq__ = n__; } } while (0)
 
 #include "layout.hpp"  // (a part includes a part by its name inside solve/)
-
-AVM_DEV void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // A value every lane of the wavefront holds alike, moved to scalar registers.  The trust-region loop's own scalars (radius, mu, norms,
 // costs) are live across every outlined phase; as vector registers the compiler parks them in scratch memory around the calls and each
@@ -113,20 +107,3 @@ AVM_DEV int s_off(int r, int c) {
 #else
 #define S_OFF(r, c) (L_S + roff(r) + (c))
 #endif
-
-// reciprocal / reciprocal square root from the hardware estimate + two Newton steps (about one ulp; the library forms spend
-// two to three times as long on range handling that the operands here - depths, squared norms >= 1 - never need)
-AVM_DEV double fast_rcp(double x) {
-  double y = __builtin_amdgcn_rcp(x), e = fma(-x, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-x, y, 1.0);
-  return fma(y, e, y);
-}
-// raw v_rsq_f64 + two Newton steps (the library rsqrt spends ~3x as long in range handling we do not need:
-// pivots of an SPD matrix are normal positive numbers)
-AVM_DEV double fast_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  y = y * (1.5 - (0.5 * x) * y * y);
-  return y;
-}

@@ -44,7 +44,7 @@ extern __shared__ __attribute__((aligned(16))) char avm_smem[];
 
 namespace {
 
-#include "solve/lds.hpp"              // LDS(), the profiling stopwatches, layout.hpp, workgroup reductions, roff / s_off, fast_rcp / fast_rsqrt
+#include "solve/lds.hpp"              // LDS(), the profiling stopwatches, layout.hpp, workgroup reductions, roff / s_off
 #include "solve/factors.hpp"          // proj_eval, imu_raw, imu_col, prior_block_dx: the factors, one thread each
 #include "solve/context.hpp"          // address-space typedefs, WinCtx and the options in LDS, build_frames, ric_of, td_shift
 #include "solve/prior_residual.hpp"   // prior_residual_dev, prior_wave
@@ -57,7 +57,7 @@ namespace {
 #endif
 #include "solve/imu_mfma.hpp"         // ImuOperands, imu_factor_load, imu_factor_mfma: one IMU factor on the matrix cores
 #include "solve/eval_jac.hpp"         // eval_jac: the full evaluation, phases A to E
-#include "solve/jac_times_vec.hpp"    // jac_times_vec_sq (the Cauchy point's |J' u|^2), readlane_d
+#include "solve/jac_times_vec.hpp"    // jac_times_vec_sq (the Cauchy point's |J' u|^2)
 #include "solve/chol_regs_tables.hpp" // chol_regs' elimination order and compile-time tables (tests/test_tp_pattern.py states them in numpy)
 #include "solve/chol_regs.hpp"        // chol_regs<WV>: the factorization on register tiles, both triangular solves; tp_pattern_export
 #ifndef AVM_TP  // the other builds (the latency build: for a prior chol_regs' pattern does not hold)
