@@ -235,6 +235,22 @@ class FselOut(C.Structure):
     _fields_ = [("n_selected", c_ip), ("selected_ids", c_ip), ("fvalues", c_dp), ("min_gap", c_dp)]
 
 
+MAX_ALIGN_FRAMES = 64  # AVM_MAX_ALIGN_FRAMES
+
+
+class AlignBatch(C.Structure):
+    """avm_align_batch (include/avm.h): the inputs of VisualIMUAlignment for B windows."""
+    _fields_ = [("n_windows", C.c_int32), ("max_frames", C.c_int32), ("max_samp", C.c_int32),
+                ("n_frames", c_ip), ("frame_R", c_dp), ("frame_T", c_dp), ("tic", c_dp),
+                ("imu_n", c_ip), ("imu_dt", c_dp), ("imu_acc", c_dp), ("imu_gyr", c_dp), ("imu_lin_ba", c_dp), ("imu_lin_bg", c_dp),
+                ("key_index", c_ip)]
+
+
+class AlignOut(C.Structure):
+    """avm_align_out (include/avm.h)."""
+    _fields_ = [("ok", c_ip), ("delta_bg", c_dp), ("g_c0", c_dp), ("x", c_dp), ("g_world", c_dp), ("deltas", c_dp)]
+
+
 AVM_ABI_VERSION = 6  # include/avm.h: avm_create() refuses a caller built against another header
 
 

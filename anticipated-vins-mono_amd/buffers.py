@@ -166,6 +166,41 @@ class FselOutArrays(_Arrays):
         return self._fill(abi.FselOut())
 
 
+class AlignArrays(_Arrays):
+    """avm_align_batch: all_image_frame (SfM poses and raw IMU) of B windows, the inputs of Estimator::visualInitialAlign()."""
+
+    F64 = ["frame_R", "frame_T", "tic", "imu_dt", "imu_acc", "imu_gyr", "imu_lin_ba", "imu_lin_bg"]
+    I32 = ["n_frames", "imu_n", "key_index"]
+
+    def struct(self) -> abi.AlignBatch:
+        return self._fill(abi.AlignBatch())
+
+    @property
+    def n_windows(self) -> int:
+        return self.dims["n_windows"]
+
+    def slice(self, lo: int, hi: int) -> "AlignArrays":
+        d = dict(self.dims)
+        d["n_windows"] = hi - lo
+        return AlignArrays(d, {k: v[lo:hi] for k, v in self.a.items()})
+
+
+class AlignOutArrays(_Arrays):
+    F64, I32 = ["delta_bg", "g_c0", "x", "g_world", "deltas"], ["ok"]
+
+    @staticmethod
+    def alloc(n_windows: int, max_frames: int, device=None, want_deltas: bool = True) -> "AlignOutArrays":
+        a = {"ok": np.zeros(n_windows, np.int32), "delta_bg": np.zeros((n_windows, 3)), "g_c0": np.zeros((n_windows, 3)),
+             "x": np.zeros((n_windows, 3 * max_frames + 1)), "g_world": np.zeros((n_windows, 3))}
+        if want_deltas:
+            a["deltas"] = np.zeros((n_windows, max_frames - 1, 10))
+        o = AlignOutArrays({}, a)
+        return o.to_device(device) if device else o
+
+    def struct(self) -> abi.AlignOut:
+        return self._fill(abi.AlignOut())
+
+
 def summary_alloc(n_windows: int, device=None):
     """[B] avm_solve_summary records (numpy structured array, or a raw byte tensor on device)."""
     if device is None:

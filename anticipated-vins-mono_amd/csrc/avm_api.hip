@@ -2,6 +2,7 @@
 // Host language is C++ (the reference's host code is C++: vins_estimator/src/estimator.cpp,
 // feature_selector.cpp).  No torch types, no exceptions across the boundary.  There is no CPU
 // fallback: without a HIP device avm_create() fails with AVM_ERR_NO_DEVICE.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -61,6 +62,7 @@ struct avm_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   int n_slots = 0;
+  int max_windows = 0;  // avm_config::max_windows (0: no limit stated); avm_visual_initial_align_batch refuses larger batches
   // device buffers owned by the ctx
   double* scratch = nullptr;
   int32_t* iscratch = nullptr;
@@ -138,8 +140,17 @@ const char* table_rule_text(int rule) {
   return "bad table";
 }
 
-int report_bad(avm_ctx* c, int first_bad, const char* unit) {
-  c->err = std::string(unit) + " " + std::to_string(first_bad / 8) + ": " + table_rule_text(first_bad % 8);
+const char* align_rule_text(int rule) {
+  switch (rule) {
+    case BAD_ALIGN_FRAMES: return "n_frames outside [2, max_frames]";
+    case BAD_ALIGN_IMU: return "imu_n outside [0, max_samp]";
+    case BAD_ALIGN_KEYS: return "key_index must be strictly increasing inside [0, n_frames)";
+  }
+  return "bad table";
+}
+
+int report_bad(avm_ctx* c, int first_bad, const char* unit, const char* (*text)(int) = table_rule_text) {
+  c->err = std::string(unit) + " " + std::to_string(first_bad / 8) + ": " + text(first_bad % 8);
   return AVM_ERR_INVALID;
 }
 
@@ -171,12 +182,12 @@ int flag_begin(avm_ctx* c, int words, Launch launch, FlagCheck* f) {
   return AVM_OK;
 }
 
-int flag_end(avm_ctx* c, const FlagCheck& f, const char* unit, int* tp_misfit = nullptr) {
+int flag_end(avm_ctx* c, const FlagCheck& f, const char* unit, int* tp_misfit = nullptr, const char* (*text)(int) = table_rule_text) {
   HIPCHK(c, hipEventSynchronize(c->ev_flag));
   if (tp_misfit) *tp_misfit = f.host[1];
   if (f.host[0] == 0x7f7f7f7f) return AVM_OK;
   (void)hipStreamSynchronize(c->stream);
-  return report_bad(c, f.host[0], unit);
+  return report_bad(c, f.host[0], unit, text);
 }
 
 int null_window_tables(avm_ctx* c, const avm_window_batch* b, int what) {
@@ -319,7 +330,7 @@ inline void set_ptr(void* s, const Field& f, const void* p) { std::memcpy(static
 
 // who uses an array: the calls that take the whole batch (solve, pre-integration, factor evaluation; struct-valued outputs), and the four
 // that take a subset of the window tables
-enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16 };
+enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32 };
 constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE | U_SLIDE | U_PROP;
 
 // S: the struct of the member; D, nmember: the struct the dims come from (`d` in `count`) and its batch size (`N` in `count`)
@@ -337,15 +348,15 @@ constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE
 // avm_window_batch.  The four state arrays come first so that the packed path can bring them back with one copy (N_STATES).
 #define WIN(member, type, count, in, out) FIELD(avm_window_batch, avm_window_batch, n_windows, "w_" #member, member, type, count, in, out)
 const Field WINDOW_FIELDS[] = {
-    WIN(pose, double, N * 77, U_GEOM | U_PROP, U_WHOLE | U_SLIDE | U_PROP)
-    WIN(speedbias, double, N * 99, U_IMU, U_WHOLE | U_SLIDE | U_PROP)
-    WIN(ex_pose, double, N * 7, U_GEOM, U_WHOLE | U_SLIDE)
-    WIN(inv_depth, double, N * d.max_feat, U_GEOM, U_WHOLE | U_TRI | U_SLIDE)
-    WIN(n_feat, int32_t, N, U_GEOM, U_SLIDE)
-    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM, U_SLIDE)
-    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE, U_SLIDE)
-    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM, U_SLIDE)
-    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM, U_SLIDE)
+    WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
+    WIN(speedbias, double, N * 99, U_IMU | U_ALIGN, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
+    WIN(ex_pose, double, N * 7, U_GEOM | U_ALIGN, U_WHOLE | U_SLIDE)
+    WIN(inv_depth, double, N * d.max_feat, U_GEOM | U_ALIGN, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN)
+    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN, U_SLIDE)
+    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN, U_SLIDE)
+    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN, U_SLIDE)
+    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN, U_SLIDE)
+    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN, U_SLIDE)
     WIN(imu_n, int32_t, N * 10, U_IMU, U_SLIDE)
     WIN(imu_dt, double, N * 10 * d.max_samp, U_IMU, U_SLIDE)
     WIN(imu_acc, double, N * 10 * (d.max_samp + 1) * 3, U_IMU, U_SLIDE)
@@ -406,6 +417,21 @@ const Field HORIZON_FIELDS[] = {HZ(k_pos, double, 3) HZ(k_quat, double, 4) HZ(k_
                                 HZ(k1_quat, double, 4) HZ(acc, double, 3) HZ(gyr, double, 3) HZ(nr_imu, int32_t, 1) HZ(delta_imu, double, 1)};
 #undef HZ
 constexpr Table HORIZON_IN = table_of(HORIZON_FIELDS);
+
+// avm_align_batch / avm_align_out (avm_visual_initial_align_batch)
+#define AL(member, type, count) FIELD(avm_align_batch, avm_align_batch, n_windows, "al_" #member, member, type, count, U_WHOLE, 0)
+const Field ALIGN_FIELDS[] = {
+    AL(n_frames, int32_t, N) AL(frame_R, double, N * d.max_frames * 9) AL(frame_T, double, N * d.max_frames * 3) AL(tic, double, N * 3)
+    AL(imu_n, int32_t, N * (d.max_frames - 1)) AL(imu_dt, double, N * (d.max_frames - 1) * d.max_samp)
+    AL(imu_acc, double, N * (d.max_frames - 1) * (d.max_samp + 1) * 3) AL(imu_gyr, double, N * (d.max_frames - 1) * (d.max_samp + 1) * 3)
+    AL(imu_lin_ba, double, N * (d.max_frames - 1) * 3) AL(imu_lin_bg, double, N * (d.max_frames - 1) * 3) AL(key_index, int32_t, N * AVM_NFRAMES)};
+#undef AL
+constexpr Table ALIGN = table_of(ALIGN_FIELDS);
+#define AO(member, type, count) FIELD(avm_align_out, avm_align_batch, n_windows, "ao_" #member, member, type, count, 0, U_WHOLE)
+const Field ALIGN_OUT_FIELDS[] = {AO(ok, int32_t, N) AO(delta_bg, double, N * 3) AO(g_c0, double, N * 3) AO(x, double, N * (3 * d.max_frames + 1))
+                                  AO(g_world, double, N * 3) AO(deltas, double, N * (d.max_frames - 1) * 10)};
+#undef AO
+constexpr Table ALIGN_OUT = table_of(ALIGN_OUT_FIELDS);
 
 constexpr size_t PACK_LIMIT = 4u << 20;  // batches up to 4 MiB (a few windows: the real-time use) travel packed
 inline size_t pack_up(size_t n) { return (n + 63) & ~size_t(63); }
@@ -708,6 +734,7 @@ int avm_create(const avm_config* cfg, avm_ctx** out) {
   if (hipSetDevice(dev) != hipSuccess) return AVM_ERR_HIP;
   avm_ctx* c = new avm_ctx();
   c->device = dev;
+  c->max_windows = cfg ? cfg->max_windows : 0;
   // A BLOCKING stream (not hipStreamNonBlocking): device-resident buffers are usually produced on the legacy default
   // stream (PyTorch's current stream, plain hipMemcpy), and a blocking stream is ordered after that work and before
   // whatever the default stream does next - AVM_MEM_DEVICE calls need no extra synchronization from such callers.
@@ -998,6 +1025,21 @@ int avm_debug_struct_sizes(int* out) {
   return 7;
 }
 
+// test hook (not in avm.h): sizeof and the member offsets of avm_align_batch / avm_align_out, for the ctypes mirror check; out: >= 23 ints
+int avm_debug_align_layout(int* out) {
+  int n = 0;
+  out[n++] = (int)sizeof(avm_align_batch), out[n++] = (int)sizeof(avm_align_out), out[n++] = AVM_MAX_ALIGN_FRAMES;
+  for (size_t o : {offsetof(avm_align_batch, n_windows), offsetof(avm_align_batch, max_frames), offsetof(avm_align_batch, max_samp),
+                   offsetof(avm_align_batch, n_frames), offsetof(avm_align_batch, frame_R), offsetof(avm_align_batch, frame_T),
+                   offsetof(avm_align_batch, tic), offsetof(avm_align_batch, imu_n), offsetof(avm_align_batch, imu_dt),
+                   offsetof(avm_align_batch, imu_acc), offsetof(avm_align_batch, imu_gyr), offsetof(avm_align_batch, imu_lin_ba),
+                   offsetof(avm_align_batch, imu_lin_bg), offsetof(avm_align_batch, key_index), offsetof(avm_align_out, ok),
+                   offsetof(avm_align_out, delta_bg), offsetof(avm_align_out, g_c0), offsetof(avm_align_out, x),
+                   offsetof(avm_align_out, g_world), offsetof(avm_align_out, deltas)})
+    out[n++] = (int)o;
+  return n;
+}
+
 // test hook (not in avm.h): sqrt_info of the last pre-integration, [B][10][15][15]
 int avm_debug_copy_sqrt_info(avm_ctx* c, int n_windows, double* host_out) {
   if (!c || !c->pre_sqrt) return AVM_ERR_INVALID;
@@ -1022,6 +1064,76 @@ int avm_triangulate_batch(avm_ctx* c, avm_mem mem, avm_window_batch* batch, doub
   HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["triangulate"] = ms;
+  return AVM_OK;
+}
+
+int avm_visual_initial_align_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, const avm_align_batch* al, avm_window_batch* win,
+                                   avm_align_out* out) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!opt || !al || !out || al->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (al->max_frames > AVM_MAX_ALIGN_FRAMES) return fail(c, AVM_ERR_CAPACITY, "max_frames > 64 (AVM_MAX_ALIGN_FRAMES)");
+  if (c->max_windows > 0 && al->n_windows > c->max_windows) return fail(c, AVM_ERR_CAPACITY, "more windows than avm_config::max_windows");
+  if (al->max_frames < 2 || al->max_samp < 0) return fail(c, AVM_ERR_INVALID, "max_frames < 2 or max_samp < 0");
+  for (const Field& f : ALIGN)
+    if (!get_ptr(al, f) && (win || f.offset != offsetof(avm_align_batch, key_index))) return fail(c, AVM_ERR_INVALID, "a table of avm_align_batch is NULL");
+  if (!out->ok || !out->delta_bg || !out->g_c0 || !out->x || (win && !out->g_world))
+    return fail(c, AVM_ERR_INVALID, "avm_align_out: ok, delta_bg, g_c0, x (and g_world with windows) must be given");
+  int rc;
+  if (win) {
+    if (win->n_windows != al->n_windows) return fail(c, AVM_ERR_INVALID, "windows->n_windows differs from align->n_windows");
+    if (!win->pose || !win->speedbias || !win->ex_pose || !win->inv_depth || !win->obs_xy) return fail(c, AVM_ERR_INVALID, "null state array of the window batch");
+    if ((rc = check_wide_strides(c, win)) != AVM_OK) return rc;
+  }
+  if (al->n_windows == 0) return AVM_OK;
+  // table checks, before any kernel indexes with them
+  if (mem == AVM_MEM_HOST) {
+    for (int b = 0; b < al->n_windows; b++) {
+      const int rule = check_align_tables(*al, b, win != nullptr);
+      if (rule) return report_bad(c, b * 8 + rule, "window", align_rule_text);
+    }
+  } else {
+    FlagCheck f;
+    if ((rc = flag_begin(c, 1, [&](int* flag) { return launch_validate_align(*al, win != nullptr, flag, c->stream); }, &f)) != AVM_OK) return rc;
+    if ((rc = flag_end(c, f, "window", nullptr, align_rule_text)) != AVM_OK) return rc;
+  }
+  if (win && (rc = validate_windows(c, mem, win, CHK_TRACKS)) != AVM_OK) return rc;
+
+  AlignArgs aa;
+  std::memset(&aa.w, 0, sizeof aa.w);
+  if ((rc = on_device(c, mem, ALIGN, U_WHOLE, al, &aa.a)) != AVM_OK) return rc;
+  if (win && (rc = on_device(c, mem, WINDOWS, U_ALIGN, win, &aa.w)) != AVM_OK) return rc;
+  aa.has_windows = win ? 1 : 0;
+  aa.g_norm = std::sqrt(opt->g[0] * opt->g[0] + opt->g[1] * opt->g[1] + opt->g[2] * opt->g[2]);
+  avm_align_out want = *out;  // what this call returns: g_world only with windows
+  if (!win) want.g_world = nullptr;
+  aa.out = want;
+  if (mem == AVM_MEM_HOST && alloc_out(c, ALIGN_OUT, &want, &aa.out, al) != AVM_OK) return fail(c, AVM_ERR_HIP, "hipMalloc failed (align out)");
+  const size_t n_iv = (size_t)al->n_windows * (al->max_frames - 1);
+  aa.delta = aa.out.deltas ? aa.out.deltas : static_cast<double*>(pool_get(c, "al_delta", sizeof(double) * n_iv * 10));
+  aa.sum_dt = static_cast<double*>(pool_get(c, "al_sum_dt", sizeof(double) * n_iv));
+  if (!aa.delta || !aa.sum_dt) return fail(c, AVM_ERR_HIP, "hipMalloc failed (align pre-integrations)");
+  // (the rows of intervals beyond n_frames - 1 are never written by the kernels: defined values for the caller)
+  HIPCHK(c, hipMemsetAsync(aa.delta, 0, sizeof(double) * n_iv * 10, c->stream));
+
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, launch_align_gyro_bias(aa, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, launch_align_solve(aa, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+  if (win) {
+    HIPCHK(c, launch_align_prepare(aa, c->stream));
+    HIPCHK(c, launch_triangulate(aa.w, 5.0 /* INIT_DEPTH, parameters.cpp:113 */, c->stream, 1, aa.out.ok));
+    HIPCHK(c, launch_align_apply(aa, c->stream));
+  }
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  if (win && (rc = copy_back(c, mem, WINDOWS, U_ALIGN, win, &aa.w, win)) != AVM_OK) return rc;
+  if ((rc = copy_back(c, mem, ALIGN_OUT, U_WHOLE, &want, &aa.out, al)) != AVM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->last_ms["align_gyro_bias"] = ms;
+  if (hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) c->last_ms["align_solve"] = ms;
+  if (hipEventElapsedTime(&ms, c->ev[2], c->ev[3]) == hipSuccess) c->last_ms["align_apply"] = ms;
   return AVM_OK;
 }
 

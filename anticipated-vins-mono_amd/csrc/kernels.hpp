@@ -161,6 +161,37 @@ __host__ __device__ inline int window_prior_tp_misfit(const avm_window_batch& B,
   return (nsb > 1 || later ? 1 : 0) | (late ? 2 : 0);
 }
 
+// ---- Estimator::visualInitialAlign (visual_align.hip) -------------------------------------------------------------------------------
+struct AlignArgs {
+  avm_align_batch a;   // device pointers
+  avm_window_batch w;  // device pointers; only read when has_windows
+  int has_windows;
+  double g_norm;       // G.norm()
+  avm_align_out out;   // device pointers (ok, delta_bg, g_c0, x always; g_world with windows)
+  double *delta, *sum_dt;  // [B][max_frames - 1][10], [B][max_frames - 1]: the repropagated pre-integrations
+};
+enum { BAD_ALIGN_FRAMES = 1, BAD_ALIGN_IMU = 2, BAD_ALIGN_KEYS = 3 };
+// 0 = fine; otherwise the first violated rule of window b (keys: key_index is read)
+__host__ __device__ inline int check_align_tables(const avm_align_batch& A, int b, bool keys) {
+  const int F = A.n_frames[b];
+  if (F < 2 || F > A.max_frames) return BAD_ALIGN_FRAMES;
+  for (int j = 0; j < F - 1; j++) {
+    const int n = A.imu_n[(size_t)b * (A.max_frames - 1) + j];
+    if (n < 0 || n > A.max_samp) return BAD_ALIGN_IMU;
+  }
+  if (keys)
+    for (int i = 0; i < AVM_NFRAMES; i++) {
+      const int k = A.key_index[(size_t)b * AVM_NFRAMES + i];
+      if (k < 0 || k >= F || (i > 0 && k <= A.key_index[(size_t)b * AVM_NFRAMES + i - 1])) return BAD_ALIGN_KEYS;
+    }
+  return 0;
+}
+hipError_t launch_validate_align(const avm_align_batch& a, bool keys, int* first_bad, hipStream_t stream);
+hipError_t launch_align_gyro_bias(const AlignArgs& a, hipStream_t stream);
+hipError_t launch_align_solve(const AlignArgs& a, hipStream_t stream);
+hipError_t launch_align_prepare(const AlignArgs& a, hipStream_t stream);
+hipError_t launch_align_apply(const AlignArgs& a, hipStream_t stream);
+
 // Launch of a kernel whose dynamic LDS exceeds the default limit.  hipFuncAttributeMaxDynamicSharedMemorySize is set once per process
 // and kernel, by the first call: a function-local static per Kernel, initialised under the language's guard, so concurrent first calls from
 // two threads are safe.  A failed hipFuncSetAttribute is remembered and returned by every later call as well; it is not tried again.
@@ -198,7 +229,8 @@ hipError_t launch_fsel_build_cloud(const avm_window_batch& b, const double* k1_p
 hipError_t launch_fsel_nn_depth(const avm_fsel_batch& b, double* kd, double* depth_out, hipStream_t stream);
 size_t fsel_kd_doubles(const avm_fsel_batch& b);  // doubles of FselBuffers::kd / the kd argument above for this batch
 hipError_t launch_fsel_horizon_imu(const avm_fsel_horizon_in& in, double* hor_pos, double* hor_quat, hipStream_t stream);
-hipError_t launch_triangulate(const avm_window_batch& b, double init_depth, hipStream_t stream);
+// zero_tic: triangulate on the camera positions themselves (visualInitialAlign, estimator.cpp:383-388); only: optional [B] device mask, windows with 0 are left alone
+hipError_t launch_triangulate(const avm_window_batch& b, double init_depth, hipStream_t stream, int zero_tic = 0, const int32_t* only = nullptr);
 hipError_t launch_imu_propagate(const avm_window_batch& b, const double* g, hipStream_t stream);
 hipError_t launch_slide_window(const avm_window_batch& b, int flag, int shift_depth, double init_depth, int* err, hipStream_t stream);
 hipError_t launch_projection_td_eval(const avm_td_factor_batch& f, double* residual, double* jac, hipStream_t stream);

@@ -16,17 +16,19 @@ constexpr int TRI_NT = 64;
 constexpr int TRI_ROWS = 2 * NFR;  // 22
 }
 
-__global__ __launch_bounds__(TRI_NT) void triangulate_kernel(avm_window_batch B, double init_depth) {
+// zero_tic: on the camera positions themselves (visualInitialAlign, estimator.cpp:383-388); only: optional [B] mask, windows with 0 are left alone
+__global__ __launch_bounds__(TRI_NT) void triangulate_kernel(avm_window_batch B, double init_depth, int zero_tic, const int32_t* only) {
   const long gid = (long)blockIdx.x * TRI_NT + threadIdx.x;
   const int w = (int)(gid / B.max_feat), e = (int)(gid % B.max_feat);
   if (w >= B.n_windows || e >= B.n_feat[w]) return;
+  if (only && !only[w]) return;
   double* lam = B.inv_depth + (size_t)w * B.max_feat + e;
   if (*lam > 0.0) return;
   const int start = B.feat_start[(size_t)w * B.max_feat + e], nobs = B.feat_nobs[(size_t)w * B.max_feat + e];
   const double* obs = B.obs_xy + ((size_t)w * B.max_obs + B.feat_obs_begin[(size_t)w * B.max_feat + e]) * 2;
   const double* pose = B.pose + (size_t)w * NFR * 7;
   const double* ex = B.ex_pose + (size_t)w * 7;
-  const v3 tic = mk3(ex[0], ex[1], ex[2]);
+  const v3 tic = zero_tic ? mk3(0, 0, 0) : mk3(ex[0], ex[1], ex[2]);  // (zero: TIC_TMP of estimator.cpp:383-388)
   double ric[9];
   q2R(quat{ex[6], ex[3], ex[4], ex[5]}, ric);
   auto cam = [&](int f, double* R, v3& t) {  // camera f in the world: R = Rs ric, t = Ps + Rs tic
@@ -399,10 +401,10 @@ hipError_t launch_projection_td_eval(const avm_td_factor_batch& f, double* resid
   return hipGetLastError();
 }
 
-hipError_t launch_triangulate(const avm_window_batch& b, double init_depth, hipStream_t stream) {
+hipError_t launch_triangulate(const avm_window_batch& b, double init_depth, hipStream_t stream, int zero_tic, const int32_t* only) {
   const long n = (long)b.n_windows * b.max_feat;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(triangulate_kernel, dim3((unsigned)((n + TRI_NT - 1) / TRI_NT)), dim3(TRI_NT), 0, stream, b, init_depth);
+  hipLaunchKernelGGL(triangulate_kernel, dim3((unsigned)((n + TRI_NT - 1) / TRI_NT)), dim3(TRI_NT), 0, stream, b, init_depth, zero_tic, only);
   return hipGetLastError();
 }
 

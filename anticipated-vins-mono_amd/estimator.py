@@ -69,6 +69,28 @@ class Estimator:
             pa["r"][i, :mp] = wa["prior_r"][i, :mp]
             pa["x0"][i, :mb] = wa["prior_x0"][i, :mb]
 
+    # the reference's name
+    def visualInitialAlign(self, align: buffers.AlignArrays, windows: buffers.WindowArrays = None, out: buffers.AlignOutArrays = None):
+        """Estimator::visualInitialAlign (estimator.cpp:355-431) for B windows.  windows=None: VisualIMUAlignment only
+        (initial_aligment.cpp:199-207).  With windows: pose, velocities, gyro biases and inverse depths are set in place; a window
+        whose `ok` is 0 keeps them, except for the bias increment.  Returns the AlignOutArrays (ok, delta_bg, g_c0, x, g_world,
+        deltas).  Before the first optimization() call reset_linearization_biases(windows)."""
+        dev = "cuda:%d" % self.ctx.device if align.on_device else None
+        out = out or buffers.AlignOutArrays.alloc(align.n_windows, align.dims["max_frames"], dev)
+        sa, so = align.struct(), out.struct()
+        sw = windows.struct() if windows is not None else None
+        rc = self.ctx._L.avm_visual_initial_align_batch(self.ctx.h, C.byref(self.options), align.mem, C.byref(sa),
+                                                        C.byref(sw) if sw is not None else None, C.byref(so))
+        self.ctx.check(rc, "avm_visual_initial_align_batch")
+        return out
+
+    @staticmethod
+    def reset_linearization_biases(windows: buffers.WindowArrays):
+        """pre_integrations[i]->repropagate(0, Bgs[i]) of visualInitialAlign (estimator.cpp:391-394): the solve pre-integrates from
+        imu_lin_ba / imu_lin_bg, so they become 0 and the (new) gyro biases of the frames."""
+        windows.a["imu_lin_ba"][:] = 0.0
+        windows.a["imu_lin_bg"][:] = windows.a["speedbias"][:, : abi.WINDOW_SIZE, 6:9]
+
     def triangulate(self, windows: buffers.WindowArrays, init_depth: float = 5.0):
         """FeatureManager::triangulate (feature_manager.cpp:202-257), the step before optimization() in solveOdometry():
         features whose inverse depth is <= 0 get 1 / depth from the multi-view linear triangulation, in place."""

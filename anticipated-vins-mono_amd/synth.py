@@ -10,10 +10,11 @@ a shard of windows is identical no matter which rank generates it.
 import numpy as np
 
 from . import abi
-from .buffers import FselArrays, WindowArrays
+from .buffers import AlignArrays, FselArrays, WindowArrays
 
 SEED_WINDOW = 0xA17C0000
 SEED_FSEL = 0xF5E10000
+SEED_ALIGN = 0xA1160000  # make_align: a stream of its own, the generators above do not move
 
 # config/euroc/euroc_config.yaml:30-42
 RIC = np.array(
@@ -502,3 +503,95 @@ class Sequence:
         dt, acc, gyr = self.imu_interval(k + 1 + abi.WINDOW_SIZE - 1)
         a["imu_n"][0, 9], a["imu_dt"][0, 9, :20], a["imu_acc"][0, 9, :21], a["imu_gyr"][0, 9, :21] = 20, dt, acc, gyr
         return keep + entrants
+
+
+def make_align(n_windows, n_frames, key_index=None, scale=2.5, first_id=0, max_frames=None, n_feat=40, bgs0=None, ragged=False,
+               frame_samples=20, max_samp=None):
+    """Inputs of Estimator::visualInitialAlign for B windows: all_image_frame with `n_frames` frames (SfM poses and raw 200 Hz IMU),
+    and - when key_index (11 strictly increasing positions in all_image_frame) is given - the window batch of the key frames with
+    n_feat feature tracks.  Window w comes from seed SEED_ALIGN + first_id + w.  The SfM poses are the analytic trajectory's camera
+    poses seen from an arbitrary frame c0 (a random rotation and origin), divided by the true `scale`, as ImageFrame::R = R_c0_ck RIC^T
+    and ImageFrame::T (estimator.cpp:288-289).  bgs0: the incoming Bgs (also the linearization bias of every interval); ragged:
+    4/5 .. 6/5 of frame_samples per interval (16 .. 24 at the default) instead of frame_samples.  Returns (AlignArrays, WindowArrays or None)."""
+    B, F = n_windows, n_frames
+    MF = max_frames or F
+    ms = max_samp or (frame_samples * 6 // 5 if ragged else frame_samples)
+    dt = 0.005
+    bgs0 = np.zeros(3) if bgs0 is None else np.asarray(bgs0, float)
+    al = {"n_frames": np.full(B, F, np.int32), "frame_R": np.zeros((B, MF, 3, 3)), "frame_T": np.zeros((B, MF, 3)), "tic": np.tile(TIC, (B, 1)),
+          "imu_n": np.zeros((B, MF - 1), np.int32), "imu_dt": np.zeros((B, MF - 1, ms)), "imu_acc": np.zeros((B, MF - 1, ms + 1, 3)),
+          "imu_gyr": np.zeros((B, MF - 1, ms + 1, 3)), "imu_lin_ba": np.zeros((B, MF - 1, 3)), "imu_lin_bg": np.tile(bgs0, (B, MF - 1, 1)),
+          "key_index": np.zeros((B, abi.NFRAMES), np.int32)}
+    al["frame_R"][:] = np.eye(3)
+    win = None
+    if key_index is not None:
+        key = np.asarray(key_index, np.int32)
+        assert key.shape == (abi.NFRAMES,) and (np.diff(key) > 0).all() and key[0] >= 0 and key[-1] < F
+        al["key_index"][:] = key
+        wms = int(ms * np.diff(key).max())
+        win = make_windows(0, n_feat=n_feat, with_prior=False, max_samp=wms, max_prior=1, max_pblk=1).a
+        win = {k: np.zeros((B,) + v.shape[1:], v.dtype) for k, v in win.items()}
+    G = np.array([0, 0, G_NORM])
+    for b in range(B):
+        rng = np.random.Generator(np.random.Philox(key=SEED_ALIGN + first_id + b))
+        tr = _Trajectory(rng)
+        ba, bg = rng.normal(0, 0.02, 3), rng.normal(0, 0.002, 3)
+        ns = rng.integers(frame_samples * 4 // 5, frame_samples * 6 // 5 + 1, F - 1) if ragged else np.full(F - 1, frame_samples)
+        idx = np.concatenate([[0], np.cumsum(ns)])  # frame k is sample idx[k] of the 200 Hz grid
+        tk = idx * dt
+        n_all = int(idx[-1]) + 1
+        acc, gyr = np.zeros((n_all, 3)), np.zeros((n_all, 3))
+        for i in range(n_all):
+            t = i * dt
+            acc[i] = tr.R(t).T @ (tr.acc(t) + G) + ba + rng.normal(0, ACC_N, 3)
+            gyr[i] = tr.omega_body(t) + bg + rng.normal(0, GYR_N, 3)
+        for j in range(F - 1):
+            n = int(ns[j])
+            al["imu_n"][b, j] = n
+            al["imu_dt"][b, j, :n] = dt
+            al["imu_acc"][b, j, : n + 1] = acc[idx[j] : idx[j] + n + 1]
+            al["imu_gyr"][b, j, : n + 1] = gyr[idx[j] : idx[j] + n + 1]
+        # c0: an arbitrary frame
+        Q = _rot_zyx(*rng.uniform(-np.pi, np.pi, 3) * np.array([1.0, 0.45, 1.0]))
+        org = tr.pos(0.0) + rng.normal(0, 1.0, 3)
+        Rw = [tr.R(t) for t in tk]
+        Pw = [tr.pos(t) for t in tk]
+        for k in range(F):
+            al["frame_R"][b, k] = Q @ Rw[k] @ _expm_so3(rng.normal(0, np.deg2rad(0.02), 3))
+            al["frame_T"][b, k] = (Q @ (Pw[k] + Rw[k] @ TIC - org) + rng.normal(0, 2e-3, 3)) / scale
+        if win is None:
+            continue
+        # ---- the window of the key frames: IMU intervals concatenated, feature tracks over the key frames
+        for i in range(abi.WINDOW_SIZE):
+            lo, hi = int(idx[key[i]]), int(idx[key[i + 1]])
+            win["imu_n"][b, i] = hi - lo
+            win["imu_dt"][b, i, : hi - lo] = dt
+            win["imu_acc"][b, i, : hi - lo + 1] = acc[lo : hi + 1]
+            win["imu_gyr"][b, i, : hi - lo + 1] = gyr[lo : hi + 1]
+        win["imu_lin_bg"][b] = bgs0
+        win["speedbias"][b, :, 6:9] = bgs0
+        win["pose"][b, :, 6] = 1.0
+        win["ex_pose"][b, :3], win["ex_pose"][b, 3:] = TIC, quat_from_R(RIC)
+        win["inv_depth"][b] = 0.2
+        win["n_feat"][b] = n_feat
+        Rk, Pk = [Rw[k] for k in key], [Pw[k] for k in key]
+        starts = np.sort(rng.integers(0, 7, n_feat))
+        o = 0
+        for e in range(n_feat):
+            s0 = int(starts[e])
+            L = int(rng.integers(4, abi.NFRAMES - s0 + 1))
+            for _ in range(50):
+                xy = np.array([rng.uniform(-0.7, 0.7), rng.uniform(-0.45, 0.45)])
+                pw = Rk[s0] @ (RIC @ (np.array([xy[0], xy[1], 1.0]) * rng.uniform(2.0, 12.0)) + TIC) + Pk[s0]
+                pcs = [RIC.T @ (Rk[f].T @ (pw - Pk[f]) - TIC) for f in range(s0, s0 + L)]
+                if min(pc[2] for pc in pcs) >= 0.5:
+                    break
+            win["feat_start"][b, e], win["feat_nobs"][b, e], win["feat_obs_begin"][b, e] = s0, L, o
+            win["obs_xy"][b, o : o + L] = np.array([pc[:2] / pc[2] for pc in pcs]) + rng.normal(0, 1.5 / 460.0, (L, 2))
+            o += L
+    al["frame_R"] = al["frame_R"].reshape(B, MF, 9)
+    align = AlignArrays(dict(n_windows=B, max_frames=MF, max_samp=ms), al)
+    if win is None:
+        return align, None
+    d = dict(n_windows=B, max_feat=max(n_feat, 1), max_obs=max(n_feat, 1) * abi.NFRAMES, max_samp=wms, max_prior=1, max_pblk=1)
+    return align, WindowArrays(d, win)

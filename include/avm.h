@@ -422,6 +422,57 @@ int avm_fsel_build_cloud(avm_ctx* ctx, avm_mem mem, const avm_window_batch* wind
  * feat_obs_begin / feat_nobs change (one element moves for removeFront).  inv_depth holds 1 / estimated_depth. */
 int avm_slide_window(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, int32_t marginalization_flag, int32_t shift_depth, double init_depth);
 
+/* ---- Estimator::visualInitialAlign (estimator.cpp:355-431) with VisualIMUAlignment (initial/initial_aligment.cpp): the step that
+ * moves solver_flag from INITIAL to NON_LINEAR.  It starts from the up-to-scale camera trajectory of initialStructure (relativePose,
+ * GlobalSFM, solvePnP stay with the host: OpenCV and a Ceres BA) and is dense FP64 algebra on the raw IMU of all_image_frame. */
+#define AVM_MAX_ALIGN_FRAMES 64   /* all_image_frame.size(); 63 intervals = one lane per interval of a wavefront */
+
+typedef struct avm_align_batch {          /* the inputs of VisualIMUAlignment(all_image_frame, Bgs, g, x) */
+  int32_t n_windows, max_frames, max_samp;
+  const int32_t* n_frames;   /* [B] all_image_frame.size(), 2 .. max_frames */
+  const double* frame_R;     /* [B][max_frames][9] ImageFrame::R row-major (= R_c0_ck * RIC^T, estimator.cpp:288,342) */
+  const double* frame_T;     /* [B][max_frames][3] ImageFrame::T (camera position in c0, up to scale) */
+  const double* tic;         /* [B][3] TIC[0] */
+  /* raw IMU of interval j (frame j -> j+1), same conventions as avm_window_batch with 10 -> max_frames-1 */
+  const int32_t* imu_n;      /* [B][max_frames-1] */
+  const double *imu_dt, *imu_acc, *imu_gyr, *imu_lin_ba, *imu_lin_bg;
+  const int32_t* key_index;  /* [B][11] position of Headers[i] in all_image_frame, strictly increasing; only read when windows != NULL */
+} avm_align_batch;
+
+typedef struct avm_align_out {
+  int32_t* ok;        /* [B] the bool visualInitialAlign returns */
+  double* delta_bg;   /* [B][3] */
+  double* g_c0;       /* [B][3] g after RefineGravity, in c0 */
+  double* x;          /* [B][3*max_frames+1] body-frame velocities of all frames, then s (already /100, :190-191) */
+  double* g_world;    /* [B][3] R0 * g (:418); only written when windows != NULL */
+  double* deltas;     /* nullable [B][max_frames-1][10]: delta p,q,v after the repropagation - parity surface */
+} avm_align_out;
+
+/* windows == NULL: exactly VisualIMUAlignment (initial_aligment.cpp:199-207) - solveGyroscopeBias, the repropagation of every interval
+ * with (0, Bgs[0]), LinearAlignment, RefineGravity.  Bgs[0] is then the linearization bias of interval 0, imu_lin_bg[b][0].
+ * windows != NULL: the whole of visualInitialAlign, in place on windows->pose, speedbias[.][.][0..2], speedbias[.][.][6..8] and
+ * inv_depth; Bgs are speedbias[.][i][6..8].  A window with ok == 0 keeps its pose, velocities and depths; its gyro biases are still
+ * incremented by delta_bg (the reference does that before it can fail).  G.norm() is the norm of opt->g, RIC the quaternion of
+ * windows->ex_pose, INIT_DEPTH 5.0 (parameters.cpp:113).  ok, delta_bg, g_c0 and x must be given (g_world too with windows).
+ *   x of a window with n_frames < max_frames: velocities at [0, 3 n_frames), zeros up to 3 max_frames, s at index 3 max_frames.
+ *   x (s included), g_c0 and g_world of a window with ok == 0 are zero, wherever it failed; delta_bg and deltas are what was computed.
+ * Quirks of the reference that are kept: RefineGravity never clears or un-scales its A and b between the four passes
+ * (:63-66, :115-116); Vs[kv] = R_key(kv) * x.segment<3>(kv * 3) indexes x by the key-frame counter, not by the frame's position in
+ * all_image_frame (estimator.cpp:397-406).
+ * Deviations: the solves are Cholesky factorizations without pivoting.  Non-finite inputs, or a pivot that is not a positive finite
+ * number, end THAT window with ok = 0 (delta_bg = 0 if it is the 3 x 3 system of the gyroscope bias) - Eigen's pivoted LDLT would
+ * return some vector for a singular system, which the reference gives no meaning to.  n_frames < 4 (6 (F - 1) equations for 3 F + 4
+ * unknowns) is refused the same way.  FromTwoVectors' antipodal branch (g along -z of c0; Eigen takes an SVD there) uses a unit axis
+ * perpendicular to g, which is all that branch defines.
+ * What the reference does next and this call cannot: it repropagates the window's pre_integrations with (0, Bgs[i]) (:391-394).  The
+ * solve pre-integrates from the caller's const tables imu_lin_ba / imu_lin_bg: the caller sets imu_lin_ba = 0 and
+ * imu_lin_bg[.][j] = speedbias[.][j][6..8] before the first avm_window_solve_batch.
+ * Statuses: max_frames > AVM_MAX_ALIGN_FRAMES, or more windows than avm_config::max_windows (when that is > 0): AVM_ERR_CAPACITY;
+ * n_frames / imu_n / key_index out of range or not increasing: AVM_ERR_INVALID before any kernel indexes with them.
+ * avm_last_kernel_ms keys: "align_gyro_bias", "align_solve", "align_apply". */
+int avm_visual_initial_align_batch(avm_ctx* ctx, const avm_options* opt, avm_mem mem, const avm_align_batch* align,
+                                   avm_window_batch* windows /* nullable */, avm_align_out* out);
+
 /* ---- SURVEY 8(f)4 + B4 (ground-truth mode): host-side format adapters.  Pure host bookkeeping like their
  * reference counterparts: no device work, no avm_ctx, usable without a GPU. ---------------------------------------- */
 

@@ -234,6 +234,31 @@ struct WindowTables {
   std::vector<double> zero_d_;
 };
 
+// one entry of all_image_frame (initial/initial_alignment.h:14-28): the up-to-scale SfM pose initialStructure() computed for the
+// image (estimator.cpp:288-289,342-343) and the raw IMU buffers from the previous image to this one
+struct ImageFrame {
+  std::array<double, 9> R{{1, 0, 0, 0, 1, 0, 0, 0, 1}};  // row-major; = R_c0_ck * RIC^T
+  Vector3d T{0, 0, 0};
+  bool is_key_frame = false;
+  IntegrationBase pre_integration;  // unused on the first frame of the map
+};
+
+// flat tables of all_image_frame in the layout of avm_align_batch (one window); owns the storage the batch points into
+struct AlignTables {
+  int32_t n_frames = 0;
+  int max_frames = 2, max_samp = 1;
+  std::vector<double> frame_R, frame_T, tic, imu_dt, imu_acc, imu_gyr, imu_lin_ba, imu_lin_bg;
+  std::vector<int32_t> imu_n, key_index;
+  avm_align_batch batch() {
+    avm_align_batch b{};
+    b.n_windows = 1, b.max_frames = max_frames, b.max_samp = max_samp;
+    b.n_frames = &n_frames, b.frame_R = frame_R.data(), b.frame_T = frame_T.data(), b.tic = tic.data();
+    b.imu_n = imu_n.data(), b.imu_dt = imu_dt.data(), b.imu_acc = imu_acc.data(), b.imu_gyr = imu_gyr.data();
+    b.imu_lin_ba = imu_lin_ba.data(), b.imu_lin_bg = imu_lin_bg.data(), b.key_index = key_index.data();
+    return b;
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------------
 // Estimator: the members optimization() reads and writes (estimator.h:62-115), and HP-A itself
 // ---------------------------------------------------------------------------------------------------------
@@ -255,6 +280,9 @@ class Estimator {
     }
     tic[0] = Vector3d{0, 0, 0}, ric[0] = Quaterniond{}, td = 0;
     f_manager.feature.clear();
+    all_image_frame.clear();
+    for (double& h : Headers) h = 0.0;
+    g = Vector3d{0, 0, 0};
     solver_flag = INITIAL, marginalization_flag = MARGIN_OLD;
     last_marginalization_info = MarginalizationInfo{};
     summary = avm_solve_summary{};
@@ -268,6 +296,13 @@ class Estimator {
   Quaterniond ric[1];
   double td = 0;
   FeatureManager f_manager;
+  // initialization (estimator.h:64,83,102): every image since the window began with its SfM pose and IMU buffers, the stamps of the
+  // window's frames (keys of all_image_frame), gravity in the world frame
+  std::map<double, ImageFrame> all_image_frame;
+  double Headers[AVM_NFRAMES] = {0};
+  Vector3d g{0, 0, 0};
+  Vector3d align_delta_bg{0, 0, 0};  // what the last visualInitialAlign() added to every Bgs
+  std::vector<double> align_x;       // its x: body-frame velocities of all_image_frame, then s
   IntegrationBase pre_integrations[AVM_NFRAMES];  // [j] spans frames j-1 .. j; [0] is unused by this path (estimator.cpp:702-709)
   MarginalizationInfo last_marginalization_info;
   avm_options options;        // NUM_ITERATIONS, noise densities, G, ... (parameters.cpp); marginalization_flag is set per call
@@ -464,10 +499,85 @@ class Estimator {
     }
   }
 
+  // all_image_frame + Headers + tic -> the tables of avm_align_batch
+  void marshalAlign(AlignTables& t) const {
+    const size_t F = all_image_frame.size();
+    if (F < 2) throw Error(AVM_ERR_INVALID, "all_image_frame holds fewer than two frames");
+    if (F > AVM_MAX_ALIGN_FRAMES) throw Error(AVM_ERR_CAPACITY, "all_image_frame holds more than 64 frames (AVM_MAX_ALIGN_FRAMES)");
+    size_t S = 1;
+    for (auto it = std::next(all_image_frame.begin()); it != all_image_frame.end(); ++it) S = std::max(S, it->second.pre_integration.dt_buf.size());
+    t.n_frames = (int32_t)F, t.max_frames = (int)F, t.max_samp = (int)S;
+    t.frame_R.assign(F * 9, 0.0), t.frame_T.assign(F * 3, 0.0);
+    t.tic.assign(tic[0].begin(), tic[0].end());
+    t.imu_n.assign(F - 1, 0), t.imu_dt.assign((F - 1) * S, 0.0);
+    t.imu_acc.assign((F - 1) * (S + 1) * 3, 0.0), t.imu_gyr.assign((F - 1) * (S + 1) * 3, 0.0);
+    t.imu_lin_ba.assign((F - 1) * 3, 0.0), t.imu_lin_bg.assign((F - 1) * 3, 0.0);
+    t.key_index.assign(AVM_NFRAMES, 0);
+    size_t k = 0;
+    for (auto it = all_image_frame.begin(); it != all_image_frame.end(); ++it, ++k) {
+      std::copy(it->second.R.begin(), it->second.R.end(), t.frame_R.begin() + k * 9);
+      std::copy(it->second.T.begin(), it->second.T.end(), t.frame_T.begin() + k * 3);
+      if (k == 0) continue;
+      const IntegrationBase& p = it->second.pre_integration;  // interval k - 1: frame k - 1 -> frame k
+      const size_t j = k - 1, n = p.dt_buf.size(), row0 = j * (S + 1);
+      t.imu_n[j] = (int32_t)n;
+      for (int c = 0; c < 3; c++) {
+        t.imu_acc[row0 * 3 + c] = p.linearized_acc[c], t.imu_gyr[row0 * 3 + c] = p.linearized_gyr[c];  // row 0 = the constructor's sample
+        t.imu_lin_ba[j * 3 + c] = p.linearized_ba[c], t.imu_lin_bg[j * 3 + c] = p.linearized_bg[c];
+      }
+      for (size_t s = 0; s < n; s++) {
+        t.imu_dt[j * S + s] = p.dt_buf[s];
+        for (int c = 0; c < 3; c++) t.imu_acc[(row0 + s + 1) * 3 + c] = p.acc_buf[s][c], t.imu_gyr[(row0 + s + 1) * 3 + c] = p.gyr_buf[s][c];
+      }
+    }
+    for (int i = 0; i <= AVM_WINDOW_SIZE; i++) {  // all_image_frame[Headers[i].stamp.toSec()] (estimator.cpp:370)
+      const auto it = all_image_frame.find(Headers[i]);
+      if (it == all_image_frame.end()) throw Error(AVM_ERR_INVALID, "Headers[" + std::to_string(i) + "] is not a key of all_image_frame");
+      t.key_index[i] = (int32_t)std::distance(all_image_frame.begin(), it);
+    }
+  }
+
+  // Estimator::visualInitialAlign (estimator.cpp:355-431): gyroscope bias, velocities / gravity / scale, the change of state.  Ps, Rs,
+  // Vs, Bgs, g and the feature depths come back; every Bgs carries delta_bg whatever the outcome (initial_aligment.cpp:29-30), and
+  // all_image_frame's pre-integrations are relinearized at (0, Bgs[0]) (:32-36).  On success the window's pre_integrations are
+  // relinearized at (0, Bgs[i]) (estimator.cpp:391-394: the device integrates from the linearization biases on every call) and
+  // solver_flag becomes NON_LINEAR - what processImage does with initialStructure()'s true (estimator.cpp:161-164); the rest of
+  // initialStructure (relativePose, GlobalSFM, solvePnP) is the caller's and has filled all_image_frame[.].R / .T before this call.
+  bool visualInitialAlign() {
+    AlignTables at;
+    marshalAlign(at);
+    WindowTables t;
+    marshal(t, [](const FeaturePerId& f) { return f.estimated_depth > 0 ? 1.0 / f.estimated_depth : -1.0; });
+    avm_window_batch b = t.batch(nullptr);
+    avm_align_batch ab = at.batch();
+    int32_t ok = 0;
+    double g_c0[3], g_world[3] = {0, 0, 0};
+    align_x.assign(3 * (size_t)at.max_frames + 1, 0.0);
+    avm_align_out out{};
+    out.ok = &ok, out.delta_bg = align_delta_bg.data(), out.g_c0 = g_c0, out.x = align_x.data(), out.g_world = g_world;
+    ctx_.check(avm_visual_initial_align_batch(ctx_.get(), &options, AVM_MEM_HOST, &ab, &b, &out), "avm_visual_initial_align_batch");
+    std::copy(t.pose.begin(), t.pose.end(), &para_Pose[0][0]);
+    std::copy(t.speedbias.begin(), t.speedbias.end(), &para_SpeedBias[0][0]);
+    double2vector();
+    for (auto it = std::next(all_image_frame.begin()); it != all_image_frame.end(); ++it)
+      it->second.pre_integration.linearized_ba = Vector3d{0, 0, 0}, it->second.pre_integration.linearized_bg = Bgs[0];
+    if (!ok) return false;
+    for (int i = 0; i <= AVM_WINDOW_SIZE; i++) all_image_frame[Headers[i]].is_key_frame = true;
+    int k = 0;
+    for (auto& f : f_manager.feature) {
+      if (!in_problem(f)) continue;
+      f.estimated_depth = 1.0 / t.inv_depth[k++];
+    }
+    for (int i = 0; i <= AVM_WINDOW_SIZE; i++) pre_integrations[i].linearized_ba = Vector3d{0, 0, 0}, pre_integrations[i].linearized_bg = Bgs[i];
+    g = Vector3d{g_world[0], g_world[1], g_world[2]};
+    solver_flag = NON_LINEAR;
+    return true;
+  }
+
   // Estimator::slideWindow (estimator.cpp:996-1107) with slideWindowOld / slideWindowNew and the three FeatureManager
   // remove* methods (feature_manager.cpp:275-352), for frame_count == WINDOW_SIZE: the states, the IMU buffers and EVERY
   // feature of f_manager (not only the ones that pass the solve's filter) go through avm_slide_window() and come back.
-  // Headers / all_image_frame bookkeeping is the caller's.
+  // Headers / all_image_frame bookkeeping is the caller's (visualInitialAlign() reads both).
   void slideWindow(double init_depth = 5.0) {
     vector2double();
     WindowTables t;
