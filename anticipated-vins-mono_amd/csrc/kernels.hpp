@@ -41,14 +41,20 @@ struct PreintArgs {
 };
 
 // per-slot global scratch layout (doubles), one slot per resident workgroup (stays L2 resident)
-// (one layout for both builds of the solve kernel and the marginalization kernel: the slots are shared)
+// (one layout for every build of the solve kernel and the marginalization kernel: the slots are shared.  The regions and their sizes are here, because
+//  the host sizes the slots from TOTAL; what lies inside each region is in solve/slot.hpp, which holds every layout against these sizes)
 struct Scratch {
-  static constexpr size_t PF = 0;                               // per-factor products, feature-major: [14..15 quantities][frames][152] (solve), [8 + 7][11][152] (marginalization)
-  static constexpr size_t PART = PF + 17 * (size_t)MAXOBS;       // per (frame b, start a) partial blocks: [12][11][69] + [12][35]
-  static constexpr size_t IJRAW = PART + 9600;                  // [10][15][31] IMU residual + Jacobian before sqrt_info
-  static constexpr size_t W = IJRAW + 4656;                     // E^T F, feature-major: Wt[80][152] (solve), Wt[73][152] (marginalization)
-  static constexpr size_t HP = W + (size_t)80 * 152;            // [MAXPRIOR][MAXPRIOR] J0^T J0
-  static constexpr size_t TOTAL = HP + (size_t)MAXPRIOR * MAXPRIOR;
+  static constexpr size_t PF_N = 17 * (size_t)MAXOBS;           // 17 quantities x observation slots
+  static constexpr size_t PART_N = 9600;
+  static constexpr size_t IJRAW_N = 4656;
+  static constexpr size_t W_N = (size_t)80 * 152;               // 80 columns x 152 features
+  static constexpr size_t HP_N = (size_t)MAXPRIOR * MAXPRIOR;
+  static constexpr size_t PF = 0;                               // per-factor products with Je, feature-major
+  static constexpr size_t PART = PF + PF_N;                     // partial blocks of the frame tasks
+  static constexpr size_t IJRAW = PART + PART_N;                // IMU residual + Jacobian before sqrt_info
+  static constexpr size_t W = IJRAW + IJRAW_N;                  // E^T F, feature-major
+  static constexpr size_t HP = W + W_N;                         // the prior's packed J0^T J0 and its destinations; the speculation's backup
+  static constexpr size_t TOTAL = HP + HP_N;
 };
 constexpr int ISCRATCH = MAXOBS + (NFR + 1) * MAXE;  // ints per slot: observation slot -> feature, then cov[12][150] (row 11: the relocalization frame)
 

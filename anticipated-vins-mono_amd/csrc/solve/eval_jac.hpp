@@ -43,7 +43,7 @@ AVM_NOINL double eval_jac(const WinCtx&, const avm_options&) {
 #endif
     const int i = lane;
     if (c.psum[i] <= o.max_sum_dt)
-      imu_raw<true>(xs, fr.R, o, c.pdelta + i * 10, c.pjac + i * 225, c.psum[i], c.lba + i * 3, c.lbg + i * 3, i, IJR + i * 465);
+      imu_raw<true>(xs, fr.R, o, c.pdelta + i * 10, c.pjac + i * 225, c.psum[i], c.lba + i * 3, c.lbg + i * 3, i, IJR + i * IJBLK);
   }
   // ... || the prior (dx, residual, cost, J0^T r_p) on the last wavefront, which has the lightest load of phase A
 #ifdef AVM_X
@@ -95,21 +95,21 @@ AVM_NOINL double eval_jac(const WinCtx&, const avm_options&) {
 #ifndef AVM_X
     // the partial (a,a) blocks of the frame tasks, summed further down, are requested now as well
 #ifdef AVM_TP
-    constexpr int NPR = (NFR * 27 + NT - 1) / NT;  // 297 sums on 256 threads: two rounds
+    constexpr int NPR = (NFR * SPARTW + NT - 1) / NT;  // 297 sums on 256 threads: two rounds
     double pp[NPR][NFR - 1];
 #pragma unroll
     for (int u = 0; u < NPR; u++) {
-      const int tt = min(t + u * NT, NFR * 27 - 1);
-      const int f = tt / 27, q = tt % 27;
+      const int tt = min(t + u * NT, NFR * SPARTW - 1);
+      const int f = tt / SPARTW, q = tt % SPARTW;
 #pragma unroll
-      for (int b = 1; b < NFR; b++) pp[u][b - 1] = (c.sc + Scratch::PART)[((size_t)b * NFR + f) * 27 + q];  // unconditional, masked below
+      for (int b = 1; b < NFR; b++) pp[u][b - 1] = (c.sc + Scratch::PART)[((size_t)b * NFR + f) * SPARTW + q];  // unconditional, masked below
     }
 #else
     double pp[NFR - 1];
-    if (t < NFR * 27) {
-      const int f = t / 27, q = t % 27;
+    if (t < NFR * SPARTW) {
+      const int f = t / SPARTW, q = t % SPARTW;
 #pragma unroll
-      for (int b = 1; b < NFR; b++) pp[b - 1] = (c.sc + Scratch::PART)[((size_t)b * NFR + f) * 27 + q];  // unconditional, masked below
+      for (int b = 1; b < NFR; b++) pp[b - 1] = (c.sc + Scratch::PART)[((size_t)b * NFR + f) * SPARTW + q];  // unconditional, masked below
     }
 #endif
 #endif
@@ -131,17 +131,17 @@ AVM_NOINL double eval_jac(const WinCtx&, const avm_options&) {
       const double sacc = q < 3 ? -sraw : sraw;  // (the W entries are minus the products summed here: exact)
       if (q < 6)
         W[(6 * a + q) * WLE + e] = sacc;
-      else if (q == 6)
+      else if (q == PQ_HEE)
         lds[L_HEE + e] = sacc;
-      else if (q == 7)
+      else if (q == PQ_GE)
         lds[L_G + NF + e] = sacc;
       else
-        W[(XC_EX + (q - 8)) * WLE + e] = sacc;  // E^T F of the ex_pose (6) and td (1) columns
+        W[(XC_EX + (q - PQ_JEX)) * WLE + e] = sacc;  // E^T F of the ex_pose (6) and td (1) columns
 #else
       const double sacc = q < 3 ? -(s0a + s1a) : s0a + s1a;  // (the W entries are minus the products summed here: exact)
       if (q < 6)
         W[(6 * a + q) * WLE + e] = sacc;
-      else if (q == 6)
+      else if (q == PQ_HEE)
         lds[L_HEE + e] = sacc;
       else
         lds[L_G + NF + e] = sacc;
@@ -167,15 +167,15 @@ AVM_NOINL double eval_jac(const WinCtx&, const avm_options&) {
 #pragma unroll
         for (int b = 1; b < NFRP; b++)
           if (b > f && (ids[I_PMASK + b] & (1 << f))) sacc += pp[b - 1];
-        if (q < 21) {
+        if (q < SP_GA) {
           int i = 0;
           while ((i + 1) * (i + 2) / 2 <= q) i++;
           const int j = q - i * (i + 1) / 2;
           lds[L_S + roff(6 * f + i) + 6 * f + j] += sacc * (lds[L_SC + 6 * f + i] * lds[L_SC + 6 * f + j]);
-        } else if (q < 27) {
-          lds[L_G + 6 * f + (q - 21)] += sacc;
+        } else if (q < SP_XA) {
+          lds[L_G + 6 * f + (q - SP_GA)] += sacc;
         } else {
-          lds[L_S + roff(XC_EX + (q - 27) / 6) + 6 * f + (q - 27) % 6] += sacc * (lds[L_SC + XC_EX + (q - 27) / 6] * lds[L_SC + 6 * f + (q - 27) % 6]);  // ([ex td], start pose f)
+          lds[L_S + roff(XC_EX + (q - SP_XA) / 6) + 6 * f + (q - SP_XA) % 6] += sacc * (lds[L_SC + XC_EX + (q - SP_XA) / 6] * lds[L_SC + 6 * f + (q - SP_XA) % 6]);  // ([ex td], start pose f)
         }
       } else {
         const int q = tt - NFR * SPARTW;
@@ -201,35 +201,35 @@ AVM_NOINL double eval_jac(const WinCtx&, const avm_options&) {
 #pragma unroll
     for (int u = 0; u < NPR; u++) {
       const int tt = t + u * NT;
-      if (tt >= NFR * 27) break;
-      const int f = tt / 27, q = tt % 27;
+      if (tt >= NFR * SPARTW) break;
+      const int f = tt / SPARTW, q = tt % SPARTW;
       double sacc = 0;
 #pragma unroll
       for (int b = 1; b < NFR; b++)
         if (b > f && (ids[I_PMASK + b] & (1 << f))) sacc += pp[u][b - 1];
-      if (q < 21) {
+      if (q < SP_GA) {
         int i = 0;
         while ((i + 1) * (i + 2) / 2 <= q) i++;
         const int j = q - i * (i + 1) / 2;
         lds[L_S + roff(6 * f + i) + 6 * f + j] += sacc * (lds[L_SC + 6 * f + i] * lds[L_SC + 6 * f + j]);
       } else {
-        lds[L_G + 6 * f + (q - 21)] += sacc;
+        lds[L_G + 6 * f + (q - SP_GA)] += sacc;
       }
     }
 #else
-    if (t < NFR * 27) {
-      const int f = t / 27, q = t % 27;
+    if (t < NFR * SPARTW) {
+      const int f = t / SPARTW, q = t % SPARTW;
       double sacc = 0;
 #pragma unroll
       for (int b = 1; b < NFR; b++)
         if (b > f && (ids[I_PMASK + b] & (1 << f))) sacc += pp[b - 1];
-      if (q < 21) {
+      if (q < SP_GA) {
         int i = 0;
         while ((i + 1) * (i + 2) / 2 <= q) i++;
         const int j = q - i * (i + 1) / 2;
         lds[L_S + roff(6 * f + i) + 6 * f + j] += sacc * (lds[L_SC + 6 * f + i] * lds[L_SC + 6 * f + j]);
       } else {
-        lds[L_G + 6 * f + (q - 21)] += sacc;
+        lds[L_G + 6 * f + (q - SP_GA)] += sacc;
       }
     }
 #endif

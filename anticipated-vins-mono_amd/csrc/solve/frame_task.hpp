@@ -61,7 +61,7 @@ AVM_DEV double frame_task(const WinCtx&, const avm_options&, int wvi, int stage_
     if (a_run < 0) return;
     Drun = (Drun + Drun1) + (Drun2 + Drun3);
     Drun1 = Drun2 = Drun3 = d4{0, 0, 0, 0};
-    double* PART = PART0 + (size_t)b_run * NFR * 27;
+    double* PART = PART0 + (size_t)b_run * NFR * SPARTW;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int row = drow + 4 * r;
@@ -71,8 +71,8 @@ AVM_DEV double frame_task(const WinCtx&, const avm_options&, int wvi, int stage_
         lds[L_S + roff(6 * b_run + row) + 6 * a_run + (dcol - 6)] = v * (scl[6 * b_run + row] * scl[6 * a_run + (dcol - 6)]);  // Jj^T Ji
       if (row >= 6 && row < 12) {
         const int i = row - 6;
-        if (dcol >= 6 && dcol < 12 && dcol - 6 <= i) PART[a_run * 27 + i * (i + 1) / 2 + (dcol - 6)] = v;  // Ji^T Ji (lower)
-        if (dcol == 12) PART[a_run * 27 + 21 + i] = v;                                                    // Ji^T r
+        if (dcol >= 6 && dcol < 12 && dcol - 6 <= i) PART[a_run * SPARTW + SP_AA + i * (i + 1) / 2 + (dcol - 6)] = v;  // Ji^T Ji (lower)
+        if (dcol == 12) PART[a_run * SPARTW + SP_GA + i] = v;                                                    // Ji^T r
       }
     }
     pmask |= 1 << a_run;
@@ -124,11 +124,11 @@ AVM_DEV double frame_task(const WinCtx&, const avm_options&, int wvi, int stage_
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         W[(6 * b + k) * WLE + e] = Jj[k] * Je[0] + Jj[6 + k] * Je[1];
-        if (k >= 3) PF[(k * NFR + b) * WLE + e] = Ji[k] * Je[0] + Ji[6 + k] * Je[1];
+        if (k >= 3) PF[((PQ_JI + k) * NFR + b) * WLE + e] = Ji[k] * Je[0] + Ji[6 + k] * Je[1];
       }
 #ifndef AVM_TP
-      PF[(6 * NFR + b) * WLE + e] = Je[0] * Je[0] + Je[1] * Je[1];
-      PF[(7 * NFR + b) * WLE + e] = Je[0] * r[0] + Je[1] * r[1];
+      PF[(PQ_HEE * NFR + b) * WLE + e] = Je[0] * Je[0] + Je[1] * Je[1];
+      PF[(PQ_GE * NFR + b) * WLE + e] = Je[0] * r[0] + Je[1] * r[1];
 #endif
     }
 #ifdef AVM_TP

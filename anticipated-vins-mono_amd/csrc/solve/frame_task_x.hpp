@@ -4,7 +4,7 @@
 // operand tiles), frame 11 = the relocalization frame (its "observations" are the match points, its pose relo_Pose).
 // X^T X now has three tiles: D00 = [Jj Ji r]^2 as before, D10 = [Jex Jtd]^T [Jj Ji r] and D11 = [Jex Jtd]^2.
 //   D00, per start-frame run a:  (b,a), (a,a) -> PART[b][a], g_a;        total: (b,b), g_b
-//   D10, per run:  [Jex Jtd]^T Ji -> PART[b][a][27..68];                 total: [Jex Jtd]^T Jj -> S rows 72..78 x cols 6b.. (owned by
+//   D10, per run:  [Jex Jtd]^T Ji -> PART[b][a][SP_XA..];                 total: [Jex Jtd]^T Jj -> S rows 72..78 x cols 6b.. (owned by
 //        this frame), [Jex Jtd]^T r -> PARTX[b][28..34]
 //   D11, total: -> PARTX[b][0..27]
 // Members that are switched off (estimate_extrinsic / estimate_td == 0) stage exact zeros, so their blocks come out zero.
@@ -46,10 +46,10 @@ AVM_DEV double frame_task(const WinCtx&, const avm_options&, int b, int stage_of
       if (row < 6 && dcol >= 6 && dcol < 12) lds[L_S + roff(6 * b + row) + 6 * a_run + (dcol - 6)] = v * (scl[6 * b + row] * scl[6 * a_run + (dcol - 6)]);  // Jj^T Ji (S is written Jacobi-scaled, as in the other builds)
       if (row >= 6 && row < 12) {
         const int i = row - 6;
-        if (dcol >= 6 && dcol < 12 && dcol - 6 <= i) PART[a_run * SPARTW + i * (i + 1) / 2 + (dcol - 6)] = v;  // Ji^T Ji (lower)
-        if (dcol == 12) PART[a_run * SPARTW + 21 + i] = v;                                                    // Ji^T r
+        if (dcol >= 6 && dcol < 12 && dcol - 6 <= i) PART[a_run * SPARTW + SP_AA + i * (i + 1) / 2 + (dcol - 6)] = v;  // Ji^T Ji (lower)
+        if (dcol == 12) PART[a_run * SPARTW + SP_GA + i] = v;                                                  // Ji^T r
       }
-      if (row < 7 && dcol >= 6 && dcol < 12) PART[a_run * SPARTW + 27 + row * 6 + (dcol - 6)] = D10[r];         // [Jex Jtd]^T Ji
+      if (row < 7 && dcol >= 6 && dcol < 12) PART[a_run * SPARTW + SP_XA + row * 6 + (dcol - 6)] = D10[r];      // [Jex Jtd]^T Ji
     }
     pmask |= 1 << a_run;
     Dtot += D00, D10tot += D10;
@@ -85,12 +85,12 @@ AVM_DEV double frame_task(const WinCtx&, const avm_options&, int b, int stage_of
 #pragma unroll
       for (int k = 0; k < 6; k++) {
         W[(6 * b + k) * WLE + e] = Jj[k] * Je[0] + Jj[6 + k] * Je[1];
-        if (k >= 3) PF[(k * NFRP + b) * WLE + e] = Ji[k] * Je[0] + Ji[6 + k] * Je[1];  // (k < 3: minus W's entry, see the base build's frame task)
-        PF[((8 + k) * NFRP + b) * WLE + e] = Jx[k] * Je[0] + Jx[6 + k] * Je[1];
+        if (k >= 3) PF[((PQ_JI + k) * NFRP + b) * WLE + e] = Ji[k] * Je[0] + Ji[6 + k] * Je[1];  // (k < 3: minus W's entry, see the base build's frame task)
+        PF[((PQ_JEX + k) * NFRP + b) * WLE + e] = Jx[k] * Je[0] + Jx[6 + k] * Je[1];
       }
-      PF[(6 * NFRP + b) * WLE + e] = Je[0] * Je[0] + Je[1] * Je[1];
-      PF[(7 * NFRP + b) * WLE + e] = Je[0] * r[0] + Je[1] * r[1];
-      PF[(14 * NFRP + b) * WLE + e] = Jt[0] * Je[0] + Jt[1] * Je[1];
+      PF[(PQ_HEE * NFRP + b) * WLE + e] = Je[0] * Je[0] + Je[1] * Je[1];
+      PF[(PQ_GE * NFRP + b) * WLE + e] = Je[0] * r[0] + Je[1] * r[1];
+      PF[(PQ_JTD * NFRP + b) * WLE + e] = Jt[0] * Je[0] + Jt[1] * Je[1];
     }
     // The staging tile holds HALF a chunk (lanes 0-31 stage and the wavefront multiplies, then lanes 32-63: the scheme of the throughput build
     // and of marg_frame_task).  A run that straddles the two halves simply continues: the switch below only acts on a new start frame.

@@ -14,7 +14,7 @@ AVM_DEV void imu_factor_load(int i, ImuOperands& o) {
   const WinCtx& c = lds_ctx();
   const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
   gcdouble* U = c.psqrt + i * 225;                 // upper triangular, zeros stored below the diagonal
-  gcdouble* raw = c.sc + Scratch::IJRAW + i * 465; // [15][31]: column 0 = residual, 1..30 = Jacobian
+  gcdouble* raw = c.sc + Scratch::IJRAW + i * IJBLK; // [15][31]: column 0 = residual, 1..30 = Jacobian
   const int lic = min(li, 14);
   // The combined columns are taken in the order residual | pose i | pose i + 1 | speed-bias i | speed-bias i + 1, the
   // order of the state columns themselves (12 consecutive pose columns, 18 consecutive speed-bias entries), so that the scatter of

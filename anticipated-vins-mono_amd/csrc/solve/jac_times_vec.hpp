@@ -81,7 +81,7 @@ AVM_NOINL double jac_times_vec_sq(const WinCtx&, const avm_options&) {
   double* rvb = lds + L_WCH;  // [150] (the factorization's scratch is dead here)
   if (t < 150) {
     const int i = t / 15, k = t % 15;
-    const double* IJR = c.sc + Scratch::IJRAW + i * 465;
+    const double* IJR = c.sc + Scratch::IJRAW + i * IJBLK;
     double jv[30];
 #pragma unroll
     for (int p = 0; p < 30; p++) jv[p] = IJR[k * 31 + 1 + p];

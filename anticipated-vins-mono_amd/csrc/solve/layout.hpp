@@ -157,6 +157,8 @@ constexpr int LDS_BUDGET = 163840;
 #endif
 
 // the tail all three builds share
+constexpr int ST_XE = 152;         // schur_reduce: f_e at lds[L_ST + e] and x_e beside it at lds[L_ST + ST_XE + e] (L_ST is dead during the Schur update)
+static_assert(MAXE + 2 <= ST_XE && 2 * ST_XE <= VEC, "f_e and x_e (MAXE + 2 each, the tiles' clamp included) share the step vector");
 constexpr int L_SC = L_DD + VEC;   // Jacobi scaling
 constexpr int L_X = L_SC + VEC;
 constexpr int L_FR = L_X + XN;     // [2][FRS]

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(NT) AVM_MARG_OCC void AVM_MARG_KERNEL(SolveArgs A, 
     if (t == 0) ids[I_NCOV] = 0;
     build_frames(L_X, 0);
     double* IJR = c.sc + Scratch::IJRAW;
-    for (int i = t; i < 465; i += NT) IJR[i] = 0.0;
+    for (int i = t; i < IJBLK; i += NT) IJR[i] = 0.0;
     __syncthreads();
     int nf0 = 0;  // features starting at frame 0 (they come first)
     for (int e0 = 0; e0 < c.nf; e0 += 64) nf0 += __popcll(__ballot(e0 + lane < c.nf && ids[I_FSTART + min(e0 + lane, MAXE - 1)] == 0));
@@ -184,28 +184,28 @@ __global__ __launch_bounds__(NT) AVM_MARG_OCC void AVM_MARG_KERNEL(SolveArgs A, 
       double pv[NFR - 1];
 #pragma unroll
       for (int b = 1; b < NFR; b++) pv[b - 1] = PART[(size_t)b * PARTW + q];
-      if (q < 104) {
+      if (q < MP_XB) {
         double sacc = 0;
 #pragma unroll
         for (int b = 1; b < NFR; b++) sacc += ids[I_NCOV + b] > 0 ? pv[b - 1] : 0.0;
-        if (q < 21) {
+        if (q < MP_GA) {
           int i = 0;
           while ((i + 1) * (i + 2) / 2 <= q) i++;
           lds[L_S + roff(i) + (q - i * (i + 1) / 2)] = sacc;
-        } else if (q < 27) {
-          lds[M_G + (q - 21)] = sacc;
-        } else if (q < 69) {
-          lds[L_S + roff(MEX0 + (q - 27) / 6) + (q - 27) % 6] = sacc;
-        } else if (q < 97) {
-          const int k = q - 69;
+        } else if (q < MP_XA) {
+          lds[M_G + (q - MP_GA)] = sacc;
+        } else if (q < MP_XX) {
+          lds[L_S + roff(MEX0 + (q - MP_XA) / 6) + (q - MP_XA) % 6] = sacc;
+        } else if (q < MP_GX) {
+          const int k = q - MP_XX;
           int i = 0;
           while ((i + 1) * (i + 2) / 2 <= k) i++;
           lds[L_S + roff(MEX0 + i) + MEX0 + (k - i * (i + 1) / 2)] = sacc;
         } else {
-          lds[M_G + MEX0 + (q - 97)] = sacc;
+          lds[M_G + MEX0 + (q - MP_GX)] = sacc;
         }
       } else {
-        const int k = q - 104;
+        const int k = q - MP_XB;
 #pragma unroll
         for (int b = 1; b < NFR; b++)
           if (ids[I_NCOV + b] > 0) lds[L_S + roff(MEX0 + k / 6) + 6 * b + k % 6] = pv[b - 1];

@@ -1,4 +1,4 @@
-// solve/prior_jtj.hpp - the prior's J0^T J0 on the matrix cores (prior_jtj_add_lds, prior_jtj_packed) and the layout of the per-factor products in the scratch slot
+// solve/prior_jtj.hpp - the prior's J0^T J0 on the matrix cores (prior_jtj_add_lds, prior_jtj_packed)
 // Part of window_solve.hip, which includes it inside namespace avm; no translation unit of its own.
 
 // Prior J0^T J0 on the matrix cores (16x16 tiles, K = prior rows), marginalization-kernel variant: the tiles are
@@ -40,26 +40,7 @@ AVM_NOINL void prior_jtj_add_lds(gcdouble* pJ, int ldp, int pn, int s_off) {
 
 // Solve-kernel variant: lower triangle packed by idx = p (p + 1) / 2 + q into HPk, plus the destination of every
 // entry inside the packed S (or -1 if the prior column is not a state of the solve) - the per-iteration add is then
-// a flat gather.  All operand loads of a tile are issued before the MFMA chain.
-// Layout of the solve kernel's per-factor products in the scratch slot: the FEATURE index runs fastest, so the
-// frame tasks (lane = feature) write, and the per-feature sums / Schur tiles / back substitution read, whole lines:
-//   Wt [NPOSE][WLE]       E^T F transposed: Wt[c][e] = (E^T F)[e][c]
-//   PFt[8][NFR][WLE]      per (quantity q, observing frame b, feature e): Ji^T Je (q < 6), Je^T Je, Je^T r
-constexpr int WLE = 152;
-#ifdef AVM_X
-constexpr int NQ = 15;      // per-factor quantities: Ji^T Je (6), Je^T Je, Je^T r, Jex^T Je (6), Jtd^T Je
-constexpr int SPARTW = 69;   // per (frame b, start a): Ji^T Ji (21) | Ji^T r (6) | [Jex; Jtd]^T Ji (7 x 6)
-constexpr int PARTX = 35;   // per frame b: [Jex; Jtd]^T [Jex; Jtd] lower (28) | [Jex; Jtd]^T r (7)
-constexpr int PARTX0 = NFRP * NFR * SPARTW;
-static_assert(PARTX0 + NFRP * PARTX <= 9600, "partial blocks fit the PART region");
-#else
-constexpr int NQ = 8;
-constexpr int SPARTW = 27;
-#endif
-static_assert(NQB == NQ || NQB == 6, "eval_jac's phase B sums every per-factor quantity, or (throughput build) the first six");
-static_assert(NPOSE * WLE <= 80 * 152 && NQ * NFRP * WLE <= 17 * MAXOBS, "transposed layouts fit the W / PF regions");
-constexpr int HPK_MAX = MAXPRIOR * (MAXPRIOR + 1) / 2;  // 4656 doubles, followed by 4656 ints (fits the [96][96] slot)
-static_assert(HPK_MAX + HPK_MAX / 2 <= MAXPRIOR * MAXPRIOR, "packed Hp + destinations fit the HP scratch region");
+// a flat gather (solve/slot.hpp: the HP region).  All operand loads of a tile are issued before the MFMA chain.
 AVM_NOINL void prior_jtj_packed(gcdouble* pJ, int ldp, int pn, gdouble* HPk, gint* dst) {
   const int* pidx = reinterpret_cast<const int*>(LDS() + L_INT) + I_PIDX;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;

@@ -65,7 +65,7 @@ AVM_DEV void schur_macro_tile(const WinCtx&) {
 #pragma unroll
     for (int m = 0; m < KB; m++) {
       const int el = min(e0 + 8 * lk + m, MAXE + 1);
-      fe[m] = lds[L_ST + el], xe[m] = lds[L_ST + 152 + el];
+      fe[m] = lds[L_ST + el], xe[m] = lds[L_ST + ST_XE + el];
     }
 #pragma unroll
     for (int m = 0; m < KB; m++) {
@@ -177,7 +177,7 @@ AVM_NOINL void schur_reduce(const WinCtx&, double mu) {
       const double se = scl[NF + t];
       f = se * se * d, x = se * d * lds[L_G + NF + t];
     }
-    lds[L_ST + t] = f, lds[L_ST + 152 + t] = x;
+    lds[L_ST + t] = f, lds[L_ST + ST_XE + t] = x;
   }
   __syncthreads();
 #ifdef AVM_TP

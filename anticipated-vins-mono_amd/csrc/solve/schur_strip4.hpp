@@ -41,7 +41,7 @@ AVM_DEV void schur_strip4(const WinCtx&) {
 #pragma unroll
     for (int m = 0; m < KB; m++) {
       const int el = min(e0 + 8 * lk + m, MAXE + 1);
-      fe[m] = lds[L_ST + el], xe[m] = lds[L_ST + 152 + el];
+      fe[m] = lds[L_ST + el], xe[m] = lds[L_ST + ST_XE + el];
     }
 #pragma unroll
     for (int m = 0; m < KB; m++) {

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
     // the frames that do not observe a feature) - the evaluations only ever rewrite the same nonzero entries
     {
       gdouble* IJR = c.sc + Scratch::IJRAW;
-      for (int i = t; i < 10 * 465; i += NT) IJR[i] = 0.0;
+      for (int i = t; i < (NFR - 1) * IJBLK; i += NT) IJR[i] = 0.0;
       gdouble* Wt = c.sc + Scratch::W;
       for (int idx = t; idx < c.nf * NFR; idx += NT) {
         const int f = idx / c.nf, e = idx - f * c.nf;
@@ -386,8 +386,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
     // eval_jac() stages the frame tasks' rows in the LDS range that also holds the Gauss-Newton step, the dogleg step
     // and the candidate state, so a speculative evaluation parks what a rejection needs (current point, GN step)
     // in the spare tail of the slot's prior region
-    gdouble* spec_save = c.sc + Scratch::HP + HPK_MAX + HPK_MAX / 2 + 8;
-    static_assert(HPK_MAX + HPK_MAX / 2 + 8 + XN + VEC <= MAXPRIOR * MAXPRIOR, "speculation backup fits the slot");
+    gdouble* spec_save = c.sc + Scratch::HP + HP_SPEC;
     auto spec_enter = [&]() {  // x -> backup, x <- candidate
       __syncthreads();
       for (int i = t; i < XN; i += NT) spec_save[i] = lds[L_X + i], lds[L_X + i] = lds[L_XC + i];

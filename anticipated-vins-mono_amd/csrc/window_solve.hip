@@ -49,7 +49,8 @@ namespace {
 #include "solve/context.hpp"          // address-space typedefs, WinCtx and the options in LDS, build_frames, ric_of, td_shift
 #include "solve/prior_residual.hpp"   // prior_residual_dev, prior_wave
 #include "solve/eval_cost.hpp"        // eval_cost: residual-only cost of a candidate state
-#include "solve/prior_jtj.hpp"        // prior_jtj_add_lds, the layout of the scratch slot's per-factor products, prior_jtj_packed
+#include "solve/slot.hpp"             // the map of the scratch slot: Wt / PFt, the PART rows, the raw IMU blocks, the HP region
+#include "solve/prior_jtj.hpp"        // prior_jtj_add_lds, prior_jtj_packed
 #ifndef AVM_X
 #include "solve/frame_task.hpp"       // frame_task: a wavefront's projection factors -> X^T X on the matrix cores
 #else
@@ -72,8 +73,14 @@ namespace {
 #include "solve/solve_kernel.hpp"     // the kernel: load, frame deal, TrustRegionMinimizer, gauge fix
 
 #ifndef AVM_X  // marginalization: latency and throughput builds
-#include "solve/marg.hpp"             // layout (namespace mg), assembly, elimination, eigen-decomposition, pseudo-inverse
-#include "solve/marg_kernel.hpp"      // the marginalization kernel
+#include "solve/marg_layout.hpp"        // what the marginalization computes, its map of LDS (namespace mg), mg_col
+#include "solve/marg_imu0.hpp"          // marg_imu0_raw, marg_prior_wave (phase A beside the frame tasks), marg_imu0_gram (phase D)
+#include "solve/marg_feature_sums.hpp"  // marg_feature_sums: phase B, the per-feature sums
+#include "solve/marg_schur.hpp"         // marg_schur_macro_tile, marg_schur_phase: phase F, the start-0 inverse depths eliminated
+#include "solve/marg_frame_task.hpp"    // marg_frame_task: phase A, a wavefront's projection factors -> X^T X on the matrix cores
+#include "solve/jacobi_eig_lds.hpp"     // jacobi_eig_lds<NTH>: cyclic Jacobi eigen-decomposition in LDS
+#include "solve/pinv16.hpp"             // pinv16_cholesky: the 16 x 16 pseudo-inverse when no eigenvalue is clamped
+#include "solve/marg_kernel.hpp"        // the marginalization kernel: one function, phases A to G and the output
 #endif
 
 #if defined(AVM_TP)  // each build's launchers and test exports

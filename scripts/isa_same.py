@@ -4,8 +4,8 @@ the git history)
 
     scripts/isa_same.py REV          (e.g. HEAD, HEAD~1, main)
 
-Builds window_solve.hip three ways (latency, -DAVM_X=1, -DAVM_TP=1) and fsel.hip, prior_eig.hip, preint.hip and triangulate.hip (the
-Makefile's plain FLAGS) with
+Builds window_solve.hip three ways (latency, -DAVM_X=1, -DAVM_TP=1) and fsel.hip, prior_eig.hip, preint.hip, triangulate.hip and
+visual_align.hip (the Makefile's plain FLAGS) with
 scripts/isa_mix.py's build_co() (csrc/Makefile's flags for that build plus --cuda-device-only) from `git archive REV` of csrc/ and include/ in a temporary directory and from the working tree, dumps the
 gfx950 code objects' .text, .rodata and .note sections (.note: every kernel's registers, spills, LDS and scratch) and prints one line
 per build and section with both sha256 hashes.  Exit status 1 on any difference.  (.dynstr / .strtab carry a string derived from the
@@ -28,7 +28,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_mix import CSRC, LLVM, ROOT, build_co  # noqa: E402
 
 BUILDS = [("latency", "window_solve.hip", []), ("extended", "window_solve.hip", ["-DAVM_X=1"]), ("throughput", "window_solve.hip", ["-DAVM_TP=1"]),
-          ("selector", "fsel.hip", []), ("prior_eig", "prior_eig.hip", []), ("preint", "preint.hip", []), ("triangulate", "triangulate.hip", [])]
+          ("selector", "fsel.hip", []), ("prior_eig", "prior_eig.hip", []), ("preint", "preint.hip", []), ("triangulate", "triangulate.hip", []),
+          ("visual_align", "visual_align.hip", [])]
 SECTIONS = [".text", ".rodata", ".note"]
 
 
@@ -61,7 +62,7 @@ def main():
         for sec in SECTIONS:
             old, new = res[(b, 0)][sec], res[(b, 1)][sec]
             differ += old != new
-            print("%-11s %-7s %s %s %s" % (b, sec, old[:16], new[:16], "same" if old == new else "DIFFERENT"))
+            print("%-12s %-7s %s %s %s" % (b, sec, old[:16], new[:16], "same" if old == new else "DIFFERENT"))
     sys.exit(1 if differ else 0)
 
 

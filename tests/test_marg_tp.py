@@ -52,7 +52,7 @@ def _quad(p, i):
 
 
 @pytest.mark.parametrize("flag", ["OLD", "SECOND_NEW"])
-@pytest.mark.parametrize("tracks,nf,prior", [("dense", 150, True), ("sparse", 60, True), ("sparse", 150, False), ("dense", 12, True)])
+@pytest.mark.parametrize("tracks,nf,prior", [("dense", 150, True), ("sparse", 60, True), ("sparse", 150, False), ("dense", 12, True), ("dense", 32, True), ("dense", 33, True)])
 def test_the_two_forms_of_the_marginalization_agree_to_rounding(ctx, monkeypatch, flag, tracks, nf, prior):
     """Same window, same solve (the throughput form both times), the marginalization once per form: the same kept set, and the
     same prior as far as a consumer can see it (J^T J, J^T r, |r|^2) - different accumulation orders of the same sums."""

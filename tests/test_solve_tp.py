@@ -51,7 +51,7 @@ def _solve(E, w, form, monkeypatch):
     return g, s, E.ctx.last_solve_form()
 
 
-@pytest.mark.parametrize("tracks,nf,prior", [("dense", 150, True), ("sparse", 60, True), ("sparse", 150, False), ("dense", 12, True)])
+@pytest.mark.parametrize("tracks,nf,prior", [("dense", 150, True), ("sparse", 60, True), ("sparse", 150, False), ("dense", 12, True), ("dense", 32, True), ("dense", 33, True)])
 def test_the_two_forms_of_the_solve_agree_to_rounding(estimator, monkeypatch, tracks, nf, prior):
     w = synth.make_windows(12, tracks=tracks, n_feat=nf, max_feat=150, with_prior=prior)
     g0, s0, f0 = _solve(estimator, w, "0", monkeypatch)
