@@ -264,6 +264,17 @@ class Config(C.Structure):
     ]
 
 
+# The entry points of a batch of streams (include/avm.h; lib.py sets these argtypes): per-window marginalization flags through the solve and
+# the roll, the keyframe decision, the failure detection.  ctx is a void pointer, avm_mem an int.
+PROTOTYPES = {
+    "avm_window_solve_batch_flags": [C.c_void_p, C.POINTER(Options), C.c_int, C.POINTER(WindowBatch), c_ip, C.POINTER(PriorOut),
+                                     C.POINTER(SolveSummary)],
+    "avm_slide_window_flags": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.c_int32, C.c_double, C.c_int32],
+    "avm_keyframe_decision_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.c_double, c_ip, c_ip, c_dp],
+    "avm_failure_detection_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_dp, c_ip],
+}
+
+
 def default_options() -> Options:
     """Values the reference runs with (estimator.cpp:794-806, euroc_config.yaml:54-63) + Ceres defaults.
 

@@ -140,6 +140,14 @@ const char* table_rule_text(int rule) {
   return "bad table";
 }
 
+// windows of an entry point that takes per-window marginalization flags (BAD_FLAG is the selector's BAD_FSEL number: a unit has one or the other)
+const char* solve_flag_rule_text(int rule) {
+  return rule == BAD_FLAG ? "marginalization flag must be AVM_MARGIN_OLD, AVM_MARGIN_SECOND_NEW or AVM_MARGIN_NONE" : table_rule_text(rule);
+}
+const char* roll_flag_rule_text(int rule) {
+  return rule == BAD_FLAG ? "marginalization flag must be AVM_MARGIN_OLD or AVM_MARGIN_SECOND_NEW" : table_rule_text(rule);
+}
+
 const char* align_rule_text(int rule) {
   switch (rule) {
     case BAD_ALIGN_FRAMES: return "n_frames outside [2, max_frames]";
@@ -157,7 +165,8 @@ int report_bad(avm_ctx* c, int first_bad, const char* unit, const char* (*text)(
 // ---- table checks ----
 // They run before any kernel indexes with the caller's tables: host tables are checked on the host, device-resident ones by a
 // one-thread-per-window (or per-frame) kernel.  Its verdict is a word that stays 0x7f7f7f7f while every table passes and otherwise names
-// the first window / frame that does not (8 * index + rule); the check of windows has a second word, tp_misfit.
+// the first window / frame that does not (8 * index + rule); the check of windows has a second word, tp_misfit, and with per-window
+// marginalization flags a third: which flag values occur.
 // flag_begin enqueues the check, the copy of its verdict into pinned memory and an event; flag_end waits for that event only.  What a
 // caller enqueues in between (the solve: its pre-integration, which clamps the one table entry it indexes with; the selector: the whole
 // select, whose kernels look at the device flag before they index with a table) runs while the host reads the verdict and prepares the next
@@ -170,11 +179,11 @@ struct FlagCheck {
 
 template <class Launch>
 int flag_begin(avm_ctx* c, int words, Launch launch, FlagCheck* f) {
-  int* dev = static_cast<int*>(pool_get(c, "v_flag", 2 * sizeof(int)));
-  f->host = static_cast<int*>(pool_get(c, "v_flag_h", 2 * sizeof(int), PINNED));
+  int* dev = static_cast<int*>(pool_get(c, "v_flag", 4 * sizeof(int)));
+  f->host = static_cast<int*>(pool_get(c, "v_flag_h", 4 * sizeof(int), PINNED));
   if (!dev || !f->host) return fail(c, AVM_ERR_HIP, "allocation failed (validation flag)");
   HIPCHK(c, hipMemsetAsync(dev, 0x7f, sizeof(int), c->stream));
-  if (words > 1) HIPCHK(c, hipMemsetAsync(dev + 1, 0, sizeof(int), c->stream));
+  if (words > 1) HIPCHK(c, hipMemsetAsync(dev + 1, 0, (words - 1) * sizeof(int), c->stream));
   HIPCHK(c, launch(dev));
   HIPCHK(c, hipMemcpyAsync(f->host, dev, words * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(c->ev_flag, c->stream));
@@ -197,27 +206,37 @@ int null_window_tables(avm_ctx* c, const avm_window_batch* b, int what) {
   return AVM_OK;
 }
 
-int validate_windows_begin(avm_ctx* c, const avm_window_batch* b, int what, FlagCheck* f) {
+// fr: per-window marginalization flags (device memory, like the tables) checked in the same pass; flag_end then leaves the values that occur,
+// as bits, in f->host[2]
+int validate_windows_begin(avm_ctx* c, const avm_window_batch* b, int what, FlagCheck* f, const FlagRule& fr = FlagRule()) {
   const int rc = null_window_tables(c, b, what);
   if (rc != AVM_OK) return rc;
-  return flag_begin(c, 2, [&](int* flag) { return launch_validate_windows(*b, what, flag, c->stream); }, f);
+  return flag_begin(c, fr.flags ? 3 : 2, [&](int* flag) { return launch_validate_windows(*b, what, flag, c->stream, fr); }, f);
 }
 
 // tp_misfit (optional, with CHK_PRIOR): bit 0 set when some window's prior does not fit the throughput form of the solve, bit 1 when one
 // does not fit the throughput form of the marginalization (kernels.hpp, window_prior_tp_misfit)
-int validate_windows(avm_ctx* c, avm_mem mem, const avm_window_batch* b, int what, int* tp_misfit = nullptr) {
+// fr, text, flags_seen: per-window marginalization flags (in `mem` space) checked with the tables, the messages with the flag rule's, and
+// which values occur (bit f: some window has flag f)
+int validate_windows(avm_ctx* c, avm_mem mem, const avm_window_batch* b, int what, int* tp_misfit = nullptr, const FlagRule& fr = FlagRule(),
+                     const char* (*text)(int) = table_rule_text, unsigned* flags_seen = nullptr) {
   if (tp_misfit) *tp_misfit = 0;
+  if (flags_seen) *flags_seen = 0;
   if (mem != AVM_MEM_HOST) {
     FlagCheck f;
-    const int rc = validate_windows_begin(c, b, what, &f);
-    return rc != AVM_OK ? rc : flag_end(c, f, "window", tp_misfit);
+    int rc = validate_windows_begin(c, b, what, &f, fr);
+    if (rc == AVM_OK) rc = flag_end(c, f, "window", tp_misfit, text);
+    if (rc == AVM_OK && flags_seen && fr.flags) *flags_seen = (unsigned)f.host[2];
+    return rc;
   }
   const int rc = null_window_tables(c, b, what);
   if (rc != AVM_OK) return rc;
   for (int w = 0; w < b->n_windows; w++) {
-    const int rule = check_window_tables(*b, w, what);
-    if (rule) return report_bad(c, w * 8 + rule, "window");
+    int rule = check_window_tables(*b, w, what);
+    if (!rule && fr.flags && !flag_allowed(fr, w)) rule = BAD_FLAG;
+    if (rule) return report_bad(c, w * 8 + rule, "window", text);
     if (tp_misfit && (what & CHK_PRIOR)) *tp_misfit |= window_prior_tp_misfit(*b, w);
+    if (flags_seen && fr.flags) *flags_seen |= 1u << fr.flags[w];
   }
   return AVM_OK;
 }
@@ -328,9 +347,9 @@ inline void* get_ptr(const void* s, const Field& f) {
 }
 inline void set_ptr(void* s, const Field& f, const void* p) { std::memcpy(static_cast<char*>(s) + f.offset, &p, sizeof p); }
 
-// who uses an array: the calls that take the whole batch (solve, pre-integration, factor evaluation; struct-valued outputs), and the four
-// that take a subset of the window tables
-enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32 };
+// who uses an array: the calls that take the whole batch (solve, pre-integration, factor evaluation; struct-valued outputs), and the ones
+// that take a subset of the window tables (U_KEYF: the keyframe decision, U_FAIL: the failure detection)
+enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32, U_KEYF = 64, U_FAIL = 128 };
 constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE | U_SLIDE | U_PROP;
 
 // S: the struct of the member; D, nmember: the struct the dims come from (`d` in `count`) and its batch size (`N` in `count`)
@@ -348,15 +367,15 @@ constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE
 // avm_window_batch.  The four state arrays come first so that the packed path can bring them back with one copy (N_STATES).
 #define WIN(member, type, count, in, out) FIELD(avm_window_batch, avm_window_batch, n_windows, "w_" #member, member, type, count, in, out)
 const Field WINDOW_FIELDS[] = {
-    WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
-    WIN(speedbias, double, N * 99, U_IMU | U_ALIGN, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
+    WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
+    WIN(speedbias, double, N * 99, U_IMU | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
     WIN(ex_pose, double, N * 7, U_GEOM | U_ALIGN, U_WHOLE | U_SLIDE)
     WIN(inv_depth, double, N * d.max_feat, U_GEOM | U_ALIGN, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN)
-    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN, U_SLIDE)
-    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN, U_SLIDE)
-    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN, U_SLIDE)
-    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN, U_SLIDE)
-    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN, U_SLIDE)
+    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
+    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
+    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_KEYF, U_SLIDE)
+    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
+    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
     WIN(imu_n, int32_t, N * 10, U_IMU, U_SLIDE)
     WIN(imu_dt, double, N * 10 * d.max_samp, U_IMU, U_SLIDE)
     WIN(imu_acc, double, N * 10 * (d.max_samp + 1) * 3, U_IMU, U_SLIDE)
@@ -609,7 +628,7 @@ SolveForms choose_forms(int n_windows, int n_slots, bool extended, bool marg, in
 int check_prior_out(avm_ctx* c, const avm_prior_out* po) {
   bool all = po != nullptr;
   for (const Field& f : PRIOR_OUT) all = all && get_ptr(po, f);
-  if (!all) return fail(c, AVM_ERR_INVALID, "prior_out (or one of its arrays) is NULL but marginalization_flag != AVM_MARGIN_NONE");
+  if (!all) return fail(c, AVM_ERR_INVALID, "prior_out (or one of its arrays) is NULL but marginalization_flag != AVM_MARGIN_NONE (or per-window flags are given)");
   if (po->max_prior > MAXPRIOR || po->max_prior < 1 || po->max_pblk < 1) return fail(c, AVM_ERR_CAPACITY, "prior_out dims");
   return AVM_OK;
 }
@@ -620,6 +639,7 @@ SolveArgs solve_args(const avm_ctx* c, const avm_options* opt, const avm_window_
   sa.pre_delta = c->pre_delta, sa.pre_jac = c->pre_jac, sa.pre_sqrt = c->pre_sqrt, sa.pre_sum_dt = c->pre_sum;
   sa.scratch = c->scratch, sa.iscratch = c->iscratch, sa.summary = d_sum, sa.n_slots = c->n_slots;
   sa.prof = c->prof;
+  sa.marg_flags = nullptr;  // (avm_window_solve_batch_flags sets it for the marginalization)
   // (a cap that is not finite, or beyond 1e9 s, means "no cap": the conversion to device ticks must not overflow)
   sa.time_cap_ticks = (opt->max_solver_time_s > 0.0 && opt->max_solver_time_s <= 1.0e9) ? (long long)(opt->max_solver_time_s * c->wall_clock_hz) + 1 : 0;
   const char* ns = getenv("AVM_NO_SPECULATE");
@@ -664,7 +684,10 @@ int run_marginalize(avm_ctx* c, const avm_options* opt, avm_mem mem, const Solve
   double* marg_scale = static_cast<double*>(pool_get(c, "marg_scale", sizeof(double) * B * prior_out->max_prior));
   if (!marg_scale) return fail(c, AVM_ERR_HIP, "hipMalloc failed (marginalization scales)");
   HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
-  HIPCHK(c, marg_tp ? launch_marginalize_tp(sa, dpo, *marg_err, marg_scale, c->stream) : launch_marginalize(sa, dpo, *marg_err, marg_scale, c->stream));
+  if (sa.marg_flags)  // (the flag per window: the kernels of window_solve_mm.o / window_solve_tp_mm.o)
+    HIPCHK(c, marg_tp ? launch_marginalize_tp_mixed(sa, dpo, *marg_err, marg_scale, c->stream) : launch_marginalize_mixed(sa, dpo, *marg_err, marg_scale, c->stream));
+  else
+    HIPCHK(c, marg_tp ? launch_marginalize_tp(sa, dpo, *marg_err, marg_scale, c->stream) : launch_marginalize(sa, dpo, *marg_err, marg_scale, c->stream));
   c->last_marg_tp = marg_tp;
   HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
   int* pe_done = static_cast<int*>(pool_get(c, "pe_done", sizeof(int) * B));
@@ -853,19 +876,28 @@ int avm_last_kernel_ms(const avm_ctx* c, const char* which, float* ms) {
 
 int avm_window_solve_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, const avm_window_batch* batch, avm_prior_out* prior_out,
                            avm_solve_summary* summary) {
+  return avm_window_solve_batch_flags(c, opt, mem, batch, nullptr, prior_out, summary);
+}
+
+int avm_window_solve_batch_flags(avm_ctx* c, const avm_options* opt, avm_mem mem, const avm_window_batch* batch, const int32_t* flags,
+                                 avm_prior_out* prior_out, avm_solve_summary* summary) {
   if (!c) return AVM_ERR_INVALID;
   (void)hipSetDevice(c->device);
   int rc = check_window_batch(c, opt, batch);
   if (rc != AVM_OK) return rc;
-  const bool marg = opt->marginalization_flag != AVM_MARGIN_NONE;
+  // (with per-window flags the forms and the buffers are chosen as for a marginalizing batch: which values occur is known after the check)
+  bool marg = flags || opt->marginalization_flag != AVM_MARGIN_NONE;
   if (marg && (rc = check_prior_out(c, prior_out)) != AVM_OK) return rc;
   if (batch->n_windows == 0) return AVM_OK;
   // table check: host tables on the host, now; device-resident ones by a kernel whose verdict is read while the pre-integration runs.
-  // On the early error paths below a check in flight is drained before the caller may free its tables.
+  // On the early error paths below a check in flight is drained before the caller may free its tables.  The per-window flags are checked
+  // in the same pass: no kernel reads a flag before the verdict is in.
   int tp_misfit = 0;
+  unsigned flags_seen = 0;
   FlagCheck check;
-  rc = mem == AVM_MEM_HOST ? validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &tp_misfit)
-                           : validate_windows_begin(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &check);
+  const FlagRule fr{flags, (1u << AVM_MARGIN_OLD) | (1u << AVM_MARGIN_SECOND_NEW) | (1u << AVM_MARGIN_NONE)};
+  rc = mem == AVM_MEM_HOST ? validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &tp_misfit, fr, solve_flag_rule_text, &flags_seen)
+                           : validate_windows_begin(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &check, fr);
   if (rc != AVM_OK) return rc;
 
   // choose forms (the slots for the throughput forms are sized before the priors' verdict is in: a batch that then takes the latency forms uses half of them)
@@ -893,7 +925,8 @@ int avm_window_solve_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, cons
     return rc;
   }
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  if (check.dev && (rc = flag_end(c, check, "window", &tp_misfit)) != AVM_OK) return rc;
+  if (check.dev && (rc = flag_end(c, check, "window", &tp_misfit, solve_flag_rule_text)) != AVM_OK) return rc;
+  if (check.dev && flags) flags_seen = (unsigned)check.host[2];
   forms = choose_forms(batch->n_windows, c->n_slots, extended, marg, tp_misfit);
 
   // solve
@@ -901,9 +934,24 @@ int avm_window_solve_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, cons
   if ((rc = run_solve(c, sa, extended, forms)) != AVM_OK) return rc;
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
 
-  // marginalize and take the square root
+  // marginalize and take the square root.  Per-window flags that are all AVM_MARGIN_NONE: no launch, every window reports n = -1
   int* marg_err = nullptr;
   PackedBack prior_back;
+  if (flags && flags_seen == 1u << AVM_MARGIN_NONE) {
+    marg = false;
+    const size_t nb = sizeof(int32_t) * batch->n_windows;
+    if (mem == AVM_MEM_HOST) {
+      std::memset(prior_out->n, 0xff, nb), std::memset(prior_out->nblk, 0, nb);
+    } else {
+      HIPCHK(c, hipMemsetAsync(prior_out->n, 0xff, nb, c->stream));
+      HIPCHK(c, hipMemsetAsync(prior_out->nblk, 0, nb, c->stream));
+    }
+  }
+  if (marg && flags) {
+    const void* dflags = flags;
+    if (mem == AVM_MEM_HOST && (rc = stage_array(c, "w_marg_flags", flags, sizeof(int32_t) * batch->n_windows, &dflags)) != AVM_OK) return rc;
+    sa.marg_flags = static_cast<const int32_t*>(dflags);
+  }
   if (marg && (rc = run_marginalize(c, opt, mem, sa, forms.marg_tp, prior_out, &marg_err, &prior_back)) != AVM_OK) return rc;
 
   // return outputs: the states (a packed batch: its four head blocks as one copy), para_Td / relo_Pose, the summaries - one synchronize
@@ -1137,25 +1185,111 @@ int avm_visual_initial_align_batch(avm_ctx* c, const avm_options* opt, avm_mem m
   return AVM_OK;
 }
 
+namespace {
+// the roll: flags ([B], in `mem` space) per window, or flags == null and `flag` for every window
+int slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, const int32_t* flags, int32_t flag, int32_t shift_depth, double init_depth,
+                 int32_t remove_failures) {
+  if (batch->n_windows == 0) return AVM_OK;
+  // (the flags are checked with the tables, before the kernel reads either)
+  const FlagRule fr{flags, (1u << AVM_MARGIN_OLD) | (1u << AVM_MARGIN_SECOND_NEW)};
+  int rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU, nullptr, fr, roll_flag_rule_text);
+  if (rc != AVM_OK) return rc;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_SLIDE, batch, &d)) != AVM_OK) return rc;
+  const void* dflags = flags;
+  if (flags && mem == AVM_MEM_HOST && (rc = stage_array(c, "w_roll_flags", flags, sizeof(int32_t) * batch->n_windows, &dflags)) != AVM_OK) return rc;
+  int* derr = static_cast<int*>(pool_get(c, "slide_err", sizeof(int)));
+  if (!derr) return fail(c, AVM_ERR_HIP, "hipMalloc failed (slide flag)");
+  HIPCHK(c, hipMemsetAsync(derr, 0, sizeof(int), c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_slide_window(d, static_cast<const int32_t*>(dflags), flag, shift_depth, init_depth, remove_failures, derr, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  int herr = 0;
+  HIPCHK(c, hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = copy_back(c, mem, WINDOWS, U_SLIDE, batch, &d, batch)) != AVM_OK) return rc;  // (everything the roll rewrites)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["slide_window"] = ms;
+  if (herr) return fail(c, AVM_ERR_CAPACITY, "MARGIN_SECOND_NEW: interval 8 + interval 9 exceed max_samp samples");
+  return AVM_OK;
+}
+}  // namespace
+
 int avm_slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, int32_t flag, int32_t shift_depth, double init_depth) {
   if (!c) return AVM_ERR_INVALID;
   (void)hipSetDevice(c->device);
   if (!batch || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   if (flag != AVM_MARGIN_OLD && flag != AVM_MARGIN_SECOND_NEW) return fail(c, AVM_ERR_INVALID, "marginalization_flag must be MARGIN_OLD or MARGIN_SECOND_NEW");
-  if (batch->n_windows == 0) return AVM_OK;
-  int rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU);
+  return slide_window(c, mem, batch, nullptr, flag, shift_depth, init_depth, 0);
+}
+
+int avm_slide_window_flags(avm_ctx* c, avm_mem mem, avm_window_batch* batch, const int32_t* flags, int32_t shift_depth, double init_depth,
+                           int32_t remove_failures) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!batch || !flags || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  return slide_window(c, mem, batch, flags, AVM_MARGIN_OLD, shift_depth, init_depth, remove_failures);
+}
+
+int avm_keyframe_decision_batch(avm_ctx* c, avm_mem mem, const avm_window_batch* batch, double min_parallax, int32_t* flags, int32_t* last_track_num,
+                                double* parallax) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!batch || !flags || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (!batch->obs_xy) return fail(c, AVM_ERR_INVALID, "null obs_xy");
+  int rc = check_wide_strides(c, batch);  // (the API's table contract: the kernel walks the list in chunks, any count)
   if (rc != AVM_OK) return rc;
+  if (batch->n_windows == 0) return AVM_OK;
+  if ((rc = validate_windows(c, mem, batch, CHK_TRACKS)) != AVM_OK) return rc;
   avm_window_batch d;
-  if ((rc = on_device(c, mem, WINDOWS, U_SLIDE, batch, &d)) != AVM_OK) return rc;
-  int* derr = static_cast<int*>(pool_get(c, "slide_err", sizeof(int)));
-  if (!derr) return fail(c, AVM_ERR_HIP, "hipMalloc failed (slide flag)");
-  HIPCHK(c, hipMemsetAsync(derr, 0, sizeof(int), c->stream));
-  HIPCHK(c, launch_slide_window(d, flag, shift_depth, init_depth, derr, c->stream));
-  int herr = 0;
-  HIPCHK(c, hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if ((rc = copy_back(c, mem, WINDOWS, U_SLIDE, batch, &d, batch)) != AVM_OK) return rc;  // (everything the roll rewrites)
+  if ((rc = on_device(c, mem, WINDOWS, U_KEYF, batch, &d)) != AVM_OK) return rc;
+  const size_t B = batch->n_windows;
+  int32_t *dflags = flags, *dltn = last_track_num;
+  double* dpar = parallax;
+  if (mem == AVM_MEM_HOST) {
+    dflags = static_cast<int32_t*>(pool_get(c, "k_flags", sizeof(int32_t) * B));
+    dltn = last_track_num ? static_cast<int32_t*>(pool_get(c, "k_ltn", sizeof(int32_t) * B)) : nullptr;
+    dpar = parallax ? static_cast<double*>(pool_get(c, "k_par", sizeof(double) * B * 2)) : nullptr;
+    if (!dflags || (last_track_num && !dltn) || (parallax && !dpar)) return fail(c, AVM_ERR_HIP, "hipMalloc failed (keyframe decision out)");
+  }
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_keyframe_decision(d, min_parallax, dflags, dltn, dpar, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if (mem == AVM_MEM_HOST) {
+    HIPCHK(c, hipMemcpyAsync(flags, dflags, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
+    if (last_track_num) HIPCHK(c, hipMemcpyAsync(last_track_num, dltn, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
+    if (parallax) HIPCHK(c, hipMemcpyAsync(parallax, dpar, sizeof(double) * B * 2, hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (herr) return fail(c, AVM_ERR_CAPACITY, "MARGIN_SECOND_NEW: interval 8 + interval 9 exceed max_samp samples");
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["keyframe_decision"] = ms;
+  return AVM_OK;
+}
+
+int avm_failure_detection_batch(avm_ctx* c, avm_mem mem, const avm_window_batch* batch, const double* last_P, int32_t* failed) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!batch || !last_P || !failed || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (!batch->pose || !batch->speedbias) return fail(c, AVM_ERR_INVALID, "null pose / speedbias");
+  if (batch->n_windows == 0) return AVM_OK;
+  int rc;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_FAIL, batch, &d)) != AVM_OK) return rc;
+  const size_t B = batch->n_windows;
+  const void* dlp = last_P;
+  int32_t* dfailed = failed;
+  if (mem == AVM_MEM_HOST) {
+    if ((rc = stage_array(c, "fd_last_P", last_P, sizeof(double) * B * 3, &dlp)) != AVM_OK) return rc;
+    dfailed = static_cast<int32_t*>(pool_get(c, "fd_failed", sizeof(int32_t) * B));
+    if (!dfailed) return fail(c, AVM_ERR_HIP, "hipMalloc failed (failure detection out)");
+  }
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_failure_detection(d, static_cast<const double*>(dlp), dfailed, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if (mem == AVM_MEM_HOST) HIPCHK(c, hipMemcpyAsync(failed, dfailed, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["failure_detection"] = ms;
   return AVM_OK;
 }
 

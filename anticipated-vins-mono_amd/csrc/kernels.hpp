@@ -70,6 +70,7 @@ struct SolveArgs {
   long long* prof;  // optional [n_slots][PROF_SLOTS] per-phase shader-clock accumulators (debug)
   int speculate;    // 1: evaluate the Jacobian at the candidate directly while steps keep being accepted (solve/solve_kernel.hpp)
   long long time_cap_ticks;  // avm_options::max_solver_time_s in ticks of the device wall clock (wall_clock64); 0 = no cap
+  const int32_t* marg_flags;  // [B] device, or null: every window takes opt.marginalization_flag (read by the -DAVM_MARG_MIXED marginalization kernels only)
 };
 
 struct EvalArgs {
@@ -95,6 +96,18 @@ struct FselBuffers {
 enum { CHK_TRACKS = 1, CHK_IMU = 2, CHK_PRIOR = 4 };
 // 0 = fine; otherwise the first violated rule (messages in avm_api.hip, table_rule_text)
 enum { BAD_NFEAT = 1, BAD_TRACK = 2, BAD_ORDER = 3, BAD_OBS = 4, BAD_IMU = 5, BAD_PRIOR = 6, BAD_FSEL = 7 };
+constexpr int BAD_FLAG = 7;  // (windows; BAD_FSEL is the selector frames' only rule) a per-window marginalization flag outside the set the entry point takes
+
+// The per-window marginalization flags of an entry point, checked in the same pass as the tables: `allowed` has bit f set for every
+// value f the entry point takes.  flags == null: nothing to check.
+struct FlagRule {
+  const int32_t* flags = nullptr;
+  unsigned allowed = 0;
+};
+__host__ __device__ inline bool flag_allowed(const FlagRule& fr, int w) {
+  const int f = fr.flags[w];
+  return f >= 0 && f < 32 && ((fr.allowed >> f) & 1u);
+}
 
 // The lowest-numbered violated rule of window w (0 = fine), looking at features e = first, first + stride, ... only, so
 // that the host (first 0, stride 1) and a wavefront (first = lane, stride 64, then a min over the lanes) agree.
@@ -221,9 +234,10 @@ hipError_t launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, 
   return launch_lds_below<Kernel>(grid, block, lds_bytes, lds_bytes, stream, args...);
 }
 
-// first_bad: TWO ints.  [0]: INT_MAX when every window / problem passes, else (index * 8 + rule) of the lowest failing index;
-// [1] (windows, with CHK_PRIOR): the OR of window_prior_tp_misfit() over the windows (left alone when every prior fits)
-hipError_t launch_validate_windows(const avm_window_batch& b, int what, int* first_bad, hipStream_t stream);
+// first_bad: THREE ints.  [0]: INT_MAX when every window / problem passes, else (index * 8 + rule) of the lowest failing index;
+// [1] (windows, with CHK_PRIOR): the OR of window_prior_tp_misfit() over the windows (left alone when every prior fits);
+// [2] (windows, with flags): the OR of 1 << flag over the windows whose flag is allowed
+hipError_t launch_validate_windows(const avm_window_batch& b, int what, int* first_bad, hipStream_t stream, const FlagRule& fr = FlagRule());
 hipError_t launch_validate_fsel(const avm_fsel_batch& b, int* first_bad, hipStream_t stream);
 
 void launch_preint(const PreintArgs& a, hipStream_t stream);
@@ -238,7 +252,14 @@ hipError_t launch_fsel_horizon_imu(const avm_fsel_horizon_in& in, double* hor_po
 // zero_tic: triangulate on the camera positions themselves (visualInitialAlign, estimator.cpp:383-388); only: optional [B] device mask, windows with 0 are left alone
 hipError_t launch_triangulate(const avm_window_batch& b, double init_depth, hipStream_t stream, int zero_tic = 0, const int32_t* only = nullptr);
 hipError_t launch_imu_propagate(const avm_window_batch& b, const double* g, hipStream_t stream);
-hipError_t launch_slide_window(const avm_window_batch& b, int flag, int shift_depth, double init_depth, int* err, hipStream_t stream);
+// flags: [B] device, or null: every window takes `flag`; remove_failures: FeatureManager::removeFailures() behind the roll
+hipError_t launch_slide_window(const avm_window_batch& b, const int32_t* flags, int flag, int shift_depth, double init_depth, int remove_failures,
+                               int* err, hipStream_t stream);
+// FeatureManager::addFeatureCheckParallax's return value per window; last_track_num / parallax ([B][2]: sum, num) may be null
+hipError_t launch_keyframe_decision(const avm_window_batch& b, double min_parallax, int32_t* flags, int32_t* last_track_num, double* parallax,
+                                    hipStream_t stream);
+// Estimator::failureDetection per window: failed[w] = 0, or the number of the first rule that fired
+hipError_t launch_failure_detection(const avm_window_batch& b, const double* last_P, int32_t* failed, hipStream_t stream);
 hipError_t launch_projection_td_eval(const avm_td_factor_batch& f, double* residual, double* jac, hipStream_t stream);
 hipError_t launch_window_solve(const SolveArgs& a, hipStream_t stream);
 hipError_t launch_window_solve_x(const SolveArgs& a, hipStream_t stream);  // window_solve_x.o: estimate_extrinsic / estimate_td / relocalization
@@ -254,6 +275,9 @@ hipError_t launch_eval_factors(const EvalArgs& a, hipStream_t stream);
 hipError_t launch_marginalize(const SolveArgs& a, const avm_prior_out& po, int* err, double* scale, hipStream_t stream);
 // window_solve_tp.o: the same marginalization as two 256-thread workgroups per CU (a.n_slots = the throughput solve's 2 x CUs slots)
 hipError_t launch_marginalize_tp(const SolveArgs& a, const avm_prior_out& po, int* err, double* scale, hipStream_t stream);
+// window_solve_mm.o / window_solve_tp_mm.o: the same two with the flag per window, a.marg_flags[w] (solve/marg_kernel.hpp, AVM_MARG_MIXED)
+hipError_t launch_marginalize_mixed(const SolveArgs& a, const avm_prior_out& po, int* err, double* scale, hipStream_t stream);
+hipError_t launch_marginalize_tp_mixed(const SolveArgs& a, const avm_prior_out& po, int* err, double* scale, hipStream_t stream);
 // second half of the marginalization: eigen-decomposition of A' (left in po.J / po.r by launch_marginalize) -> sqrt prior
 // noise_rel: avm_options::marg_noise_rel (0 = the reference-literal clamp S > eps and nothing else)
 hipError_t launch_prior_eig(const avm_prior_out& po, int n_windows, double eps, double noise_rel, const double* scale, long long* prof,

@@ -1,10 +1,24 @@
 // solve/marg_kernel.hpp - the marginalization kernel
 // Part of window_solve.hip, which includes it inside namespace avm; no translation unit of its own.
+// -DAVM_MARG_MIXED (window_solve_mm.o, window_solve_tp_mm.o: this kernel and nothing else): the marginalization flag PER WINDOW,
+// A.marg_flags[w] read inside the window loop, for avm_window_solve_batch_flags.  The flag is still the same for every thread of a
+// workgroup, like the `continue` of "MARGIN_SECOND_NEW had nothing to drop", and AVM_MARGIN_NONE is that same report: the caller keeps
+// the prior it had.  A build of its own and not a null test in the one kernel: these bodies use the whole register file, and with a flag
+// that varies from window to window the latency form makes three more trips to spill memory per window (scripts/isa_spill_trips.py: 22
+// against 19).  The launch with one flag for the batch keeps the code it had.
 #ifdef AVM_TP
+#ifdef AVM_MARG_MIXED
+#define AVM_MARG_KERNEL marginalize_tp_mixed_kernel
+#else
 #define AVM_MARG_KERNEL marginalize_tp_kernel
+#endif
 #define AVM_MARG_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))  // two four-wavefront workgroups per CU, like the solve beside it
 #else
+#ifdef AVM_MARG_MIXED
+#define AVM_MARG_KERNEL marginalize_mixed_kernel
+#else
 #define AVM_MARG_KERNEL marginalize_kernel
+#endif
 #define AVM_MARG_OCC
 #endif
 __global__ __launch_bounds__(NT) AVM_MARG_OCC void AVM_MARG_KERNEL(SolveArgs A, avm_prior_out PO, int* err, double* scale_out) {
@@ -16,8 +30,16 @@ __global__ __launch_bounds__(NT) AVM_MARG_OCC void AVM_MARG_KERNEL(SolveArgs A, 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const avm_options& o = lds_opt();
   const avm_window_batch& B = A.b;
+#ifndef AVM_MARG_MIXED
   const int flag = A.opt.marginalization_flag;
+#endif
   for (int w = blockIdx.x; w < B.n_windows; w += gridDim.x) {
+#ifdef AVM_MARG_MIXED
+    const int flag = A.marg_flags[w];
+    const bool not_marginalized = flag == AVM_MARGIN_NONE;
+#else
+    constexpr bool not_marginalized = false;
+#endif
     WinCtx cl;
     cl.prof = A.prof ? as_global(A.prof + (size_t)blockIdx.x * PROF_SLOTS) : nullptr;
     cl.sc = as_global(A.scratch + (size_t)blockIdx.x * Scratch::TOTAL);
@@ -105,7 +127,7 @@ __global__ __launch_bounds__(NT) AVM_MARG_OCC void AVM_MARG_KERNEL(SolveArgs A, 
     bool has9 = false;
     for (int k = 0; k < c.pnblk; k++)
       if (ids[I_PBLK + k * 3] == AVM_BLK_POSE && ids[I_PBLK + k * 3 + 1] == AVM_WINDOW_SIZE - 1) has9 = true;
-    if (flag == AVM_MARGIN_SECOND_NEW && !(use_prior && has9)) {
+    if (not_marginalized || (flag == AVM_MARGIN_SECOND_NEW && !(use_prior && has9))) {
       if (t == 0) PO.n[w] = -1, PO.nblk[w] = 0;  // nothing to do: the caller keeps the old prior
       continue;
     }

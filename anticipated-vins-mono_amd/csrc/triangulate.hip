@@ -163,8 +163,14 @@ hipError_t launch_imu_propagate(const avm_window_batch& b, const double* g, hipS
 // ---- 8(f)2: Estimator::slideWindow (estimator.cpp:996-1107) + removeBackShiftDepth / removeBack / removeFront
 // (feature_manager.cpp:275-352), in place.  One wavefront per window: the lanes move the frame / IMU arrays, lane 0 walks
 // the feature list (order-preserving compaction of <= 150 entries: not worth a scan).
-__global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, int flag, int shift_depth, double init_depth, int* err) {
+// flags: the flag per window (null: `flag_all` for every window; the wavefront is the window, so the flag is uniform in it).
+// remove_failures: f_manager.removeFailures() behind the roll (estimator.cpp:197-198): a feature that went through the solve's filter
+// with a negative inverse depth - setDepth's solve_flag == 2, feature_manager.cpp:141-159, decided on the tables as they are BEFORE
+// the roll - is erased, whatever the roll did to it.
+__global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, const int32_t* flags, int flag_all, int shift_depth, double init_depth,
+                                                          int remove_failures, int* err) {
   const int w = blockIdx.x, lane = threadIdx.x;
+  const int flag = flags ? flags[w] : flag_all;
   double* pose = B.pose + (size_t)w * NFR * 7;
   double* sb = B.speedbias + (size_t)w * NFR * 9;
   int32_t* imu_n = const_cast<int32_t*>(B.imu_n) + (size_t)w * 10;
@@ -238,6 +244,7 @@ __global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, in
   for (int e = 0; e < nf; e++) {
     int st = fstart[e], no = fnobs[e], ob = fobs[e];
     double l = lam[e];
+    const bool failure = remove_failures && no >= 2 && st < AVM_WINDOW_SIZE - 2 && l < 0.0;
     bool keep = true;
     if (flag == AVM_MARGIN_OLD) {
       if (st != 0) {
@@ -269,22 +276,106 @@ __global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, in
         if (no == 0) keep = false;
       }
     }
-    if (keep) fstart[o] = st, fnobs[o] = no, fobs[o] = ob, lam[o] = l, o++;
+    if (keep && !failure) fstart[o] = st, fnobs[o] = no, fobs[o] = ob, lam[o] = l, o++;
   }
   *n_feat = o;
 }
 
-hipError_t launch_slide_window(const avm_window_batch& b, int flag, int shift_depth, double init_depth, int* err, hipStream_t stream) {
+hipError_t launch_slide_window(const avm_window_batch& b, const int32_t* flags, int flag, int shift_depth, double init_depth, int remove_failures,
+                               int* err, hipStream_t stream) {
   if (b.n_windows == 0) return hipSuccess;
-  hipLaunchKernelGGL(slide_window_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, flag, shift_depth, init_depth, err);
+  hipLaunchKernelGGL(slide_window_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, flags, flag, shift_depth, init_depth, remove_failures, err);
+  return hipGetLastError();
+}
+
+// ---- FeatureManager::addFeatureCheckParallax's return value (feature_manager.cpp:74-96, compensatedParallax2 :355-388) for
+// frame_count == WINDOW_SIZE, on tables that already hold the new image's observations.  One wavefront per window: the lanes compute the
+// terms of a 64-feature chunk side by side, the terms are then added in list order, one after the other, as the reference's loop does - the
+// decision is a comparison of that sum, so its arithmetic is the reference's: no contraction into FMAs (the reference's x86 build has
+// none), a correctly rounded square root, one division.
+__global__ __launch_bounds__(64) void keyframe_decision_kernel(avm_window_batch B, double min_parallax, int32_t* flags, int32_t* last_track_num,
+                                                               double* parallax) {
+#pragma clang fp contract(off)
+  const int w = blockIdx.x, lane = threadIdx.x;
+  const int nf = B.n_feat[w];
+  const int32_t* fstart = B.feat_start + (size_t)w * B.max_feat;
+  const int32_t* fnobs = B.feat_nobs + (size_t)w * B.max_feat;
+  const int32_t* fobs = B.feat_obs_begin + (size_t)w * B.max_feat;
+  const double* obs = B.obs_xy + (size_t)w * B.max_obs * 2;
+  int tracked = 0, num = 0;
+  double sum = 0.0;
+  for (int e0 = 0; e0 < nf; e0 += 64) {
+    const int e = e0 + lane;
+    const bool in = e < nf;
+    const int st = in ? fstart[e] : 0, no = in ? fnobs[e] : 0, ob = in ? fobs[e] : 0;
+    // (a feature the new image extended: it has an observation in frame 10 and one before it)
+    tracked += __popcll(__ballot(in && no >= 2 && st + no - 1 == NFR - 1));
+    // start_frame <= frame_count - 2 && endFrame() >= frame_count - 1
+    const bool span = in && st <= NFR - 3 && st + no - 1 >= NFR - 2;
+    double term = 0.0;
+    if (span) {
+      const double* pi = obs + 2 * (size_t)(ob + (NFR - 3 - st));  // frame 8, frame 9 behind it
+      // (p(2) == 1: u_i = p_i(0) / 1, and the "compensated" pair is the same number; min(a, a) = a)
+      const double du = pi[0] - pi[2], dv = pi[1] - pi[3];
+      const double len = __dsqrt_rn(du * du + dv * dv);
+      term = 0.0 < len ? len : 0.0;  // max(ans = 0, .)
+    }
+    unsigned long long m = __ballot(span);
+    num += __popcll(m);
+    while (m) {  // (m is the wavefront's: every lane adds the same terms in the same order)
+      const int l = __ffsll((long long)m) - 1;
+      sum += __shfl(term, l, 64);
+      m &= m - 1;
+    }
+  }
+  if (lane != 0) return;
+  int keyframe = 1;  // return true: MARGIN_OLD
+  if (tracked >= 20 && num > 0) keyframe = sum / num >= min_parallax;
+  flags[w] = keyframe ? AVM_MARGIN_OLD : AVM_MARGIN_SECOND_NEW;
+  if (last_track_num) last_track_num[w] = tracked;
+  if (parallax) parallax[2 * (size_t)w] = sum, parallax[2 * (size_t)w + 1] = num;
+}
+
+hipError_t launch_keyframe_decision(const avm_window_batch& b, double min_parallax, int32_t* flags, int32_t* last_track_num, double* parallax,
+                                    hipStream_t stream) {
+  if (b.n_windows == 0) return hipSuccess;
+  hipLaunchKernelGGL(keyframe_decision_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, min_parallax, flags, last_track_num, parallax);
+  return hipGetLastError();
+}
+
+// ---- Estimator::failureDetection (estimator.cpp:612-658): the rules that return true, in the reference's order; one thread per window.
+__global__ __launch_bounds__(TRI_NT) void failure_detection_kernel(avm_window_batch B, const double* last_P, int32_t* failed) {
+#pragma clang fp contract(off)
+  const int w = blockIdx.x * TRI_NT + threadIdx.x;
+  if (w >= B.n_windows) return;
+  const double* sb = B.speedbias + ((size_t)w * NFR + (NFR - 1)) * 9;
+  const double* P = B.pose + ((size_t)w * NFR + (NFR - 1)) * 7;
+  const double* lp = last_P + 3 * (size_t)w;
+  auto norm = [](double x, double y, double z) { return __dsqrt_rn(x * x + y * y + z * z); };
+  const double dx = P[0] - lp[0], dy = P[1] - lp[1], dz = P[2] - lp[2];
+  int rule = 0;
+  if (norm(sb[3], sb[4], sb[5]) > 2.5) rule = 1;        // Bas[WINDOW_SIZE].norm() > 2.5
+  else if (norm(sb[6], sb[7], sb[8]) > 1.0) rule = 2;   // Bgs[WINDOW_SIZE].norm() > 1.0
+  else if (norm(dx, dy, dz) > 5.0) rule = 3;            // (tmp_P - last_P).norm() > 5
+  else if (fabs(dz) > 1.0) rule = 4;                    // abs(tmp_P.z() - last_P.z()) > 1
+  failed[w] = rule;
+}
+
+hipError_t launch_failure_detection(const avm_window_batch& b, const double* last_P, int32_t* failed, hipStream_t stream) {
+  if (b.n_windows == 0) return hipSuccess;
+  hipLaunchKernelGGL(failure_detection_kernel, dim3((b.n_windows + TRI_NT - 1) / TRI_NT), dim3(TRI_NT), 0, stream, b, last_P, failed);
   return hipGetLastError();
 }
 
 // ---- table validation: one wavefront per window (one thread per selector frame), the lowest failing index wins ------------------------------
-__global__ __launch_bounds__(64) void validate_windows_kernel(avm_window_batch B, int what, int* first_bad) {
+__global__ __launch_bounds__(64) void validate_windows_kernel(avm_window_batch B, int what, int* first_bad, FlagRule fr) {
   const int w = blockIdx.x, lane = threadIdx.x;  // one wavefront per window, lane = feature (mod 64)
   int rule = check_window_tables(B, w, what, lane, 64);
   rule = rule ? rule : 1 << 30;
+  if (lane == 0 && fr.flags) {  // the window's marginalization flag: the highest-numbered rule
+    if (!flag_allowed(fr, w)) rule = min(rule, BAD_FLAG);
+    else atomicOr(first_bad + 2, 1 << fr.flags[w]);
+  }
   for (int o = 32; o > 0; o >>= 1) rule = min(rule, __shfl_xor(rule, o, 64));
   if (lane == 0 && rule != 1 << 30) atomicMin(first_bad, w * 8 + rule);
   // (only for a window whose prior tables passed: the count below indexes with them)
@@ -301,8 +392,8 @@ __global__ __launch_bounds__(64) void validate_fsel_kernel(avm_fsel_batch b, int
   if (rule) atomicMin(first_bad, p * 8 + rule);
 }
 
-hipError_t launch_validate_windows(const avm_window_batch& b, int what, int* first_bad, hipStream_t stream) {
-  hipLaunchKernelGGL(validate_windows_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, what, first_bad);
+hipError_t launch_validate_windows(const avm_window_batch& b, int what, int* first_bad, hipStream_t stream, const FlagRule& fr) {
+  hipLaunchKernelGGL(validate_windows_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, what, first_bad, fr);
   return hipGetLastError();
 }
 

@@ -28,6 +28,8 @@
 //                       also marginalize_kernel and eval_factors_kernel
 //   window_solve_x.o    -DAVM_X, extended build: the same with ex_pose / td / relo_Pose as variables (178 x 178 system); the solve only
 //   window_solve_tp.o   -DAVM_TP, throughput build: 256 threads and <= 80 KB of LDS, two windows per CU; solve and marginalization
+//   window_solve_mm.o, window_solve_tp_mm.o   -DAVM_MARG_MIXED [-DAVM_TP]: the marginalization kernel of the latency / throughput build once
+//                       more, with the marginalization flag per window (solve/marg_kernel.hpp); no solve kernel
 // This file is the table of contents: every function and kernel is in a part under solve/, included below in DEFINITION ORDER, which
 // is the order the compiler emits the functions in - moving an include moves code.  A part that all three builds share carries their
 // differences inside its functions under #ifdef AVM_X / AVM_TP; a part that only some builds have sits behind a conditional include
@@ -69,8 +71,10 @@ namespace {
 
 }  // namespace
 
+#ifndef AVM_MARG_MIXED
 #include "solve/gauge.hpp"            // gauge_rot_diff: rot_diff / origin_P0 of the gauge fix
 #include "solve/solve_kernel.hpp"     // the kernel: load, frame deal, TrustRegionMinimizer, gauge fix
+#endif
 
 #ifndef AVM_X  // marginalization: latency and throughput builds
 #include "solve/marg_layout.hpp"        // what the marginalization computes, its map of LDS (namespace mg), mg_col
@@ -83,7 +87,9 @@ namespace {
 #include "solve/marg_kernel.hpp"        // the marginalization kernel: one function, phases A to G and the output
 #endif
 
-#if defined(AVM_TP)  // each build's launchers and test exports
+#if defined(AVM_MARG_MIXED)  // each build's launchers and test exports
+#include "solve/launch_mm.hpp"
+#elif defined(AVM_TP)
 #include "solve/launch_tp.hpp"
 #elif defined(AVM_X)
 #include "solve/launch_x.hpp"

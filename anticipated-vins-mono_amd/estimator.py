@@ -24,28 +24,87 @@ class Estimator:
 
     # the reference's name
     def optimization(self, windows: buffers.WindowArrays, want_summary: bool = True, prior_out: buffers.PriorOutArrays = None,
-                     summary_out=None):
+                     summary_out=None, marginalization_flags=None):
         """Solve all windows in place.  `prior_out` lets a caller that solves batch after batch hand the same
         output slots back in (the reference allocates a new MarginalizationInfo per call; the slots are plain data);
-        `summary_out` (buffers.summary_alloc) likewise for the per-window summaries: every record is rewritten by a call."""
+        `summary_out` (buffers.summary_alloc) likewise for the per-window summaries: every record is rewritten by a call.
+        `marginalization_flags`: [B] int32 where the windows live (numpy / device tensor), one MARGIN_OLD / MARGIN_SECOND_NEW /
+        MARGIN_NONE per window instead of options.marginalization_flag (keyframe_decision() gives them); every window that reports
+        n < 0 - MARGIN_NONE, or MARGIN_SECOND_NEW with nothing to drop - then keeps the prior it was solved with."""
         L = self.ctx._L
         B = windows.n_windows
         s = windows.struct()
         dev = "cuda:%d" % self.ctx.device if windows.on_device else None
         summ = (summary_out if summary_out is not None else buffers.summary_alloc(B, dev)) if want_summary else None
         prior = None
-        if self.options.marginalization_flag != abi.MARGIN_NONE:
+        if marginalization_flags is not None or self.options.marginalization_flag != abi.MARGIN_NONE:
             prior = prior_out or buffers.PriorOutArrays.alloc(B, windows.dims["max_prior"], windows.dims["max_pblk"], dev)
         po = prior.struct() if prior is not None else None
-        rc = L.avm_window_solve_batch(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s),
-                                      C.byref(po) if po is not None else None,
-                                      buffers.summary_ptr(summ) if summ is not None else None)
-        self.ctx.check(rc, "avm_window_solve_batch")
+        args = (C.byref(po) if po is not None else None, buffers.summary_ptr(summ) if summ is not None else None)
+        if marginalization_flags is None:
+            rc = L.avm_window_solve_batch(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), *args)
+            self.ctx.check(rc, "avm_window_solve_batch")
+        else:
+            flags = self._flags_like(windows, marginalization_flags)
+            rc = L.avm_window_solve_batch_flags(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), abi.iptr(flags), *args)
+            self.ctx.check(rc, "avm_window_solve_batch_flags")
         self.last_summary = summ
-        if prior is not None and self.options.marginalization_flag == abi.MARGIN_SECOND_NEW:
+        if prior is not None and (marginalization_flags is not None or self.options.marginalization_flag == abi.MARGIN_SECOND_NEW):
             self._keep_old_prior_where_nothing_was_dropped(prior, windows)
         self.last_marginalization_info = prior
         return summ
+
+    def _flags_like(self, windows, flags):
+        """[B] int32 flags in the memory space of `windows`: a host array for host windows, a device tensor for device ones."""
+        if windows.on_device:
+            import torch
+
+            if isinstance(flags, torch.Tensor):
+                t = flags.to(device="cuda:%d" % self.ctx.device, dtype=torch.int32).contiguous()
+            else:
+                t = torch.from_numpy(np.ascontiguousarray(flags, np.int32)).to("cuda:%d" % self.ctx.device)
+            assert t.shape == (windows.n_windows,)
+            return t
+        a = np.ascontiguousarray(flags.cpu().numpy() if hasattr(flags, "cpu") else flags, np.int32)
+        assert a.shape == (windows.n_windows,)
+        return a
+
+    def _out_like(self, windows, shape, dtype):
+        if windows.on_device:
+            import torch
+
+            return torch.zeros(shape, dtype=torch.int32 if dtype == np.int32 else torch.float64, device="cuda:%d" % self.ctx.device)
+        return np.zeros(shape, dtype)
+
+    def keyframe_decision(self, windows: buffers.WindowArrays, min_parallax: float):
+        """FeatureManager::addFeatureCheckParallax's verdict (feature_manager.cpp:74-96) for every window, on tables that already hold
+        the new image's observations: returns (marginalization_flags [B] int32, last_track_num [B] int32, parallax [B, 2] = sum, num),
+        arrays where the windows live.  MARGIN_OLD = keyframe.  min_parallax: MIN_PARALLAX (configured pixels / FOCAL_LENGTH)."""
+        B = windows.n_windows
+        flags, ltn, par = self._out_like(windows, (B,), np.int32), self._out_like(windows, (B,), np.int32), self._out_like(windows, (B, 2), np.float64)
+        s = windows.struct()
+        rc = self.ctx._L.avm_keyframe_decision_batch(self.ctx.h, windows.mem, C.byref(s), float(min_parallax), abi.iptr(flags), abi.iptr(ltn),
+                                                     abi.dptr(par))
+        self.ctx.check(rc, "avm_keyframe_decision_batch")
+        return flags, ltn, par
+
+    def failureDetection(self, windows: buffers.WindowArrays, last_P):
+        """Estimator::failureDetection (estimator.cpp:612-658) for every window: [B] int32, 0 or the number of the first rule that fired
+        (1: |Ba[10]| > 2.5, 2: |Bg[10]| > 1, 3: |P[10] - last_P| > 5, 4: |dP.z| > 1).  last_P: [B, 3] where the windows live."""
+        B = windows.n_windows
+        if windows.on_device:
+            import torch
+
+            lp = last_P if isinstance(last_P, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(last_P, np.float64))
+            lp = lp.to(device="cuda:%d" % self.ctx.device, dtype=torch.float64).contiguous()
+        else:
+            lp = np.ascontiguousarray(last_P, np.float64)
+        assert tuple(lp.shape) == (B, 3)
+        failed = self._out_like(windows, (B,), np.int32)
+        s = windows.struct()
+        rc = self.ctx._L.avm_failure_detection_batch(self.ctx.h, windows.mem, C.byref(s), abi.dptr(lp), abi.iptr(failed))
+        self.ctx.check(rc, "avm_failure_detection_batch")
+        return failed
 
     @staticmethod
     def _keep_old_prior_where_nothing_was_dropped(prior, windows):
@@ -114,13 +173,21 @@ class Estimator:
         rc = self.ctx._L.avm_imu_propagate_batch(self.ctx.h, windows.mem, C.byref(s), g)
         self.ctx.check(rc, "avm_imu_propagate_batch")
 
-    def slideWindow(self, windows: buffers.WindowArrays, marginalization_flag=None, shift_depth=True, init_depth=5.0):
+    def slideWindow(self, windows: buffers.WindowArrays, marginalization_flag=None, shift_depth=True, init_depth=5.0, remove_failures=False):
         """Estimator::slideWindow (estimator.cpp:996-1107) + removeBackShiftDepth / removeBack / removeFront
-        (feature_manager.cpp:275-352), in place on the batch tables (host or device resident)."""
+        (feature_manager.cpp:275-352), in place on the batch tables (host or device resident).  marginalization_flag: one int for the
+        batch, or an array / tensor of B flags, one per window.  remove_failures: f_manager.removeFailures() behind the roll
+        (estimator.cpp:197-198): the features the solve left with a negative inverse depth are erased."""
         flag = self.options.marginalization_flag if marginalization_flag is None else marginalization_flag
         s = windows.struct()
-        rc = self.ctx._L.avm_slide_window(self.ctx.h, windows.mem, C.byref(s), int(flag), int(bool(shift_depth)), float(init_depth))
-        self.ctx.check(rc, "avm_slide_window")
+        if np.ndim(flag) == 0 and not remove_failures:
+            rc = self.ctx._L.avm_slide_window(self.ctx.h, windows.mem, C.byref(s), int(flag), int(bool(shift_depth)), float(init_depth))
+            self.ctx.check(rc, "avm_slide_window")
+            return
+        flags = self._flags_like(windows, np.full(windows.n_windows, int(flag), np.int32) if np.ndim(flag) == 0 else flag)
+        rc = self.ctx._L.avm_slide_window_flags(self.ctx.h, windows.mem, C.byref(s), abi.iptr(flags), int(bool(shift_depth)), float(init_depth),
+                                                int(bool(remove_failures)))
+        self.ctx.check(rc, "avm_slide_window_flags")
 
     def preintegrate(self, windows: buffers.WindowArrays):
         """IntegrationBase for every interval: returns delta [B,10,10], jacobian, covariance [B,10,15,15], sum_dt [B,10]."""

@@ -76,6 +76,8 @@ def lib():
         L.avm_visual_initial_align_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.AlignBatch), C.POINTER(abi.WindowBatch),
                                                      C.POINTER(abi.AlignOut)]
         L.avm_debug_align_layout.argtypes = [C.POINTER(C.c_int)]
+        for name, argtypes in abi.PROTOTYPES.items():
+            getattr(L, name).argtypes = argtypes
         L.avm_comm_unique_id.argtypes = [vp, C.c_void_p]
         L.avm_comm_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_void_p]
         L.avm_gather_states.argtypes = [vp, abi.c_dp, abi.c_dp, C.c_size_t]
@@ -99,6 +101,7 @@ EXPORTS = [
     "avm_fsel_select_batch", "avm_fsel_information", "avm_fsel_nn_depth", "avm_last_kernel_ms", "avm_triangulate_batch", "avm_imu_propagate_batch", "avm_fsel_horizon_imu", "avm_projection_td_eval", "avm_fsel_build_cloud",
     "avm_ctx_stream", "avm_comm_unique_id", "avm_comm_init", "avm_gather_states", "avm_comm_destroy", "avm_gt_load_csv", "avm_gt_from_rows", "avm_gt_free", "avm_gt_size", "avm_gt_seek", "avm_fsel_horizon_ground_truth", "avm_image_from_pointcloud", "avm_slide_window",
     "avm_visual_initial_align_batch",
+    "avm_window_solve_batch_flags", "avm_slide_window_flags", "avm_keyframe_decision_batch", "avm_failure_detection_batch",
 ]
 
 

@@ -354,6 +354,21 @@ int avm_window_solve_batch(avm_ctx* ctx, const avm_options* opt, avm_mem mem,
                            const avm_window_batch* batch, avm_prior_out* prior_out,
                            avm_solve_summary* summary /* [B], host or device per mem */);
 
+/* The same solve with a marginalization flag PER WINDOW: a batch of streams, each of which took its own keyframe decision
+ * (estimator.cpp:117-120; avm_keyframe_decision_batch below).  marginalization_flags: [B] in `mem` space, each AVM_MARGIN_OLD,
+ * AVM_MARGIN_SECOND_NEW or AVM_MARGIN_NONE; anything else is AVM_ERR_INVALID naming the window, before any kernel reads a flag.
+ * NULL: opt->marginalization_flag for every window - that is avm_window_solve_batch, which is this call with NULL.
+ * Window w is solved and marginalized exactly (bit for bit) as avm_window_solve_batch does it in a batch whose
+ * opt->marginalization_flag is marginalization_flags[w]; opt->marginalization_flag itself is not read when flags are given, and
+ * prior_out must be given.  A window whose flag is AVM_MARGIN_NONE is not marginalized and reports prior_out->n = -1, nblk = 0, exactly
+ * as a MARGIN_SECOND_NEW window whose prior does not hold pose[WINDOW_SIZE - 1]: both mean "the caller keeps the prior it had".  (A
+ * batch whose flags are all AVM_MARGIN_NONE launches no marginalization and reports the same.)
+ * opt->max_solver_time_s stays ONE cap per call.  The reference gives a MARGIN_OLD frame 4/5 of SOLVER_TIME (estimator.cpp:803-806);
+ * which cap a mixed batch runs under is the caller's choice, there is no cap per window. */
+int avm_window_solve_batch_flags(avm_ctx* ctx, const avm_options* opt, avm_mem mem, const avm_window_batch* batch,
+                                 const int32_t* marginalization_flags /* [B], in `mem` space; NULL = opt's */,
+                                 avm_prior_out* prior_out, avm_solve_summary* summary);
+
 /* the single-call form, exactly one Estimator::optimization() (estimator.h:47): the same arguments with
  * batch->n_windows == 1 (AVM_ERR_INVALID otherwise).  One window occupies one compute unit; see DESIGN.md for its latency. */
 int avm_window_solve(avm_ctx* ctx, const avm_options* opt, avm_mem mem, const avm_window_batch* window,
@@ -421,6 +436,42 @@ int avm_fsel_build_cloud(avm_ctx* ctx, avm_mem mem, const avm_window_batch* wind
  * Erasing compacts the per-feature arrays in order (std::list order); observations stay where they are, only
  * feat_obs_begin / feat_nobs change (one element moves for removeFront).  inv_depth holds 1 / estimated_depth. */
 int avm_slide_window(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, int32_t marginalization_flag, int32_t shift_depth, double init_depth);
+
+/* The roll with a flag per window: marginalization_flags [B] in `mem` space, each AVM_MARGIN_OLD or AVM_MARGIN_SECOND_NEW (anything
+ * else, AVM_MARGIN_NONE included: AVM_ERR_INVALID naming the window, nothing written).  Window w is rolled exactly as avm_slide_window
+ * rolls it under marginalization_flags[w]; avm_slide_window is the uniform case with remove_failures = 0.  AVM_ERR_CAPACITY as there,
+ * also when a single MARGIN_SECOND_NEW window overflows max_samp (the other windows were rolled).
+ * remove_failures != 0: `slideWindow(); f_manager.removeFailures();`, the order of processImage (estimator.cpp:197-198).  A feature
+ * is a failure if BEFORE the roll it passed the solve's filter (feat_nobs >= 2 && feat_start < WINDOW_SIZE - 2) and its inv_depth
+ * is < 0: setDepth's solve_flag = 2 (feature_manager.cpp:141-159).  It is erased after the roll whatever the roll did to its depth
+ * (removeBackShiftDepth rewrites a non-positive re-anchored depth to init_depth), compacting in list order like the roll's own
+ * erasures.  A feature that never entered the solve is never erased by this rule: it carries inv_depth = 1 / (-1), "no depth yet". */
+int avm_slide_window_flags(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, const int32_t* marginalization_flags /* [B] */,
+                           int32_t shift_depth, double init_depth, int32_t remove_failures);
+
+/* The keyframe decision of every window: the return value of FeatureManager::addFeatureCheckParallax (feature_manager.cpp:74-96,
+ * compensatedParallax2 :355-388) for frame_count == WINDOW_SIZE, on tables that ALREADY hold the new image's observations (frame 10).
+ *   last_track_num = features with feat_nobs >= 2 whose last observation is in frame 10 (the ones the new image extended);
+ *   parallax sum / num over the features with start <= 8 && start + nobs - 1 >= 9, in list order: sqrt(du^2 + dv^2) between their
+ *   frame-8 and frame-9 observations (the observations are normalized, z == 1: the "compensated" branch is the same number);
+ *   flag = AVM_MARGIN_OLD (keyframe) if last_track_num < 20, or num == 0, or sum / num >= min_parallax (MIN_PARALLAX, i.e. the
+ *   configured pixels / FOCAL_LENGTH); else AVM_MARGIN_SECOND_NEW.
+ * The decision is discrete, so the arithmetic is the reference's and not a tolerance: every term without FMA contraction, the terms
+ * added one after the other in list order.  Outputs in `mem` space: marginalization_flags [B]; last_track_num [B] and parallax [B][2]
+ * (sum, num - both over the whole list, also where last_track_num < 20 decided) may be NULL.
+ * It is the reference's decision when the tables hold the whole f_manager.feature list (as avm_host::Estimator::slideWindow
+ * marshals it).  On the solve's FILTERED tables (start < WINDOW_SIZE - 2) the tracks that start in frame 8 are missing from the mean.
+ * Tables up to AVM_MAX_FEAT_WIDE / AVM_MAX_OBS_WIDE; they are validated before the kernel indexes with them. */
+int avm_keyframe_decision_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* windows, double min_parallax,
+                                int32_t* marginalization_flags /* [B] out */, int32_t* last_track_num /* [B] out, nullable */,
+                                double* parallax /* [B][2] out, nullable: sum, num */);
+
+/* Estimator::failureDetection (estimator.cpp:612-658) after the solve: failed[w] = 0, or the number of the first rule that fired, in
+ * the reference's order:  1: |Ba[10]| > 2.5   2: |Bg[10]| > 1.0   3: |P[10] - last_P| > 5   4: |P[10].z - last_P.z| > 1
+ * (Euclidean norms; the reference's commented-out rules and the ones that only log are not rules here).  last_P: [B][3], the newest
+ * frame's position after the previous image (estimator.cpp:209); reads windows->pose and windows->speedbias only. */
+int avm_failure_detection_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* windows, const double* last_P /* [B][3] */,
+                                int32_t* failed /* [B] out */);
 
 /* ---- Estimator::visualInitialAlign (estimator.cpp:355-431) with VisualIMUAlignment (initial/initial_aligment.cpp): the step that
  * moves solver_flag from INITIAL to NON_LINEAR.  It starts from the up-to-scale camera trajectory of initialStructure (relativePose,
