@@ -275,6 +275,25 @@ PROTOTYPES = {
 }
 
 
+MAX_IMAGE_PTS = 1024  # AVM_MAX_IMAGE_PTS
+
+
+class ImageBatch(C.Structure):
+    """avm_image_batch (include/avm.h): one image per window, the `image` map of processImage (camera 0)."""
+    _fields_ = [("n_windows", C.c_int32), ("max_pts", C.c_int32), ("n_pts", c_ip), ("feature_id", c_ip), ("xy", c_dp), ("vel_td", c_dp)]
+
+
+# The feature manager on device-resident tables (include/avm.h): the image's append by feature id, the IMU buffer, the solve's view of
+# the whole list and setDepth, the roll with ids.  A dict of its own: PROTOTYPES keeps its keys.  lib.py applies both the same way.
+TRACK_PROTOTYPES = {
+    "avm_add_image_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.POINTER(ImageBatch), C.c_double, c_ip, c_ip, c_dp],
+    "avm_imu_push_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.c_int32, c_dp, c_dp, c_dp],
+    "avm_solve_view_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(WindowBatch), c_ip],
+    "avm_solve_view_store_depths": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(WindowBatch), c_ip],
+    "avm_slide_window_tracks": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, c_ip, C.c_int32, C.c_double, C.c_int32],
+}
+
+
 def default_options() -> Options:
     """Values the reference runs with (estimator.cpp:794-806, euroc_config.yaml:54-63) + Ceres defaults.
 

@@ -85,6 +85,93 @@ class WindowArrays(_Arrays):
         return WindowArrays(d, {k: v[lo:hi] for k, v in self.a.items()})
 
 
+TRACK_KEYS = ("n_feat", "feat_start", "feat_nobs", "feat_obs_begin", "obs_xy", "inv_depth", "obs_vel_td")   # what avm_solve_view_batch writes
+
+
+class ImageArrays(_Arrays):
+    """avm_image_batch: one image per window, what processImage gets from the tracker (camera 0): n_pts [B], feature_id [B, max_pts]
+    strictly ascending, xy [B, max_pts, 2] and, with the time offset, vel_td [B, max_pts, 4] (velocity.x, velocity.y, cur_td, uv.y)."""
+
+    F64, I32 = ["xy", "vel_td"], ["n_pts", "feature_id"]
+
+    def struct(self) -> abi.ImageBatch:
+        return self._fill(abi.ImageBatch())
+
+    @property
+    def n_windows(self) -> int:
+        return self.dims["n_windows"]
+
+    @staticmethod
+    def from_maps(images, max_pts: int, with_td: bool = False) -> "ImageArrays":
+        """images: per window a dict {feature id: (x, y)} or, with_td, {feature id: (x, y, vx, vy, cur_td, v)}; std::map order = sorted ids."""
+        B = len(images)
+        a = {"n_pts": np.zeros(B, np.int32), "feature_id": np.zeros((B, max_pts), np.int32), "xy": np.zeros((B, max_pts, 2))}
+        if with_td:
+            a["vel_td"] = np.zeros((B, max_pts, 4))
+        for b, im in enumerate(images):
+            ids = sorted(im)
+            assert len(ids) <= max_pts
+            a["n_pts"][b] = len(ids)
+            for i, fid in enumerate(ids):
+                a["feature_id"][b, i] = fid
+                a["xy"][b, i] = im[fid][:2]
+                if with_td:
+                    a["vel_td"][b, i] = im[fid][2:6]
+        return ImageArrays({"n_windows": B, "max_pts": max_pts}, a)
+
+
+class TrackTables:
+    """The tables of a batch of streams whose feature manager lives in the library (include/avm.h, "the feature manager on
+    device-resident tables"): `full` holds the whole f_manager.feature list of every window (strides up to MAX_FEAT_WIDE /
+    MAX_OBS_WIDE), `feat_id` [B, max_feat] its ids, `view` is what triangulate() and optimization() take - a WindowArrays of the solve's
+    strides whose track arrays (TRACK_KEYS) are its own and whose every other array IS the array of `full` (the same object: poses, IMU,
+    prior) - and `view_row` [B, view max_feat] the row of `full` behind every row of the view.  Estimator.solve_view() fills the view,
+    Estimator.setDepth() carries its depths back."""
+
+    def __init__(self, full: WindowArrays, feat_id, max_feat: int = abi.MAX_FEAT, max_obs: int = abi.MAX_OBS, view_tracks: dict = None, view_row=None):
+        self.full, self.feat_id = full, feat_id
+        B = full.n_windows
+        dims = dict(full.dims)
+        dims["max_feat"], dims["max_obs"] = max_feat, max_obs
+        shapes = {"n_feat": (B,), "feat_start": (B, max_feat), "feat_nobs": (B, max_feat), "feat_obs_begin": (B, max_feat),
+                  "obs_xy": (B, max_obs, 2), "inv_depth": (B, max_feat), "obs_vel_td": (B, max_obs, 4)}
+        a = {k: v for k, v in full.a.items() if k not in TRACK_KEYS and not k.startswith("relo_")}
+        for k in TRACK_KEYS:
+            if k in full.a:
+                a[k] = view_tracks[k] if view_tracks else self._zeros_like(full.a[k], shapes[k])
+        self.view = WindowArrays(dims, a)
+        self.view_row = view_row if view_row is not None else self._zeros_like(full.a["n_feat"], (B, max_feat))
+
+    @staticmethod
+    def _zeros_like(x, shape):
+        if isinstance(x, np.ndarray):
+            return np.zeros(shape, x.dtype)
+        import torch
+
+        return torch.zeros(shape, dtype=x.dtype, device=x.device)
+
+    @property
+    def on_device(self) -> bool:
+        return self.full.on_device
+
+    def _rebuilt(self, conv, full):
+        d = self.view.dims
+        tracks = {k: conv(self.view.a[k]) for k in TRACK_KEYS if k in self.view.a}
+        return TrackTables(full, conv(self.feat_id), d["max_feat"], d["max_obs"], tracks, conv(self.view_row))
+
+    def copy(self) -> "TrackTables":
+        return self._rebuilt((lambda v: v.clone()) if self.on_device else (lambda v: v.copy()), self.full.copy())
+
+    def to_device(self, device="cuda:0") -> "TrackTables":
+        import torch
+
+        return self._rebuilt(lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(device) if isinstance(v, np.ndarray) else v.to(device),
+                             self.full.to_device(device))
+
+    def to_host(self) -> "TrackTables":
+        return self._rebuilt(lambda v: v.copy() if isinstance(v, np.ndarray) else v.cpu().numpy(), self.full.to_host())
+
+
 class PriorOutArrays(_Arrays):
     F64, I32 = ["J", "r", "x0"], ["n", "nblk", "blk_kind", "blk_frame"]
 

@@ -348,8 +348,11 @@ inline void* get_ptr(const void* s, const Field& f) {
 inline void set_ptr(void* s, const Field& f, const void* p) { std::memcpy(static_cast<char*>(s) + f.offset, &p, sizeof p); }
 
 // who uses an array: the calls that take the whole batch (solve, pre-integration, factor evaluation; struct-valued outputs), and the ones
-// that take a subset of the window tables (U_KEYF: the keyframe decision, U_FAIL: the failure detection)
-enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32, U_KEYF = 64, U_FAIL = 128 };
+// that take a subset of the window tables (U_KEYF: the keyframe decision, U_FAIL: the failure detection; the feature manager's calls -
+// U_TRK: the track tables of a window with its depths and td rows, U_DEPTH: setDepth, U_PUSH: the raw IMU samples, U_SLIDE_TD: the td rows
+// beside U_SLIDE in avm_slide_window_tracks)
+enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32, U_KEYF = 64, U_FAIL = 128,
+                  U_TRK = 256, U_DEPTH = 512, U_PUSH = 1024, U_SLIDE_TD = 2048 };
 constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE | U_SLIDE | U_PROP;
 
 // S: the struct of the member; D, nmember: the struct the dims come from (`d` in `count`) and its batch size (`N` in `count`)
@@ -370,16 +373,16 @@ const Field WINDOW_FIELDS[] = {
     WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
     WIN(speedbias, double, N * 99, U_IMU | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
     WIN(ex_pose, double, N * 7, U_GEOM | U_ALIGN, U_WHOLE | U_SLIDE)
-    WIN(inv_depth, double, N * d.max_feat, U_GEOM | U_ALIGN, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN)
-    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
-    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
-    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_KEYF, U_SLIDE)
-    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
-    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN | U_KEYF, U_SLIDE)
-    WIN(imu_n, int32_t, N * 10, U_IMU, U_SLIDE)
-    WIN(imu_dt, double, N * 10 * d.max_samp, U_IMU, U_SLIDE)
-    WIN(imu_acc, double, N * 10 * (d.max_samp + 1) * 3, U_IMU, U_SLIDE)
-    WIN(imu_gyr, double, N * 10 * (d.max_samp + 1) * 3, U_IMU, U_SLIDE)
+    WIN(inv_depth, double, N * d.max_feat, U_GEOM | U_ALIGN | U_TRK | U_DEPTH, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_TRK | U_DEPTH)
+    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_KEYF | U_TRK | U_DEPTH, U_SLIDE | U_TRK)
+    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(imu_n, int32_t, N * 10, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
+    WIN(imu_dt, double, N * 10 * d.max_samp, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
+    WIN(imu_acc, double, N * 10 * (d.max_samp + 1) * 3, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
+    WIN(imu_gyr, double, N * 10 * (d.max_samp + 1) * 3, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
     WIN(imu_lin_ba, double, N * 30, U_WHOLE | U_SLIDE, U_SLIDE)
     WIN(imu_lin_bg, double, N * 30, U_WHOLE | U_SLIDE, U_SLIDE)
     WIN(prior_n, int32_t, N, U_WHOLE, 0)
@@ -389,7 +392,7 @@ const Field WINDOW_FIELDS[] = {
     WIN(prior_J, double, N * d.max_prior * d.max_prior, U_WHOLE, 0)
     WIN(prior_r, double, N * d.max_prior, U_WHOLE, 0)
     WIN(prior_x0, double, N * d.max_pblk * 9, U_WHOLE, 0)
-    WIN(obs_vel_td, double, N * d.max_obs * 4, U_WHOLE, 0)
+    WIN(obs_vel_td, double, N * d.max_obs * 4, U_WHOLE | U_TRK | U_SLIDE_TD, U_TRK | U_SLIDE_TD)
     WIN(td, double, N, U_WHOLE, U_WHOLE)  // para_Td: in/out
     WIN(relo_n, int32_t, N, U_WHOLE, 0)
     WIN(relo_frame, int32_t, N, U_WHOLE, 0)
@@ -469,8 +472,8 @@ int stage_array(avm_ctx* c, const char* name, const void* host, size_t bytes, co
 // Copies the tables of the host struct *h that entry point `use` reads to the device and points *d (a copy of *h) at them.  pack: the pool
 // name of the one block - 64-byte aligned parts, in table order, absent tables left out - that the batch travels in when all of it fits
 // PACK_LIMIT: one pinned buffer and one copy (22 pageable copies of a few hundred bytes each cost more than the solve's pre-integration
-// kernel); nullptr: table by table, each into the pool buffer of its name.
-int stage(avm_ctx* c, Table t, unsigned use, const void* h, void* d, const char* pack, bool* packed) {
+// kernel); nullptr: table by table, each into the pool buffer of its name (behind `prefix`: a call that stages two structs of one kind).
+int stage(avm_ctx* c, Table t, unsigned use, const void* h, void* d, const char* pack, bool* packed, const char* prefix = "") {
   size_t total = 0;
   for (const Field& f : t)
     if ((f.in & use) && get_ptr(h, f)) total += pack_up(f.bytes(h, h));
@@ -480,7 +483,7 @@ int stage(avm_ctx* c, Table t, unsigned use, const void* h, void* d, const char*
     for (const Field& f : t) {
       if (!(f.in & use)) continue;
       const void* dev;
-      const int rc = stage_array(c, f.pool, get_ptr(h, f), f.bytes(h, h), &dev);
+      const int rc = stage_array(c, (std::string(prefix) + f.pool).c_str(), get_ptr(h, f), f.bytes(h, h), &dev);
       if (rc != AVM_OK) return rc;
       set_ptr(d, f, dev);
     }
@@ -504,10 +507,11 @@ int stage(avm_ctx* c, Table t, unsigned use, const void* h, void* d, const char*
 // The caller's struct as the kernels take it: the struct itself (AVM_MEM_DEVICE), or staged (AVM_MEM_HOST).  The entry points that take
 // a subset of the window tables never pack.
 template <class S>
-int on_device(avm_ctx* c, avm_mem mem, Table t, unsigned use, const S* h, S* d, const char* pack = nullptr, bool* packed = nullptr) {
+int on_device(avm_ctx* c, avm_mem mem, Table t, unsigned use, const S* h, S* d, const char* pack = nullptr, bool* packed = nullptr,
+              const char* prefix = "") {
   *d = *h;
   if (packed) *packed = false;
-  return mem == AVM_MEM_HOST ? stage(c, t, use, h, d, pack, packed) : AVM_OK;
+  return mem == AVM_MEM_HOST ? stage(c, t, use, h, d, pack, packed, prefix) : AVM_OK;
 }
 
 // the whole window batch: packed when it is small and has its four state arrays, the head of the block
@@ -1073,6 +1077,16 @@ int avm_debug_struct_sizes(int* out) {
   return 7;
 }
 
+// test hook (not in avm.h): sizeof and the member offsets of avm_image_batch, and AVM_MAX_IMAGE_PTS, for the ctypes mirror check; out: >= 8 ints
+int avm_debug_track_struct_sizes(int* out) {
+  int n = 0;
+  out[n++] = (int)sizeof(avm_image_batch), out[n++] = AVM_MAX_IMAGE_PTS;
+  for (size_t o : {offsetof(avm_image_batch, n_windows), offsetof(avm_image_batch, max_pts), offsetof(avm_image_batch, n_pts),
+                   offsetof(avm_image_batch, feature_id), offsetof(avm_image_batch, xy), offsetof(avm_image_batch, vel_td)})
+    out[n++] = (int)o;
+  return n;
+}
+
 // test hook (not in avm.h): sizeof and the member offsets of avm_align_batch / avm_align_out, for the ctypes mirror check; out: >= 23 ints
 int avm_debug_align_layout(int* out) {
   int n = 0;
@@ -1187,26 +1201,34 @@ int avm_visual_initial_align_batch(avm_ctx* c, const avm_options* opt, avm_mem m
 
 namespace {
 // the roll: flags ([B], in `mem` space) per window, or flags == null and `flag` for every window
+// feat_id ([B][max_feat] in `mem` space, nullable): avm_slide_window_tracks - the ids are compacted with the rows, and the rows of
+// obs_vel_td (when the batch has them) move with those of obs_xy
 int slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, const int32_t* flags, int32_t flag, int32_t shift_depth, double init_depth,
-                 int32_t remove_failures) {
+                 int32_t remove_failures, int32_t* feat_id = nullptr) {
   if (batch->n_windows == 0) return AVM_OK;
   // (the flags are checked with the tables, before the kernel reads either)
   const FlagRule fr{flags, (1u << AVM_MARGIN_OLD) | (1u << AVM_MARGIN_SECOND_NEW)};
   int rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU, nullptr, fr, roll_flag_rule_text);
   if (rc != AVM_OK) return rc;
   avm_window_batch d;
-  if ((rc = on_device(c, mem, WINDOWS, U_SLIDE, batch, &d)) != AVM_OK) return rc;
+  const unsigned use = U_SLIDE | (feat_id ? U_SLIDE_TD : 0u);
+  if ((rc = on_device(c, mem, WINDOWS, use, batch, &d)) != AVM_OK) return rc;
+  const void* dfid = feat_id;
+  const size_t fid_bytes = sizeof(int32_t) * (size_t)batch->n_windows * batch->max_feat;
+  if (feat_id && mem == AVM_MEM_HOST && (rc = stage_array(c, "w_feat_id", feat_id, fid_bytes, &dfid)) != AVM_OK) return rc;
   const void* dflags = flags;
   if (flags && mem == AVM_MEM_HOST && (rc = stage_array(c, "w_roll_flags", flags, sizeof(int32_t) * batch->n_windows, &dflags)) != AVM_OK) return rc;
   int* derr = static_cast<int*>(pool_get(c, "slide_err", sizeof(int)));
   if (!derr) return fail(c, AVM_ERR_HIP, "hipMalloc failed (slide flag)");
   HIPCHK(c, hipMemsetAsync(derr, 0, sizeof(int), c->stream));
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
-  HIPCHK(c, launch_slide_window(d, static_cast<const int32_t*>(dflags), flag, shift_depth, init_depth, remove_failures, derr, c->stream));
+  HIPCHK(c, launch_slide_window(d, static_cast<const int32_t*>(dflags), flag, shift_depth, init_depth, remove_failures, derr, c->stream,
+                                static_cast<int32_t*>(const_cast<void*>(dfid)), feat_id ? 1 : 0));
   HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
   int herr = 0;
   HIPCHK(c, hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if ((rc = copy_back(c, mem, WINDOWS, U_SLIDE, batch, &d, batch)) != AVM_OK) return rc;  // (everything the roll rewrites)
+  if ((rc = copy_back(c, mem, WINDOWS, use, batch, &d, batch)) != AVM_OK) return rc;  // (everything the roll rewrites)
+  if (feat_id && mem == AVM_MEM_HOST && dfid) HIPCHK(c, hipMemcpyAsync(feat_id, dfid, fid_bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["slide_window"] = ms;
@@ -1229,6 +1251,232 @@ int avm_slide_window_flags(avm_ctx* c, avm_mem mem, avm_window_batch* batch, con
   (void)hipSetDevice(c->device);
   if (!batch || !flags || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
   return slide_window(c, mem, batch, flags, AVM_MARGIN_OLD, shift_depth, init_depth, remove_failures);
+}
+
+int avm_slide_window_tracks(avm_ctx* c, avm_mem mem, avm_window_batch* batch, int32_t* feat_id, const int32_t* flags, int32_t shift_depth,
+                            double init_depth, int32_t remove_failures) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!batch || !feat_id || !flags || batch->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  return slide_window(c, mem, batch, flags, AVM_MARGIN_OLD, shift_depth, init_depth, remove_failures, feat_id);
+}
+
+}  // extern "C"
+
+// ---- the feature manager on device-resident tables (tracks.hip) ----
+namespace {
+struct TrackRule {
+  int status;
+  const char* text;
+};
+const TrackRule ADD_IMAGE_RULES[8] = {
+    {AVM_ERR_INVALID, "bad table"},
+    {AVM_ERR_INVALID, "n_pts outside [0, max_pts]"},
+    {AVM_ERR_INVALID, "the image's feature ids must be strictly ascending (std::map order)"},
+    {AVM_ERR_INVALID, "a track already has an observation in frame 10 (feat_start + feat_nobs > 10)"},
+    {AVM_ERR_INVALID, "an image id matches a track whose last observation is not in frame 9 (a lost id was issued again)"},
+    {AVM_ERR_INVALID, "duplicate id in feat_id[0 .. n_feat)"},
+    {AVM_ERR_CAPACITY, "n_feat + new tracks > max_feat"},
+    {AVM_ERR_CAPACITY, "the observations do not fit max_obs"}};
+const TrackRule IMU_PUSH_RULES[8] = {{AVM_ERR_INVALID, "bad table"},
+                                     {AVM_ERR_INVALID, "n outside [0, max_in]"},
+                                     {AVM_ERR_CAPACITY, "interval 9 + the new samples exceed max_samp samples"}};
+const TrackRule SOLVE_VIEW_RULES[8] = {{AVM_ERR_INVALID, "bad table"},
+                                       {AVM_ERR_CAPACITY, "more rows pass the solve's filter than view->max_feat"},
+                                       {AVM_ERR_CAPACITY, "the observations of the rows that pass the solve's filter do not fit view->max_obs"}};
+const TrackRule STORE_DEPTHS_RULES[8] = {{AVM_ERR_INVALID, "bad table"},
+                                         {AVM_ERR_INVALID, "n_feat outside [0, max_feat] (full or view)"},
+                                         {AVM_ERR_INVALID, "view_row must be strictly increasing inside [0, full n_feat)"}};
+
+// A check kernel of tracks.hip, on its own: its verdict is on the host before the kernel that writes is launched, so a refused batch
+// leaves every window as it was.  Device time between ev[0] and ev[1].
+template <class Launch>
+int track_check(avm_ctx* c, Launch launch, const TrackRule* rules) {
+  FlagCheck f;
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  const int rc = flag_begin(c, 1, launch, &f);
+  if (rc != AVM_OK) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int v = f.host[0];
+  if (v == 0x7f7f7f7f) return AVM_OK;
+  const TrackRule& r = rules[v % 8];
+  c->err = "window " + std::to_string(v / 8) + ": " + (r.text ? r.text : "bad table");
+  return r.text ? r.status : AVM_ERR_INVALID;
+}
+
+// check (ev[0] .. ev[1]) + kernels (ev[3] .. ev[4]) of the call that just synchronized
+void record_track_ms(avm_ctx* c, const char* key) {
+  float a = 0, b = 0;
+  if (hipEventElapsedTime(&a, c->ev[0], c->ev[1]) == hipSuccess && hipEventElapsedTime(&b, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms[key] = a + b;
+}
+
+// an array beside the structs, in `mem` space: the caller's pointer, or (AVM_MEM_HOST) a staged copy / a device buffer to copy back from
+template <class T>
+int array_in(avm_ctx* c, avm_mem mem, const char* pool, const T* p, size_t n, const T** d) {
+  *d = p;
+  if (mem != AVM_MEM_HOST) return AVM_OK;
+  const void* dev = nullptr;
+  const int rc = stage_array(c, pool, p, sizeof(T) * n, &dev);
+  *d = static_cast<const T*>(dev);
+  return rc;
+}
+template <class T>
+int array_out(avm_ctx* c, avm_mem mem, const char* pool, T* p, size_t n, T** d) {
+  *d = p;
+  if (mem != AVM_MEM_HOST || !p) return AVM_OK;
+  *d = static_cast<T*>(pool_get(c, pool, sizeof(T) * n));
+  return *d ? AVM_OK : fail(c, AVM_ERR_HIP, "hipMalloc failed (output array)");
+}
+template <class T>
+int array_back(avm_ctx* c, avm_mem mem, T* p, const T* d, size_t n) {
+  if (mem == AVM_MEM_HOST && p && d && n) HIPCHK(c, hipMemcpyAsync(p, d, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
+  return AVM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int avm_add_image_batch(avm_ctx* c, avm_mem mem, avm_window_batch* win, int32_t* feat_id, const avm_image_batch* img, double min_parallax,
+                        int32_t* flags_out, int32_t* last_track_num, double* parallax) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!win || !feat_id || !img || !flags_out || win->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (img->n_windows != win->n_windows) return fail(c, AVM_ERR_INVALID, "image->n_windows differs from windows->n_windows");
+  if (img->max_pts < 0) return fail(c, AVM_ERR_INVALID, "max_pts < 0");
+  if (img->max_pts > AVM_MAX_IMAGE_PTS) return fail(c, AVM_ERR_CAPACITY, "max_pts > 1024 (AVM_MAX_IMAGE_PTS)");
+  if (!img->n_pts || (img->max_pts > 0 && (!img->feature_id || !img->xy))) return fail(c, AVM_ERR_INVALID, "null image table");
+  if (!win->obs_xy || !win->inv_depth) return fail(c, AVM_ERR_INVALID, "null obs_xy / inv_depth");
+  if ((win->obs_vel_td != nullptr) != (img->vel_td != nullptr))
+    return fail(c, AVM_ERR_INVALID, "image->vel_td must be given if and only if windows->obs_vel_td is");
+  int rc = check_wide_strides(c, win);
+  if (rc != AVM_OK) return rc;
+  if (win->n_windows == 0) return AVM_OK;
+  if ((rc = validate_windows(c, mem, win, CHK_TRACKS)) != AVM_OK) return rc;
+  const size_t B = win->n_windows, P = (size_t)img->max_pts;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_TRK, win, &d)) != AVM_OK) return rc;
+  avm_image_batch di = *img;
+  const int32_t* dfid_in;
+  if ((rc = array_in(c, mem, "ai_n_pts", img->n_pts, B, &di.n_pts)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ai_ids", img->feature_id, B * P, &di.feature_id)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ai_xy", img->xy, B * P * 2, &di.xy)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ai_vel_td", img->vel_td, B * P * 4, &di.vel_td)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "w_feat_id", static_cast<const int32_t*>(feat_id), B * win->max_feat, &dfid_in)) != AVM_OK) return rc;
+  int32_t* dfid = const_cast<int32_t*>(dfid_in);
+  int32_t *dflags, *dltn;
+  double* dpar;
+  if ((rc = array_out(c, mem, "k_flags", flags_out, B, &dflags)) != AVM_OK) return rc;
+  if ((rc = array_out(c, mem, "k_ltn", last_track_num, B, &dltn)) != AVM_OK) return rc;
+  if ((rc = array_out(c, mem, "k_par", parallax, B * 2, &dpar)) != AVM_OK) return rc;
+  if ((rc = track_check(c, [&](int* flag) { return launch_add_image_check(d, dfid, di, flag, c->stream); }, ADD_IMAGE_RULES)) != AVM_OK) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_add_image(d, dfid, di, c->stream));
+  HIPCHK(c, launch_keyframe_decision(d, min_parallax, dflags, dltn, dpar, c->stream));  // (the decision of avm_keyframe_decision_batch, on the result)
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if ((rc = copy_back(c, mem, WINDOWS, U_TRK, win, &d, win)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, feat_id, dfid, B * win->max_feat)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, flags_out, dflags, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, last_track_num, dltn, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, parallax, dpar, B * 2)) != AVM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  record_track_ms(c, "add_image");
+  return AVM_OK;
+}
+
+int avm_imu_push_batch(avm_ctx* c, avm_mem mem, avm_window_batch* win, const int32_t* n, int32_t max_in, const double* dt, const double* acc,
+                       const double* gyr) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!win || !n || win->n_windows < 0 || max_in < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (max_in > 0 && (!dt || !acc || !gyr)) return fail(c, AVM_ERR_INVALID, "null sample array");
+  if (!win->imu_dt || !win->imu_acc || !win->imu_gyr) return fail(c, AVM_ERR_INVALID, "null IMU table");
+  if (win->n_windows == 0) return AVM_OK;
+  int rc = validate_windows(c, mem, win, CHK_IMU);
+  if (rc != AVM_OK) return rc;
+  const size_t B = win->n_windows, M = (size_t)max_in;
+  avm_window_batch d;
+  if ((rc = on_device(c, mem, WINDOWS, U_PUSH, win, &d)) != AVM_OK) return rc;
+  const int32_t* dn;
+  const double *ddt, *dacc, *dgyr;
+  if ((rc = array_in(c, mem, "ip_n", n, B, &dn)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ip_dt", dt, B * M, &ddt)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ip_acc", acc, B * M * 3, &dacc)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ip_gyr", gyr, B * M * 3, &dgyr)) != AVM_OK) return rc;
+  if ((rc = track_check(c, [&](int* flag) { return launch_imu_push_check(d, dn, max_in, flag, c->stream); }, IMU_PUSH_RULES)) != AVM_OK) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_imu_push(d, dn, max_in, ddt, dacc, dgyr, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if ((rc = copy_back(c, mem, WINDOWS, U_PUSH, win, &d, win)) != AVM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  record_track_ms(c, "imu_push");
+  return AVM_OK;
+}
+
+int avm_solve_view_batch(avm_ctx* c, avm_mem mem, const avm_window_batch* full, avm_window_batch* view, int32_t* view_row) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!full || !view || !view_row || full->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (view->n_windows != full->n_windows) return fail(c, AVM_ERR_INVALID, "view->n_windows differs from full->n_windows");
+  if (view->max_feat < 0 || view->max_obs < 0) return fail(c, AVM_ERR_INVALID, "negative view stride");
+  if (view->max_feat > MAXE) return fail(c, AVM_ERR_CAPACITY, "view->max_feat > 150");
+  if (view->max_obs > MAXOBS) return fail(c, AVM_ERR_CAPACITY, "view->max_obs > 1650");
+  if (!full->obs_xy || !full->inv_depth) return fail(c, AVM_ERR_INVALID, "null obs_xy / inv_depth");
+  if (!view->n_feat || !view->feat_start || !view->feat_nobs || !view->feat_obs_begin || !view->obs_xy || !view->inv_depth)
+    return fail(c, AVM_ERR_INVALID, "null view table");
+  if (view->obs_vel_td && !full->obs_vel_td) return fail(c, AVM_ERR_INVALID, "view->obs_vel_td is given but full->obs_vel_td is not");
+  if (view->n_feat == full->n_feat || view->feat_start == full->feat_start || view->feat_nobs == full->feat_nobs ||
+      view->feat_obs_begin == full->feat_obs_begin || view->obs_xy == full->obs_xy || view->inv_depth == full->inv_depth ||
+      (view->obs_vel_td && view->obs_vel_td == full->obs_vel_td))
+    return fail(c, AVM_ERR_INVALID, "the view's track tables must not be the full tables' own arrays");
+  int rc = check_wide_strides(c, full);
+  if (rc != AVM_OK) return rc;
+  if (full->n_windows == 0) return AVM_OK;
+  if ((rc = validate_windows(c, mem, full, CHK_TRACKS)) != AVM_OK) return rc;
+  const size_t B = full->n_windows;
+  avm_window_batch df, dv;
+  if ((rc = on_device(c, mem, WINDOWS, U_TRK, full, &df)) != AVM_OK) return rc;
+  // (the view's arrays travel in as well: the slots the gather does not write keep what they held)
+  if ((rc = on_device(c, mem, WINDOWS, U_TRK, static_cast<const avm_window_batch*>(view), &dv, nullptr, nullptr, "v_")) != AVM_OK) return rc;
+  int32_t* drow;
+  if ((rc = array_out(c, mem, "v_row", view_row, B * view->max_feat, &drow)) != AVM_OK) return rc;
+  if (mem == AVM_MEM_HOST && view->max_feat > 0)
+    HIPCHK(c, hipMemcpyAsync(drow, view_row, sizeof(int32_t) * B * view->max_feat, hipMemcpyHostToDevice, c->stream));
+  if ((rc = track_check(c, [&](int* flag) { return launch_solve_view_check(df, dv, flag, c->stream); }, SOLVE_VIEW_RULES)) != AVM_OK) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_solve_view(df, dv, drow, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if ((rc = copy_back(c, mem, WINDOWS, U_TRK, view, &dv, view)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, view_row, drow, B * view->max_feat)) != AVM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  record_track_ms(c, "solve_view");
+  return AVM_OK;
+}
+
+int avm_solve_view_store_depths(avm_ctx* c, avm_mem mem, avm_window_batch* full, const avm_window_batch* view, const int32_t* view_row) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!full || !view || !view_row || full->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  if (view->n_windows != full->n_windows) return fail(c, AVM_ERR_INVALID, "view->n_windows differs from full->n_windows");
+  if (view->max_feat < 0 || full->max_feat < 0) return fail(c, AVM_ERR_INVALID, "negative stride");
+  if (!full->n_feat || !full->inv_depth || !view->n_feat || !view->inv_depth) return fail(c, AVM_ERR_INVALID, "null n_feat / inv_depth");
+  if (full->n_windows == 0) return AVM_OK;
+  int rc;
+  const size_t B = full->n_windows;
+  avm_window_batch df, dv;
+  if ((rc = on_device(c, mem, WINDOWS, U_DEPTH, static_cast<const avm_window_batch*>(full), &df)) != AVM_OK) return rc;
+  if ((rc = on_device(c, mem, WINDOWS, U_DEPTH, view, &dv, nullptr, nullptr, "v_")) != AVM_OK) return rc;
+  const int32_t* drow;
+  if ((rc = array_in(c, mem, "v_row", view_row, B * view->max_feat, &drow)) != AVM_OK) return rc;
+  if ((rc = track_check(c, [&](int* flag) { return launch_store_depths_check(df, dv, drow, flag, c->stream); }, STORE_DEPTHS_RULES)) != AVM_OK)
+    return rc;
+  HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
+  HIPCHK(c, launch_store_depths(df, dv, drow, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if ((rc = copy_back(c, mem, WINDOWS, U_DEPTH, full, &df, full)) != AVM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  record_track_ms(c, "store_depths");
+  return AVM_OK;
 }
 
 int avm_keyframe_decision_batch(avm_ctx* c, avm_mem mem, const avm_window_batch* batch, double min_parallax, int32_t* flags, int32_t* last_track_num,

@@ -253,8 +253,27 @@ hipError_t launch_fsel_horizon_imu(const avm_fsel_horizon_in& in, double* hor_po
 hipError_t launch_triangulate(const avm_window_batch& b, double init_depth, hipStream_t stream, int zero_tic = 0, const int32_t* only = nullptr);
 hipError_t launch_imu_propagate(const avm_window_batch& b, const double* g, hipStream_t stream);
 // flags: [B] device, or null: every window takes `flag`; remove_failures: FeatureManager::removeFailures() behind the roll
+// feat_id ([B][max_feat] device, nullable): compacted with the per-feature arrays; move_td: removeFront shifts b.obs_vel_td with obs_xy
 hipError_t launch_slide_window(const avm_window_batch& b, const int32_t* flags, int flag, int shift_depth, double init_depth, int remove_failures,
-                               int* err, hipStream_t stream);
+                               int* err, hipStream_t stream, int32_t* feat_id = nullptr, int move_td = 0);
+
+// ---- the feature manager on device-resident tables (tracks.hip) ----------------------------------------------------------------------
+// The checks write first_bad like launch_validate_windows: it stays as it was while every window passes, else min over the failing
+// windows of (window * 8 + rule).  They index with n_feat / the track tables, which the caller has validated (CHK_TRACKS / CHK_IMU).
+enum { TRK_BAD_NPTS = 1, TRK_BAD_IDS = 2, TRK_BAD_FULL = 3, TRK_BAD_LOST = 4, TRK_BAD_DUP = 5, TRK_CAP_FEAT = 6, TRK_CAP_OBS = 7 };  // add_image
+enum { PUSH_BAD_N = 1, PUSH_CAP = 2 };                                                                                                // imu_push
+enum { VIEW_CAP_FEAT = 1, VIEW_CAP_OBS = 2 };                                                                                         // solve_view
+enum { DEPTH_BAD_NFEAT = 1, DEPTH_BAD_ROW = 2 };                                                                                      // store_depths
+hipError_t launch_add_image_check(const avm_window_batch& b, const int32_t* feat_id, const avm_image_batch& img, int* first_bad, hipStream_t stream);
+hipError_t launch_add_image(const avm_window_batch& b, int32_t* feat_id, const avm_image_batch& img, hipStream_t stream);
+hipError_t launch_imu_push_check(const avm_window_batch& b, const int32_t* n, int max_in, int* first_bad, hipStream_t stream);
+hipError_t launch_imu_push(const avm_window_batch& b, const int32_t* n, int max_in, const double* dt, const double* acc, const double* gyr,
+                           hipStream_t stream);
+hipError_t launch_solve_view_check(const avm_window_batch& full, const avm_window_batch& view, int* first_bad, hipStream_t stream);
+hipError_t launch_solve_view(const avm_window_batch& full, const avm_window_batch& view, int32_t* view_row, hipStream_t stream);
+hipError_t launch_store_depths_check(const avm_window_batch& full, const avm_window_batch& view, const int32_t* view_row, int* first_bad,
+                                     hipStream_t stream);
+hipError_t launch_store_depths(const avm_window_batch& full, const avm_window_batch& view, const int32_t* view_row, hipStream_t stream);
 // FeatureManager::addFeatureCheckParallax's return value per window; last_track_num / parallax ([B][2]: sum, num) may be null
 hipError_t launch_keyframe_decision(const avm_window_batch& b, double min_parallax, int32_t* flags, int32_t* last_track_num, double* parallax,
                                     hipStream_t stream);

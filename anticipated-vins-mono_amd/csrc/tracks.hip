@@ -1,0 +1,373 @@
+// tracks.hip — the feature manager's per-image bookkeeping on device-resident tables (include/avm.h, "the feature manager on
+// device-resident tables"): FeatureManager::addFeatureCheckParallax's append by feature id (feature_manager.cpp:45-72), the buffer half of
+// Estimator::processIMU (estimator.cpp:92-98), the solve's filtered view of the whole list (estimator.cpp:715) and setDepth's copy back
+// (feature_manager.cpp:141-159).  Integer bookkeeping and copies only: no floating-point operation in this file.
+// One 256-thread workgroup per window in the kernels that walk a list; every call has a check kernel of the same shape that runs first,
+// on its own, and writes nothing but the verdict (kernels.hpp), so that a refused batch leaves every table of every window as it was.
+#include "devmath.hpp"
+#include "kernels.hpp"
+
+namespace avm {
+namespace {
+
+constexpr int TRK_NT = 256;
+constexpr int TRK_WAVES = TRK_NT / 64;
+constexpr int TRK_SLOTS = (AVM_MAX_OBS_WIDE + TRK_NT - 1) / TRK_NT;  // 17 observation slots per thread
+constexpr int TRK_MAX_CHUNKS = AVM_MAX_IMAGE_PTS / 64;               // 16 (the rows of a window: 6)
+static_assert(AVM_MAX_IMAGE_PTS % 64 == 0 && AVM_MAX_FEAT_WIDE <= AVM_MAX_IMAGE_PTS, "chunk totals are sized by the image");
+
+// inclusive prefix sum over the wavefront, every lane active: the shift ladder of wave_sum_shr with each lane keeping its partial sum
+AVM_DEV int wave_scan_incl(int v) {
+  v += dpp_mov<0x111>(v);       // row_shr:1
+  v += dpp_mov<0x112>(v);       // row_shr:2
+  v += dpp_mov<0x114>(v);       // row_shr:4
+  v += dpp_mov<0x118>(v);       // row_shr:8   -> every lane holds the sum of its row up to itself
+  v += dpp_mov<0x142, 0xa>(v);  // row_bcast:15 -> rows 1 and 3 add the row in front of them
+  v += dpp_mov<0x143, 0xc>(v);  // row_bcast:31 -> rows 2 and 3 add rows 0 + 1
+  return v;
+}
+
+// out[i] = in[0] + ... + in[i - 1] for i <= n (out[n]: the total); tot: TRK_MAX_CHUNKS ints of LDS.  Ends with a workgroup barrier.
+AVM_DEV void block_scan_excl(const int* in, int* out, int n, int* tot) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = wave; c * 64 < n; c += TRK_WAVES) {  // (wave-uniform bounds: the DPP ladder runs with every lane active)
+    const int i = c * 64 + lane, v = i < n ? in[i] : 0;
+    const int s = wave_scan_incl(v);
+    if (i < n) out[i] = s - v;
+    if (lane == 63) tot[c] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i <= n; i += TRK_NT) {
+    const int chunks = i < n ? i >> 6 : (n + 63) >> 6;  // the chunks in front of item i; all of them for the total
+    int base = 0;
+    for (int c = 0; c < chunks; c++) base += tot[c];
+    out[i] = (i < n ? out[i] : 0) + base;
+  }
+  __syncthreads();
+}
+
+// The items i < n with pred(i), ranked in index order: emit(i, rank) for each, the count returned to every thread.  Ballot / popcount per
+// 64-item chunk, the chunk totals through `tot` (TRK_MAX_CHUNKS ints of LDS).  pred is evaluated twice; ends with a workgroup barrier.
+template <class Pred, class Emit>
+AVM_DEV int block_compact(int n, int* tot, Pred pred, Emit emit) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = wave; c * 64 < n; c += TRK_WAVES) {
+    const int i = c * 64 + lane;
+    const unsigned long long m = __ballot(i < n && pred(i));
+    if (lane == 0) tot[c] = __popcll(m);
+  }
+  __syncthreads();
+  int total = 0;
+  for (int c = 0; c * 64 < n; c++) total += tot[c];
+  for (int c = wave; c * 64 < n; c += TRK_WAVES) {
+    const int i = c * 64 + lane;
+    const bool f = i < n && pred(i);
+    const unsigned long long m = __ballot(f);
+    int base = 0;
+    for (int k = 0; k < c; k++) base += tot[k];
+    if (f) emit(i, base + __popcll(m & ((1ull << lane) - 1ull)));
+  }
+  __syncthreads();
+  return total;
+}
+
+// position of `id` in the ascending ids[0 .. n), or -1 (memory-safe on any input)
+AVM_DEV int find_id(const int* ids, int n, int id) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ids[mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return (lo < n && ids[lo] == id) ? lo : -1;
+}
+
+// the row e < n_rows with begin[e] <= d < begin[e + 1] (begin strictly ascending from 0: every row has an observation)
+AVM_DEV int row_of_slot(const int* begin, int n_rows, int d) {
+  int lo = 0, hi = n_rows;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (begin[mid] <= d) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+typedef double d2 __attribute__((ext_vector_type(2)));  // one observation (d4, devmath.hpp: its obs_vel_td row)
+
+// The barrier between "every thread has read its sources" and "the first destination is written" of a move that overlaps itself.  A
+// workgroup barrier alone lets a wavefront's global loads still be in flight when another wavefront's stores issue: wait until the values
+// are in the registers first (s_waitcnt vmcnt(0), expcnt and lgkmcnt left alone).
+AVM_DEV void sources_read_barrier() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __syncthreads();
+}
+
+AVM_DEV void report(int* first_bad, int w, int rule) { atomicMin(first_bad, w * 8 + rule); }
+
+// ---- avm_add_image_batch ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TRK_NT) void add_image_check_kernel(avm_window_batch B, const int32_t* feat_id, avm_image_batch I, int* first_bad) {
+  __shared__ int s_id[AVM_MAX_IMAGE_PTS], s_fid[AVM_MAX_FEAT_WIDE], s_bad, s_matched, s_obs;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int np = I.n_pts[w], nf = B.n_feat[w];
+  if (np < 0 || np > I.max_pts) {  // (uniform over the workgroup: nothing below indexes with it)
+    if (tid == 0) report(first_bad, w, TRK_BAD_NPTS);
+    return;
+  }
+  if (tid == 0) s_bad = 1 << 30, s_matched = 0, s_obs = 0;
+  const int32_t* ids = I.feature_id + (size_t)w * I.max_pts;
+  const int32_t* fid = feat_id + (size_t)w * B.max_feat;
+  const int32_t* fstart = B.feat_start + (size_t)w * B.max_feat;
+  const int32_t* fnobs = B.feat_nobs + (size_t)w * B.max_feat;
+  int bad = 1 << 30;
+  for (int i = tid; i < np; i += TRK_NT) {
+    s_id[i] = ids[i];
+    if (i > 0 && ids[i] <= ids[i - 1]) bad = min(bad, (int)TRK_BAD_IDS);
+  }
+  for (int e = tid; e < nf; e += TRK_NT) s_fid[e] = fid[e];
+  __syncthreads();
+  int matched = 0, obs = 0;
+  for (int e = tid; e < nf; e += TRK_NT) {
+    const int st = fstart[e], no = fnobs[e], id = s_fid[e];
+    obs += no;
+    if (st + no > AVM_WINDOW_SIZE) bad = min(bad, (int)TRK_BAD_FULL);
+    for (int j = 0; j < e; j++)
+      if (s_fid[j] == id) bad = min(bad, (int)TRK_BAD_DUP);
+    if (find_id(s_id, np, id) >= 0) {
+      matched++;
+      if (st + no < AVM_WINDOW_SIZE) bad = min(bad, (int)TRK_BAD_LOST);
+    }
+  }
+  atomicAdd(&s_matched, matched), atomicAdd(&s_obs, obs);
+  if (bad != 1 << 30) atomicMin(&s_bad, bad);
+  __syncthreads();
+  if (tid != 0) return;
+  bad = s_bad;
+  if (nf + (np - s_matched) > B.max_feat) bad = min(bad, (int)TRK_CAP_FEAT);
+  if (s_obs + np > B.max_obs) bad = min(bad, (int)TRK_CAP_OBS);
+  if (bad != 1 << 30) report(first_bad, w, bad);
+}
+
+// The append and the dense rewrite of one window's observation table.  The move overlaps itself in both directions (rows move left over
+// the roll's holes and right past the appended observations), so every source is read into registers before the barrier behind which the
+// first destination is written: TRK_SLOTS slots per thread, obs_xy and obs_vel_td each in a pass of their own.
+__global__ __launch_bounds__(TRK_NT) void add_image_kernel(avm_window_batch B, int32_t* feat_id, avm_image_batch I) {
+  __shared__ int s_id[AVM_MAX_IMAGE_PTS], s_mark[AVM_MAX_IMAGE_PTS];  // the image's ids; 1: the point extended a track of the list
+  // per row of the NEW list: the image point it takes (-1: none), its old feat_obs_begin, its new feat_nobs, its new feat_obs_begin
+  __shared__ int s_pt[AVM_MAX_FEAT_WIDE], s_ob[AVM_MAX_FEAT_WIDE], s_no[AVM_MAX_FEAT_WIDE], s_begin[AVM_MAX_FEAT_WIDE + 1];
+  __shared__ int s_tot[TRK_MAX_CHUNKS];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int np = I.n_pts[w], nf = B.n_feat[w];
+  const int32_t* ids = I.feature_id + (size_t)w * I.max_pts;
+  const double* ixy = I.xy + (size_t)w * I.max_pts * 2;
+  int32_t* fid = feat_id + (size_t)w * B.max_feat;
+  int32_t* fstart = const_cast<int32_t*>(B.feat_start) + (size_t)w * B.max_feat;
+  int32_t* fnobs = const_cast<int32_t*>(B.feat_nobs) + (size_t)w * B.max_feat;
+  int32_t* fobs = const_cast<int32_t*>(B.feat_obs_begin) + (size_t)w * B.max_feat;
+  double* obs = const_cast<double*>(B.obs_xy) + (size_t)w * B.max_obs * 2;
+  double* lam = B.inv_depth + (size_t)w * B.max_feat;
+  for (int i = tid; i < np; i += TRK_NT) s_id[i] = ids[i], s_mark[i] = 0;
+  __syncthreads();
+  // every row of the list looks its id up in the image (find_if over the list per point, the other way round)
+  for (int e = tid; e < nf; e += TRK_NT) {
+    const int p = find_id(s_id, np, fid[e]);
+    if (p >= 0) s_mark[p] = 1;
+    s_pt[e] = p, s_ob[e] = fobs[e], s_no[e] = fnobs[e] + (p >= 0 ? 1 : 0);
+  }
+  __syncthreads();
+  // the new tracks: the unmarked points in image order (ascending id), behind the list
+  const int n_new = block_compact(np, s_tot, [&](int i) { return s_mark[i] == 0; },
+                                  [&](int i, int rank) {
+                                    const int e = nf + rank;
+                                    s_pt[e] = i, s_ob[e] = 0, s_no[e] = 1;
+                                    fid[e] = s_id[i], fstart[e] = AVM_WINDOW_SIZE, lam[e] = -1.0;
+                                  });
+  const int nf2 = nf + n_new;
+  block_scan_excl(s_no, s_begin, nf2, s_tot);
+  const int total = s_begin[nf2];
+  // where every slot of the new table comes from: >= 0 a slot of the old table, < 0 the image point ~src
+  // (sfor: the slot index is a constant in the source, so that src and v are registers and never an array in scratch memory)
+  int src[TRK_SLOTS];
+  sfor<TRK_SLOTS>([&](auto K) {
+    constexpr int k = K;
+    const int d = tid + k * TRK_NT;
+    src[k] = 0;
+    if (d < total) {
+      const int e = row_of_slot(s_begin, nf2, d), j = d - s_begin[e];
+      const int old_no = s_no[e] - (s_pt[e] >= 0 ? 1 : 0);
+      src[k] = j < old_no ? s_ob[e] + j : ~s_pt[e];
+    }
+  });
+  {
+    d2 v[TRK_SLOTS];
+    sfor<TRK_SLOTS>([&](auto K) {
+      constexpr int k = K;
+      if (tid + k * TRK_NT < total) v[k] = *reinterpret_cast<const d2*>(src[k] >= 0 ? obs + 2 * (size_t)src[k] : ixy + 2 * (size_t)(~src[k]));
+    });
+    sources_read_barrier();
+    sfor<TRK_SLOTS>([&](auto K) {
+      constexpr int k = K;
+      if (tid + k * TRK_NT < total) *reinterpret_cast<d2*>(obs + 2 * (size_t)(tid + k * TRK_NT)) = v[k];
+    });
+  }
+  if (B.obs_vel_td) {
+    double* vtd = const_cast<double*>(B.obs_vel_td) + (size_t)w * B.max_obs * 4;
+    const double* itd = I.vel_td + (size_t)w * I.max_pts * 4;
+    d4 v[TRK_SLOTS];
+    sfor<TRK_SLOTS>([&](auto K) {
+      constexpr int k = K;
+      if (tid + k * TRK_NT < total) v[k] = *reinterpret_cast<const d4*>(src[k] >= 0 ? vtd + 4 * (size_t)src[k] : itd + 4 * (size_t)(~src[k]));
+    });
+    sources_read_barrier();
+    sfor<TRK_SLOTS>([&](auto K) {
+      constexpr int k = K;
+      if (tid + k * TRK_NT < total) *reinterpret_cast<d4*>(vtd + 4 * (size_t)(tid + k * TRK_NT)) = v[k];
+    });
+  }
+  for (int e = tid; e < nf2; e += TRK_NT) fnobs[e] = s_no[e], fobs[e] = s_begin[e];
+  if (tid == 0) const_cast<int32_t*>(B.n_feat)[w] = nf2;
+}
+
+// ---- avm_imu_push_batch --------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void imu_push_check_kernel(avm_window_batch B, const int32_t* n, int max_in, int* first_bad) {
+  const int w = blockIdx.x * 64 + threadIdx.x;
+  if (w >= B.n_windows) return;
+  if (n[w] < 0 || n[w] > max_in) report(first_bad, w, PUSH_BAD_N);
+  else if (B.imu_n[(size_t)w * 10 + 9] + n[w] > B.max_samp) report(first_bad, w, PUSH_CAP);
+}
+
+__global__ __launch_bounds__(64) void imu_push_kernel(avm_window_batch B, const int32_t* n, int max_in, const double* dt, const double* acc,
+                                                      const double* gyr) {
+  const int w = blockIdx.x, lane = threadIdx.x;
+  const int SD = B.max_samp, SA = (B.max_samp + 1) * 3;
+  int32_t* imu_n = const_cast<int32_t*>(B.imu_n) + (size_t)w * 10;
+  double* wdt = const_cast<double*>(B.imu_dt) + ((size_t)w * 10 + 9) * SD;
+  double* wacc = const_cast<double*>(B.imu_acc) + ((size_t)w * 10 + 9) * SA;
+  double* wgyr = const_cast<double*>(B.imu_gyr) + ((size_t)w * 10 + 9) * SA;
+  const int n9 = imu_n[9], m = n[w];
+  for (int k = lane; k < m; k += 64) wdt[n9 + k] = dt[(size_t)w * max_in + k];
+  for (int k = lane; k < 3 * m; k += 64)  // (row 0 is the sample the interval was constructed with)
+    wacc[(n9 + 1) * 3 + k] = acc[(size_t)w * max_in * 3 + k], wgyr[(n9 + 1) * 3 + k] = gyr[(size_t)w * max_in * 3 + k];
+  __syncthreads();  // (every lane has read imu_n[9])
+  if (lane == 0) imu_n[9] = n9 + m;
+}
+
+// ---- avm_solve_view_batch / avm_solve_view_store_depths ---------------------------------------------------------------------------------
+AVM_DEV bool in_view(int st, int no) { return no >= 2 && st < AVM_WINDOW_SIZE - 2; }  // estimator.cpp:715
+
+__global__ __launch_bounds__(TRK_NT) void solve_view_check_kernel(avm_window_batch F, avm_window_batch V, int* first_bad) {
+  __shared__ int s_rows, s_obs;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) s_rows = 0, s_obs = 0;
+  __syncthreads();
+  const int nf = F.n_feat[w];
+  int rows = 0, obs = 0;
+  for (int e = tid; e < nf; e += TRK_NT) {
+    const int st = F.feat_start[(size_t)w * F.max_feat + e], no = F.feat_nobs[(size_t)w * F.max_feat + e];
+    if (in_view(st, no)) rows++, obs += no;
+  }
+  atomicAdd(&s_rows, rows), atomicAdd(&s_obs, obs);
+  __syncthreads();
+  if (tid != 0) return;
+  if (s_rows > V.max_feat) report(first_bad, w, VIEW_CAP_FEAT);
+  else if (s_obs > V.max_obs) report(first_bad, w, VIEW_CAP_OBS);
+}
+
+__global__ __launch_bounds__(TRK_NT) void solve_view_kernel(avm_window_batch F, avm_window_batch V, int32_t* view_row) {
+  __shared__ int s_row[AVM_MAX_FEAT], s_no[AVM_MAX_FEAT], s_begin[AVM_MAX_FEAT + 1], s_tot[TRK_MAX_CHUNKS];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int nf = F.n_feat[w];
+  const int32_t* fstart = F.feat_start + (size_t)w * F.max_feat;
+  const int32_t* fnobs = F.feat_nobs + (size_t)w * F.max_feat;
+  const int32_t* fobs = F.feat_obs_begin + (size_t)w * F.max_feat;
+  const size_t vf = (size_t)w * V.max_feat, vo = (size_t)w * V.max_obs;
+  int32_t* vstart = const_cast<int32_t*>(V.feat_start) + vf;
+  int32_t* vnobs = const_cast<int32_t*>(V.feat_nobs) + vf;
+  int32_t* vobs = const_cast<int32_t*>(V.feat_obs_begin) + vf;
+  const int nv = block_compact(nf, s_tot, [&](int e) { return in_view(fstart[e], fnobs[e]); },
+                               [&](int e, int k) {
+                                 s_row[k] = e, s_no[k] = fnobs[e];
+                                 view_row[vf + k] = e, vstart[k] = fstart[e], vnobs[k] = fnobs[e];
+                                 V.inv_depth[vf + k] = F.inv_depth[(size_t)w * F.max_feat + e];
+                               });
+  block_scan_excl(s_no, s_begin, nv, s_tot);
+  const int total = s_begin[nv];
+  for (int k = tid; k < nv; k += TRK_NT) vobs[k] = s_begin[k];
+  if (tid == 0) const_cast<int32_t*>(V.n_feat)[w] = nv;
+  const double* fxy = F.obs_xy + (size_t)w * F.max_obs * 2;
+  double* vxy = const_cast<double*>(V.obs_xy) + vo * 2;
+  const double* ftd = V.obs_vel_td ? F.obs_vel_td + (size_t)w * F.max_obs * 4 : nullptr;
+  double* vtd = V.obs_vel_td ? const_cast<double*>(V.obs_vel_td) + vo * 4 : nullptr;
+  for (int d = tid; d < total; d += TRK_NT) {
+    const int k = row_of_slot(s_begin, nv, d);
+    const size_t s = (size_t)fobs[s_row[k]] + (d - s_begin[k]);
+    *reinterpret_cast<d2*>(vxy + 2 * (size_t)d) = *reinterpret_cast<const d2*>(fxy + 2 * s);
+    if (vtd) *reinterpret_cast<d4*>(vtd + 4 * (size_t)d) = *reinterpret_cast<const d4*>(ftd + 4 * s);
+  }
+}
+
+__global__ __launch_bounds__(64) void store_depths_check_kernel(avm_window_batch F, avm_window_batch V, const int32_t* view_row, int* first_bad) {
+  const int w = blockIdx.x, lane = threadIdx.x;
+  const int nf = F.n_feat[w], nv = V.n_feat[w];
+  if (nf < 0 || nf > F.max_feat || nv < 0 || nv > V.max_feat) {
+    if (lane == 0) report(first_bad, w, DEPTH_BAD_NFEAT);
+    return;
+  }
+  const int32_t* row = view_row + (size_t)w * V.max_feat;
+  bool bad = false;
+  for (int k = lane; k < nv; k += 64) bad = bad || row[k] < 0 || row[k] >= nf || (k > 0 && row[k] <= row[k - 1]);
+  if (bad) report(first_bad, w, DEPTH_BAD_ROW);
+}
+
+__global__ __launch_bounds__(TRK_NT) void store_depths_kernel(avm_window_batch F, avm_window_batch V, const int32_t* view_row) {
+  const int w = blockIdx.x;
+  const int nv = V.n_feat[w];
+  for (int k = threadIdx.x; k < nv; k += TRK_NT)
+    F.inv_depth[(size_t)w * F.max_feat + view_row[(size_t)w * V.max_feat + k]] = V.inv_depth[(size_t)w * V.max_feat + k];
+}
+
+}  // namespace
+
+hipError_t launch_add_image_check(const avm_window_batch& b, const int32_t* feat_id, const avm_image_batch& img, int* first_bad, hipStream_t stream) {
+  hipLaunchKernelGGL(add_image_check_kernel, dim3(b.n_windows), dim3(TRK_NT), 0, stream, b, feat_id, img, first_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_add_image(const avm_window_batch& b, int32_t* feat_id, const avm_image_batch& img, hipStream_t stream) {
+  hipLaunchKernelGGL(add_image_kernel, dim3(b.n_windows), dim3(TRK_NT), 0, stream, b, feat_id, img);
+  return hipGetLastError();
+}
+
+hipError_t launch_imu_push_check(const avm_window_batch& b, const int32_t* n, int max_in, int* first_bad, hipStream_t stream) {
+  hipLaunchKernelGGL(imu_push_check_kernel, dim3((b.n_windows + 63) / 64), dim3(64), 0, stream, b, n, max_in, first_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_imu_push(const avm_window_batch& b, const int32_t* n, int max_in, const double* dt, const double* acc, const double* gyr,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(imu_push_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, n, max_in, dt, acc, gyr);
+  return hipGetLastError();
+}
+
+hipError_t launch_solve_view_check(const avm_window_batch& full, const avm_window_batch& view, int* first_bad, hipStream_t stream) {
+  hipLaunchKernelGGL(solve_view_check_kernel, dim3(full.n_windows), dim3(TRK_NT), 0, stream, full, view, first_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_solve_view(const avm_window_batch& full, const avm_window_batch& view, int32_t* view_row, hipStream_t stream) {
+  hipLaunchKernelGGL(solve_view_kernel, dim3(full.n_windows), dim3(TRK_NT), 0, stream, full, view, view_row);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_depths_check(const avm_window_batch& full, const avm_window_batch& view, const int32_t* view_row, int* first_bad,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(store_depths_check_kernel, dim3(full.n_windows), dim3(64), 0, stream, full, view, view_row, first_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_depths(const avm_window_batch& full, const avm_window_batch& view, const int32_t* view_row, hipStream_t stream) {
+  hipLaunchKernelGGL(store_depths_kernel, dim3(full.n_windows), dim3(TRK_NT), 0, stream, full, view, view_row);
+  return hipGetLastError();
+}
+
+}  // namespace avm

@@ -167,8 +167,10 @@ hipError_t launch_imu_propagate(const avm_window_batch& b, const double* g, hipS
 // remove_failures: f_manager.removeFailures() behind the roll (estimator.cpp:197-198): a feature that went through the solve's filter
 // with a negative inverse depth - setDepth's solve_flag == 2, feature_manager.cpp:141-159, decided on the tables as they are BEFORE
 // the roll - is erased, whatever the roll did to it.
+// feat_id (nullable): the ids of the rows, compacted with them.  move_td: removeFront shifts the rows of obs_vel_td with those of obs_xy
+// (avm_slide_window_tracks; the older entry points pass null / 0 and leave obs_vel_td alone).
 __global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, const int32_t* flags, int flag_all, int shift_depth, double init_depth,
-                                                          int remove_failures, int* err) {
+                                                          int remove_failures, int* err, int32_t* feat_id, int move_td) {
   const int w = blockIdx.x, lane = threadIdx.x;
   const int flag = flags ? flags[w] : flag_all;
   double* pose = B.pose + (size_t)w * NFR * 7;
@@ -231,6 +233,8 @@ __global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, co
   int32_t* fobs = const_cast<int32_t*>(B.feat_obs_begin) + (size_t)w * B.max_feat;
   double* obs = const_cast<double*>(B.obs_xy) + (size_t)w * B.max_obs * 2;
   double* lam = B.inv_depth + (size_t)w * B.max_feat;
+  int32_t* fid = feat_id ? feat_id + (size_t)w * B.max_feat : nullptr;
+  double* vtd = (move_td && B.obs_vel_td) ? const_cast<double*>(B.obs_vel_td) + (size_t)w * B.max_obs * 4 : nullptr;
   const double* ex = B.ex_pose + (size_t)w * 7;
   double ric[9], Rb[9], Rn[9];
   q2R(quat{ex[6], ex[3], ex[4], ex[5]}, ric);
@@ -272,19 +276,26 @@ __global__ __launch_bounds__(64) void slide_window_kernel(avm_window_batch B, co
       } else if (st + no - 1 >= NFR - 2) {  // endFrame() >= frame_count - 1: it has an observation in frame 9
         const int j = NFR - 2 - st;
         for (int k = j; k + 1 < no; k++) obs[2 * (ob + k)] = obs[2 * (ob + k + 1)], obs[2 * (ob + k) + 1] = obs[2 * (ob + k + 1) + 1];
+        if (vtd)
+          for (int k = j; k + 1 < no; k++)
+            for (int i = 0; i < 4; i++) vtd[4 * (ob + k) + i] = vtd[4 * (ob + k + 1) + i];
         no--;
         if (no == 0) keep = false;
       }
     }
-    if (keep && !failure) fstart[o] = st, fnobs[o] = no, fobs[o] = ob, lam[o] = l, o++;
+    if (keep && !failure) {
+      if (fid) fid[o] = fid[e];
+      fstart[o] = st, fnobs[o] = no, fobs[o] = ob, lam[o] = l, o++;
+    }
   }
   *n_feat = o;
 }
 
 hipError_t launch_slide_window(const avm_window_batch& b, const int32_t* flags, int flag, int shift_depth, double init_depth, int remove_failures,
-                               int* err, hipStream_t stream) {
+                               int* err, hipStream_t stream, int32_t* feat_id, int move_td) {
   if (b.n_windows == 0) return hipSuccess;
-  hipLaunchKernelGGL(slide_window_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, flags, flag, shift_depth, init_depth, remove_failures, err);
+  hipLaunchKernelGGL(slide_window_kernel, dim3(b.n_windows), dim3(64), 0, stream, b, flags, flag, shift_depth, init_depth, remove_failures, err,
+                     feat_id, move_td);
   return hipGetLastError();
 }
 

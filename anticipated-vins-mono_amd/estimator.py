@@ -173,13 +173,72 @@ class Estimator:
         rc = self.ctx._L.avm_imu_propagate_batch(self.ctx.h, windows.mem, C.byref(s), g)
         self.ctx.check(rc, "avm_imu_propagate_batch")
 
-    def slideWindow(self, windows: buffers.WindowArrays, marginalization_flag=None, shift_depth=True, init_depth=5.0, remove_failures=False):
+    def _like(self, windows, x, dtype):
+        """x as a contiguous array of `dtype` in the memory space of `windows`"""
+        if windows.on_device:
+            import torch
+
+            td = torch.int32 if dtype == np.int32 else torch.float64
+            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype))
+            return t.to(device="cuda:%d" % self.ctx.device, dtype=td).contiguous()
+        return np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x, dtype)
+
+    def push_imu(self, windows: buffers.WindowArrays, n, dt, acc, gyr):
+        """The buffer half of Estimator::processIMU (estimator.cpp:92-98) for the samples between two images: n [B] samples per window,
+        dt [B, max_in], acc / gyr [B, max_in, 3], appended to interval WINDOW_SIZE - 1 in place.  imu_propagate() is the other half."""
+        n, dt, acc, gyr = self._like(windows, n, np.int32), self._like(windows, dt, np.float64), self._like(windows, acc, np.float64), self._like(windows, gyr, np.float64)
+        B, max_in = windows.n_windows, int(dt.shape[1])
+        assert tuple(n.shape) == (B,) and tuple(dt.shape) == (B, max_in) and tuple(acc.shape) == tuple(gyr.shape) == (B, max_in, 3)
+        s = windows.struct()
+        rc = self.ctx._L.avm_imu_push_batch(self.ctx.h, windows.mem, C.byref(s), abi.iptr(n), max_in, abi.dptr(dt), abi.dptr(acc), abi.dptr(gyr))
+        self.ctx.check(rc, "avm_imu_push_batch")
+
+    # the reference's name
+    def addFeatureCheckParallax(self, full: buffers.WindowArrays, feat_id, image: buffers.ImageArrays, min_parallax: float):
+        """FeatureManager::addFeatureCheckParallax (feature_manager.cpp:45-96) on the full tables, in place: every image point is appended
+        to the track of its id in feat_id [B, max_feat] or starts a new row, the observation table is rewritten dense in list order.
+        Returns keyframe_decision()'s (marginalization_flags, last_track_num, parallax) on the result."""
+        B = full.n_windows
+        assert image.n_windows == B and image.on_device == full.on_device and tuple(feat_id.shape) == (B, full.dims["max_feat"])
+        flags, ltn, par = self._out_like(full, (B,), np.int32), self._out_like(full, (B,), np.int32), self._out_like(full, (B, 2), np.float64)
+        s, si = full.struct(), image.struct()
+        rc = self.ctx._L.avm_add_image_batch(self.ctx.h, full.mem, C.byref(s), abi.iptr(feat_id), C.byref(si), float(min_parallax), abi.iptr(flags),
+                                             abi.iptr(ltn), abi.dptr(par))
+        self.ctx.check(rc, "avm_add_image_batch")
+        return flags, ltn, par
+
+    def solve_view(self, tables: buffers.TrackTables) -> buffers.WindowArrays:
+        """The rows of tables.full that pass used_num >= 2 && start_frame < WINDOW_SIZE - 2 (estimator.cpp:715), gathered into
+        tables.view (and tables.view_row): what triangulate() and optimization() take.  Returns tables.view."""
+        sf, sv = tables.full.struct(), tables.view.struct()
+        rc = self.ctx._L.avm_solve_view_batch(self.ctx.h, tables.full.mem, C.byref(sf), C.byref(sv), abi.iptr(tables.view_row))
+        self.ctx.check(rc, "avm_solve_view_batch")
+        return tables.view
+
+    # the reference's name
+    def setDepth(self, tables: buffers.TrackTables):
+        """FeatureManager::setDepth's copy (feature_manager.cpp:141-159): the inverse depths of tables.view back into the rows of
+        tables.full they came from."""
+        sf, sv = tables.full.struct(), tables.view.struct()
+        rc = self.ctx._L.avm_solve_view_store_depths(self.ctx.h, tables.full.mem, C.byref(sf), C.byref(sv), abi.iptr(tables.view_row))
+        self.ctx.check(rc, "avm_solve_view_store_depths")
+
+    def slideWindow(self, windows: buffers.WindowArrays, marginalization_flag=None, shift_depth=True, init_depth=5.0, remove_failures=False,
+                    feat_id=None):
         """Estimator::slideWindow (estimator.cpp:996-1107) + removeBackShiftDepth / removeBack / removeFront
         (feature_manager.cpp:275-352), in place on the batch tables (host or device resident).  marginalization_flag: one int for the
         batch, or an array / tensor of B flags, one per window.  remove_failures: f_manager.removeFailures() behind the roll
-        (estimator.cpp:197-198): the features the solve left with a negative inverse depth are erased."""
+        (estimator.cpp:197-198): the features the solve left with a negative inverse depth are erased.  feat_id [B, max_feat] (where
+        the windows live): the ids of the rows, compacted with them; the rows of obs_vel_td then move with their observations."""
         flag = self.options.marginalization_flag if marginalization_flag is None else marginalization_flag
         s = windows.struct()
+        if feat_id is not None:
+            assert tuple(feat_id.shape) == (windows.n_windows, windows.dims["max_feat"])
+            flags = self._flags_like(windows, np.full(windows.n_windows, int(flag), np.int32) if np.ndim(flag) == 0 else flag)
+            rc = self.ctx._L.avm_slide_window_tracks(self.ctx.h, windows.mem, C.byref(s), abi.iptr(feat_id), abi.iptr(flags), int(bool(shift_depth)),
+                                                     float(init_depth), int(bool(remove_failures)))
+            self.ctx.check(rc, "avm_slide_window_tracks")
+            return
         if np.ndim(flag) == 0 and not remove_failures:
             rc = self.ctx._L.avm_slide_window(self.ctx.h, windows.mem, C.byref(s), int(flag), int(bool(shift_depth)), float(init_depth))
             self.ctx.check(rc, "avm_slide_window")

@@ -76,8 +76,9 @@ def lib():
         L.avm_visual_initial_align_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.AlignBatch), C.POINTER(abi.WindowBatch),
                                                      C.POINTER(abi.AlignOut)]
         L.avm_debug_align_layout.argtypes = [C.POINTER(C.c_int)]
-        for name, argtypes in abi.PROTOTYPES.items():
+        for name, argtypes in list(abi.PROTOTYPES.items()) + list(abi.TRACK_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
+        L.avm_debug_track_struct_sizes.argtypes = [C.POINTER(C.c_int)]
         L.avm_comm_unique_id.argtypes = [vp, C.c_void_p]
         L.avm_comm_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_void_p]
         L.avm_gather_states.argtypes = [vp, abi.c_dp, abi.c_dp, C.c_size_t]
@@ -102,6 +103,7 @@ EXPORTS = [
     "avm_ctx_stream", "avm_comm_unique_id", "avm_comm_init", "avm_gather_states", "avm_comm_destroy", "avm_gt_load_csv", "avm_gt_from_rows", "avm_gt_free", "avm_gt_size", "avm_gt_seek", "avm_fsel_horizon_ground_truth", "avm_image_from_pointcloud", "avm_slide_window",
     "avm_visual_initial_align_batch",
     "avm_window_solve_batch_flags", "avm_slide_window_flags", "avm_keyframe_decision_batch", "avm_failure_detection_batch",
+    "avm_add_image_batch", "avm_imu_push_batch", "avm_solve_view_batch", "avm_solve_view_store_depths", "avm_slide_window_tracks",
 ]
 
 

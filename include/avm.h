@@ -434,7 +434,8 @@ int avm_fsel_build_cloud(avm_ctx* ctx, avm_mem mem, const avm_window_batch* wind
  *                          the others lose their frame-9 observation if they were still tracked in frame 9, and are
  *                          erased when none remains.
  * Erasing compacts the per-feature arrays in order (std::list order); observations stay where they are, only
- * feat_obs_begin / feat_nobs change (one element moves for removeFront).  inv_depth holds 1 / estimated_depth. */
+ * feat_obs_begin / feat_nobs change (one element moves for removeFront).  inv_depth holds 1 / estimated_depth.
+ * This entry point and avm_slide_window_flags do not move obs_vel_td: avm_slide_window_tracks does. */
 int avm_slide_window(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, int32_t marginalization_flag, int32_t shift_depth, double init_depth);
 
 /* The roll with a flag per window: marginalization_flags [B] in `mem` space, each AVM_MARGIN_OLD or AVM_MARGIN_SECOND_NEW (anything
@@ -472,6 +473,68 @@ int avm_keyframe_decision_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batc
  * frame's position after the previous image (estimator.cpp:209); reads windows->pose and windows->speedbias only. */
 int avm_failure_detection_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* windows, const double* last_P /* [B][3] */,
                                 int32_t* failed /* [B] out */);
+
+/* ---- the feature manager on device-resident tables: a batch of streams takes an image without a host rewriting its tables ----------
+ * Two kinds of tables.  The FULL tables hold the whole f_manager.feature list of every window: strides up to AVM_MAX_FEAT_WIDE /
+ * AVM_MAX_OBS_WIDE, every track of the list a row, in list order.  The keyframe decision, the roll and removeFailures work on them.
+ * The feature ids are a table BESIDE the batch, feat_id [B][max_feat] in `mem` space (the struct keeps its layout).  The VIEW is what
+ * the solve and the triangulation take: the rows with feat_nobs >= 2 && feat_start < WINDOW_SIZE - 2 (estimator.cpp:715), gathered
+ * into tables of the solve's strides by avm_solve_view_batch; avm_solve_view_store_depths carries the depths back (setDepth).
+ * Every call below takes frame_count == WINDOW_SIZE, validates every index table before a kernel indexes with it, and is all or nothing:
+ * on AVM_ERR_INVALID / AVM_ERR_CAPACITY the message names the first offending window and no table of any window has been written.
+ * avm_last_kernel_ms keys: "add_image", "imu_push", "solve_view", "store_depths" (device time of the checks and the kernels). */
+#define AVM_MAX_IMAGE_PTS 1024
+
+typedef struct avm_image_batch {      /* one image per window: the `image` map of processImage, camera 0 (id_pts.second[0]) */
+  int32_t n_windows, max_pts;         /* max_pts <= AVM_MAX_IMAGE_PTS */
+  const int32_t* n_pts;               /* [B] */
+  const int32_t* feature_id;          /* [B][max_pts] strictly ascending (std::map order) */
+  const double* xy;                   /* [B][max_pts][2] point.x, point.y (z == 1) */
+  const double* vel_td;               /* nullable [B][max_pts][4]: velocity.x, velocity.y, cur_td, uv.y - the layout of obs_vel_td;
+                                         must be given iff windows->obs_vel_td is */
+} avm_image_batch;
+
+/* FeatureManager::addFeatureCheckParallax (feature_manager.cpp:45-96) on the full tables.  For every image point, in ascending id order:
+ * an id found in feat_id[0 .. n_feat) gets the point appended to that track (feat_nobs + 1, its vel_td row with it); every other id
+ * starts a new row behind the list: feat_id = id, feat_start = WINDOW_SIZE, feat_nobs = 1, inv_depth = -1.0 (1 / estimated_depth with
+ * estimated_depth = -1, "no depth yet").  The observation table of the window is then rewritten dense in list order,
+ * feat_obs_begin[e] = feat_nobs[0] + ... + feat_nobs[e - 1] (the roll leaves holes; obs_vel_td moves with obs_xy when present); slots at
+ * and beyond the new total keep what they held.  Then the keyframe decision on the result - the kernel of avm_keyframe_decision_batch,
+ * so flags_out, last_track_num and parallax are that call's on the same tables, to the bit.
+ * AVM_ERR_INVALID: n_pts outside [0, max_pts]; ids not strictly ascending; a row with feat_start + feat_nobs > WINDOW_SIZE (the tables
+ * already hold an observation of frame 10); an id that matches a track whose last observation is not in frame WINDOW_SIZE - 1 (the
+ * reference would append it to the wrong frame; a tracker never re-issues a lost id); a duplicate in feat_id[0 .. n_feat).
+ * AVM_ERR_CAPACITY: n_feat + new tracks > max_feat, or the new total of observations > max_obs; max_pts > AVM_MAX_IMAGE_PTS. */
+int avm_add_image_batch(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, int32_t* feat_id /* [B][max_feat] in/out */,
+                        const avm_image_batch* image, double min_parallax, int32_t* flags_out /* [B] */,
+                        int32_t* last_track_num /* [B], nullable */, double* parallax /* [B][2], nullable */);
+
+/* The buffer half of Estimator::processIMU (estimator.cpp:92-98): n[w] samples are appended to interval WINDOW_SIZE - 1 of window w -
+ * imu_dt[9][imu_n ..], rows imu_n + 1 .. of imu_acc / imu_gyr, imu_n[9] += n.  n: [B], each in [0, max_in] (AVM_ERR_INVALID); dt
+ * [B][max_in], acc / gyr [B][max_in][3].  AVM_ERR_CAPACITY if a window would hold more than max_samp samples.  The dead-reckoning half
+ * is avm_imu_propagate_batch, called after it. */
+int avm_imu_push_batch(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, const int32_t* n, int32_t max_in, const double* dt,
+                       const double* acc, const double* gyr);
+
+/* The solve's view of the full tables.  `view` is a batch of the caller's with the solve's strides (max_feat <= AVM_MAX_FEAT, max_obs <=
+ * AVM_MAX_OBS, else AVM_ERR_CAPACITY); the library WRITES its n_feat, feat_start, feat_nobs, feat_obs_begin, obs_xy, inv_depth and, when
+ * view->obs_vel_td is given (then full->obs_vel_td must be), obs_vel_td - the const qualifiers are cast away as in avm_slide_window; these
+ * arrays must not be the full tables' own.  All its other pointers are the caller's business: normally they alias the full batch's.
+ * The rows of `full` with feat_nobs >= 2 && feat_start < WINDOW_SIZE - 2 are gathered in list order, their observations dense in that
+ * order; view_row[k] is the full row of view row k.  AVM_ERR_CAPACITY if a window has more such rows than view->max_feat or more
+ * observations than view->max_obs. */
+int avm_solve_view_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* full, avm_window_batch* view,
+                         int32_t* view_row /* [B][view->max_feat] out */);
+
+/* FeatureManager::setDepth's copy (feature_manager.cpp:141-159): full.inv_depth[view_row[k]] = view.inv_depth[k] for k < view.n_feat.
+ * view_row is validated first: inside [0, full.n_feat) and strictly increasing (AVM_ERR_INVALID). */
+int avm_solve_view_store_depths(avm_ctx* ctx, avm_mem mem, avm_window_batch* full, const avm_window_batch* view, const int32_t* view_row);
+
+/* avm_slide_window_flags on the full tables with their ids: the rows of feat_id [B][max_feat] are compacted together with the other
+ * per-feature arrays, and when windows->obs_vel_td is given removeFront shifts its rows together with obs_xy, so the td channels stay
+ * with their observations. */
+int avm_slide_window_tracks(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, int32_t* feat_id /* [B][max_feat] in/out */,
+                            const int32_t* marginalization_flags /* [B] */, int32_t shift_depth, double init_depth, int32_t remove_failures);
 
 /* ---- Estimator::visualInitialAlign (estimator.cpp:355-431) with VisualIMUAlignment (initial/initial_aligment.cpp): the step that
  * moves solver_flag from INITIAL to NON_LINEAR.  It starts from the up-to-scale camera trajectory of initialStructure (relativePose,

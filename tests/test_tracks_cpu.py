@@ -1,0 +1,226 @@
+"""CPU tier of the feature manager on device-resident tables (avm_add_image_batch, avm_imu_push_batch, avm_solve_view_batch,
+avm_solve_view_store_depths, avm_slide_window_tracks): the header and the ctypes prototypes, and the Python statements of the reference
+that tests/test_tracks.py holds the kernels against - checked here on hand-computed cases, without a GPU.
+
+The statements work on f_manager.feature as a Python list of dicts, like features_of / roll_features_statement of
+tests/test_mixed_batch_cpu.py, with the feature id under "id" and, for tables with a time offset, the obs_vel_td rows under "td":
+  add_image_statement    FeatureManager::addFeatureCheckParallax's loop over the image (feature_manager.cpp:52-72, find_if over the list)
+  view_statement         the filter of the solve and of triangulate (estimator.cpp:715: used_num >= 2 && start_frame < WINDOW_SIZE - 2)
+  store_depths_statement setDepth's copy (feature_manager.cpp:141-159)
+  tables_from_features   the list as tables: dense observations in list order
+  roll_tracks_statement  roll_features_statement with the td rows moving with their observations
+"""
+import copy
+import ctypes as C
+import re
+
+import numpy as np
+
+from helpers import abi, blank_windows
+from test_mixed_batch_cpu import NEW_ENTRY_POINTS, _header, _header_arg_count, roll_features_statement
+
+WINDOW_SIZE = abi.WINDOW_SIZE
+OLD, SECOND_NEW = abi.MARGIN_OLD, abi.MARGIN_SECOND_NEW
+TRACK_ENTRY_POINTS = ("avm_add_image_batch", "avm_imu_push_batch", "avm_solve_view_batch", "avm_solve_view_store_depths", "avm_slide_window_tracks")
+
+
+# ---------------------------------------------------------------- the statements
+def features_with_ids(a, feat_id, b):
+    """f_manager.feature of window b of the tables `a` (any layout of the observation table) with the ids of feat_id [B, max_feat]."""
+    out = []
+    for e in range(int(a["n_feat"][b])):
+        ob, no = int(a["feat_obs_begin"][b, e]), int(a["feat_nobs"][b, e])
+        f = dict(id=int(feat_id[b, e]), start=int(a["feat_start"][b, e]), obs=[tuple(v) for v in a["obs_xy"][b, ob:ob + no]],
+                 inv_depth=float(a["inv_depth"][b, e]))
+        if "obs_vel_td" in a:
+            f["td"] = [tuple(v) for v in a["obs_vel_td"][b, ob:ob + no]]
+        out.append(f)
+    return out
+
+
+def add_image_statement(feats, image):
+    """The loop of addFeatureCheckParallax over `image`, a dict {feature id: (x, y)} or {feature id: (x, y, vx, vy, cur_td, v)}: std::map
+    order, find_if over the list, push_back on the track or a new FeaturePerId(feature_id, frame_count = WINDOW_SIZE) behind the list
+    (estimated_depth = -1: inv_depth = 1 / -1).  In place; returns the list."""
+    for fid in sorted(image):
+        pt = tuple(float(x) for x in image[fid])
+        it = next((f for f in feats if f["id"] == fid), None)
+        if it is None:
+            it = dict(id=int(fid), start=WINDOW_SIZE, obs=[], inv_depth=1.0 / -1.0)
+            if len(pt) > 2:
+                it["td"] = []
+            feats.append(it)
+        it["obs"].append(pt[:2])
+        if len(pt) > 2:
+            it["td"].append(pt[2:6])
+    return feats
+
+
+def view_statement(feats):
+    """(the features the solve takes - copies, in list order -, their positions in the list)"""
+    rows = [i for i, f in enumerate(feats) if len(f["obs"]) >= 2 and f["start"] < WINDOW_SIZE - 2]
+    return [copy.deepcopy(feats[i]) for i in rows], rows
+
+
+def store_depths_statement(feats, rows, inv_depths):
+    for k, r in enumerate(rows):
+        feats[r]["inv_depth"] = float(inv_depths[k])
+    return feats
+
+
+def tables_from_features(lists, max_feat, max_obs, with_td=False):
+    """One list per window as tables: n_feat, feat_id, feat_start, feat_nobs, feat_obs_begin, inv_depth, obs_xy (and obs_vel_td), the
+    observations dense in list order, everything beyond zero."""
+    B = len(lists)
+    t = dict(n_feat=np.zeros(B, np.int32), feat_id=np.zeros((B, max_feat), np.int32), feat_start=np.zeros((B, max_feat), np.int32),
+             feat_nobs=np.zeros((B, max_feat), np.int32), feat_obs_begin=np.zeros((B, max_feat), np.int32), inv_depth=np.zeros((B, max_feat)),
+             obs_xy=np.zeros((B, max_obs, 2)))
+    if with_td:
+        t["obs_vel_td"] = np.zeros((B, max_obs, 4))
+    for b, feats in enumerate(lists):
+        o = 0
+        assert len(feats) <= max_feat
+        t["n_feat"][b] = len(feats)
+        for e, f in enumerate(feats):
+            no = len(f["obs"])
+            assert no >= 1 and o + no <= max_obs
+            t["feat_id"][b, e], t["feat_start"][b, e], t["feat_nobs"][b, e], t["feat_obs_begin"][b, e] = f["id"], f["start"], no, o
+            t["inv_depth"][b, e] = f["inv_depth"]
+            t["obs_xy"][b, o:o + no] = np.array(f["obs"]).reshape(-1, 2)
+            if with_td:
+                t["obs_vel_td"][b, o:o + no] = np.array(f["td"]).reshape(-1, 4)
+            o += no
+    return t
+
+
+def roll_tracks_statement(feats, flag, shift_depth, remove_failures, pose, ex_pose, init_depth=5.0):
+    """roll_features_statement on a list with ids; the td rows lose the entry of the observation the roll erases."""
+    for f in feats:
+        if "td" not in f:
+            continue
+        if flag == OLD:
+            if f["start"] == 0:
+                f["td"].pop(0)
+        elif f["start"] != WINDOW_SIZE and f["start"] + len(f["obs"]) - 1 >= WINDOW_SIZE - 1:
+            f["td"].pop(WINDOW_SIZE - 1 - f["start"])
+    return roll_features_statement(feats, flag, shift_depth, remove_failures, pose, ex_pose, init_depth)
+
+
+# ---------------------------------------------------------------- header and prototypes
+def test_header_declares_the_five_entry_points_and_keeps_the_abi():
+    for name in TRACK_ENTRY_POINTS:
+        assert _header_arg_count(name) > 0
+    assert "#define AVM_ABI_VERSION 6 " in _header() and abi.AVM_ABI_VERSION == 6
+    assert set(abi.PROTOTYPES) == set(NEW_ENTRY_POINTS)                   # the older dict keeps exactly its four keys
+    assert "typedef struct avm_image_batch {" in _header() and "#define AVM_MAX_IMAGE_PTS 1024" in _header()
+    assert abi.MAX_IMAGE_PTS == 1024
+
+
+def test_track_prototypes_match_the_headers_argument_counts():
+    import importlib
+
+    assert set(abi.TRACK_PROTOTYPES) == set(TRACK_ENTRY_POINTS)
+    for name, argtypes in abi.TRACK_PROTOTYPES.items():
+        assert len(argtypes) == _header_arg_count(name), name
+        assert re.fullmatch(r"avm_[a-z_]+", name)
+    lib_m = importlib.import_module("anticipated-vins-mono_amd.lib")
+    assert set(TRACK_ENTRY_POINTS) <= set(lib_m.EXPORTS)
+    L = lib_m.lib()                                                       # (loads without a GPU)
+    out = (C.c_int * 16)()
+    n = L.avm_debug_track_struct_sizes(out)
+    I = abi.ImageBatch
+    assert [out[i] for i in range(n)] == [C.sizeof(I), abi.MAX_IMAGE_PTS, I.n_windows.offset, I.max_pts.offset, I.n_pts.offset,
+                                          I.feature_id.offset, I.xy.offset, I.vel_td.offset]
+    out7 = (C.c_int * 8)()
+    assert L.avm_debug_struct_sizes(out7) == 7                            # the older hook keeps its seven entries
+
+
+# ---------------------------------------------------------------- the statements on hand-computed cases
+def _list():
+    """ids not ascending; tracks that end in frame 9 (ids 40, 7, 23), one that was lost in frame 6 (id 15), one that starts in frame 9"""
+    return [dict(id=40, start=0, obs=[(0.0, 0.1 * i) for i in range(10)], inv_depth=0.5),
+            dict(id=7, start=2, obs=[(1.0, 0.1 * i) for i in range(8)], inv_depth=0.25),
+            dict(id=15, start=3, obs=[(2.0, 0.1 * i) for i in range(4)], inv_depth=0.2),
+            dict(id=23, start=8, obs=[(3.0, 0.0), (3.0, 0.1)], inv_depth=-1.0),
+            dict(id=9, start=9, obs=[(4.0, 0.0)], inv_depth=-1.0)]
+
+
+def test_add_image_statement_on_hand_computed_cases():
+    # an empty image
+    assert add_image_statement(_list(), {}) == _list()
+    # an empty list: every point starts a track in frame 10, ascending id, inv_depth -1
+    out = add_image_statement([], {30: (0.3, 0.3), 5: (0.5, 0.5), 12: (0.1, 0.2)})
+    assert [f["id"] for f in out] == [5, 12, 30] and all(f["start"] == 10 and f["inv_depth"] == -1.0 and len(f["obs"]) == 1 for f in out)
+    assert out[1]["obs"] == [(0.1, 0.2)]
+    # all ids matched: the list keeps its order and length
+    out = add_image_statement(_list(), {9: (9.0, 9.0), 40: (4.0, 4.0), 7: (7.0, 7.0), 23: (2.0, 3.0)})
+    assert [f["id"] for f in out] == [40, 7, 15, 23, 9] and [len(f["obs"]) for f in out] == [11, 9, 4, 3, 2]
+    assert out[0]["obs"][-1] == (4.0, 4.0) and out[3]["obs"][-1] == (2.0, 3.0) and out[4]["obs"] == [(4.0, 0.0), (9.0, 9.0)]
+    assert [f["start"] for f in out] == [0, 2, 3, 8, 9] and out[0]["inv_depth"] == 0.5
+    # no id matched
+    out = add_image_statement(_list(), {100: (1.0, 1.0), 8: (8.0, 8.0)})
+    assert [f["id"] for f in out] == [40, 7, 15, 23, 9, 8, 100] and [len(f["obs"]) for f in out] == [10, 8, 4, 2, 1, 1, 1]
+    # new ids between matched ones: the new rows are in ascending id behind a list that is not
+    out = add_image_statement(_list(), {6: (6.0, 0.0), 7: (7.0, 0.0), 8: (8.0, 0.0), 23: (23.0, 0.0), 24: (24.0, 0.0), 39: (39.0, 0.0), 40: (40.0, 0.0)})
+    assert [f["id"] for f in out] == [40, 7, 15, 23, 9, 6, 8, 24, 39]
+    assert [len(f["obs"]) for f in out] == [11, 9, 4, 3, 1, 1, 1, 1, 1] and out[7]["obs"] == [(24.0, 0.0)]
+    # the td rows travel with the points
+    feats = [dict(id=3, start=8, obs=[(0.0, 0.0), (0.1, 0.1)], td=[(1.0, 2.0, 3.0, 4.0), (5.0, 6.0, 7.0, 8.0)], inv_depth=-1.0)]
+    out = add_image_statement(feats, {3: (0.2, 0.2, 9.0, 10.0, 11.0, 12.0), 1: (0.5, 0.5, 13.0, 14.0, 15.0, 16.0)})
+    assert out[0]["td"][-1] == (9.0, 10.0, 11.0, 12.0) and out[1]["td"] == [(13.0, 14.0, 15.0, 16.0)] and out[1]["obs"] == [(0.5, 0.5)]
+
+
+def test_view_and_store_depths_statements_on_hand_computed_cases():
+    feats = add_image_statement(_list(), {40: (4.0, 4.0), 23: (2.0, 3.0), 50: (5.0, 5.0)})
+    view, rows = view_statement(feats)
+    assert rows == [0, 1, 2] and [f["id"] for f in view] == [40, 7, 15]  # start 8 / 9 / 10 never pass; nobs >= 2
+    assert view_statement([dict(id=1, start=0, obs=[(0.0, 0.0)], inv_depth=-1.0), dict(id=2, start=7, obs=[(0.0, 0.0)] * 2, inv_depth=-1.0),
+                           dict(id=3, start=8, obs=[(0.0, 0.0)] * 3, inv_depth=-1.0)])[1] == [1]
+    view[0]["inv_depth"] = 99.0                                           # the view holds copies
+    assert feats[0]["inv_depth"] == 0.5
+    store_depths_statement(feats, rows, [0.11, 0.22, 0.33])
+    assert [f["inv_depth"] for f in feats] == [0.11, 0.22, 0.33, -1.0, -1.0, -1.0]
+    assert view_statement([]) == ([], [])
+
+
+def test_tables_from_features_is_dense_in_list_order_also_from_tables_with_holes():
+    # a table as both kinds of roll leave it: removeBack moved the begin of row 0 up (slot 0 is a hole), removeFront shortened row 1 (slot 5
+    # is a hole), row 2 sits behind an erased row's slots (6, 7)
+    w = blank_windows(1, max_feat=8, max_obs=16)
+    a = w.a
+    a["obs_vel_td"] = np.arange(64, dtype=float).reshape(1, 16, 4)
+    a["obs_xy"][0] = np.arange(32, dtype=float).reshape(16, 2)
+    a["n_feat"][0] = 3
+    a["feat_start"][0, :3], a["feat_nobs"][0, :3], a["feat_obs_begin"][0, :3] = [0, 4, 9], [2, 2, 1], [1, 3, 8]
+    a["inv_depth"][0, :3] = [0.5, 0.25, -1.0]
+    fid = np.array([[12, 3, 7, 0, 0, 0, 0, 0]], np.int32)
+    feats = features_with_ids(a, fid, 0)
+    assert [f["id"] for f in feats] == [12, 3, 7] and feats[0]["obs"] == [(2.0, 3.0), (4.0, 5.0)] and feats[2]["td"] == [(32.0, 33.0, 34.0, 35.0)]
+    t = tables_from_features([feats], 8, 16, with_td=True)
+    assert t["n_feat"].tolist() == [3] and t["feat_obs_begin"][0, :3].tolist() == [0, 2, 4] and t["feat_nobs"][0, :3].tolist() == [2, 2, 1]
+    assert t["feat_id"][0, :3].tolist() == [12, 3, 7] and t["feat_start"][0, :3].tolist() == [0, 4, 9]
+    assert np.array_equal(t["obs_xy"][0, :5], a["obs_xy"][0, [1, 2, 3, 4, 8]]) and np.array_equal(t["obs_vel_td"][0, :5], a["obs_vel_td"][0, [1, 2, 3, 4, 8]])
+    assert (t["obs_xy"][0, 5:] == 0).all() and t["inv_depth"][0, :3].tolist() == [0.5, 0.25, -1.0]
+    assert tables_from_features([[]], 8, 16)["n_feat"].tolist() == [0]
+
+
+def test_roll_tracks_statement_moves_ids_and_td_rows():
+    pose, ex = np.zeros((11, 7)), np.zeros(7)
+    pose[:, 6], ex[6] = 1.0, 1.0
+
+    def feats():
+        td = lambda n, k: [(float(k), float(i), 0.0, 0.0) for i in range(n)]
+        return [dict(id=50, start=0, obs=[(0.0, 0.0)] * 2, td=td(2, 50), inv_depth=0.5),    # MARGIN_OLD erases it (one observation left)
+                dict(id=4, start=0, obs=[(0.0, 0.0)] * 11, td=td(11, 4), inv_depth=0.5),
+                dict(id=31, start=6, obs=[(0.1, 0.1)] * 4, td=td(4, 31), inv_depth=0.5),    # ends in frame 9
+                dict(id=8, start=9, obs=[(0.2, 0.2)], td=td(1, 8), inv_depth=-1.0),         # MARGIN_SECOND_NEW erases it
+                dict(id=2, start=10, obs=[(0.3, 0.3)], td=td(1, 2), inv_depth=-1.0)]
+
+    out = roll_tracks_statement(feats(), OLD, True, False, pose, ex)
+    assert [f["id"] for f in out] == [4, 31, 8, 2] and [f["start"] for f in out] == [0, 5, 8, 9]
+    assert [t[1] for t in out[0]["td"]] == [float(i) for i in range(1, 11)] and len(out[1]["td"]) == 4
+    out = roll_tracks_statement(feats(), SECOND_NEW, True, False, pose, ex)
+    assert [f["id"] for f in out] == [50, 4, 31, 2] and [f["start"] for f in out] == [0, 0, 6, 9]
+    assert [t[1] for t in out[1]["td"]] == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0, 6.0, 7.0, 8.0, 10.0]   # frame 9's row went, frame 10's stays attached
+    assert [t[1] for t in out[2]["td"]] == [0.0, 1.0, 2.0] and all(len(f["td"]) == len(f["obs"]) for f in out)
+    assert [t[1] for t in out[0]["td"]] == [0.0, 1.0]                     # a track that ended before frame 9 keeps everything
