@@ -73,6 +73,22 @@ struct avm_ctx {
   int scratch_slots = 0;  // slots allocated (n_slots, or 2 n_slots once a batch has taken the throughput form of the solve)
   double *pre_delta = nullptr, *pre_jac = nullptr, *pre_cov = nullptr, *pre_sqrt = nullptr, *pre_sum = nullptr;
   size_t pre_cap = 0;  // windows
+  // What pre_* were computed from (run_preint): per interval a copy of the inputs preint_kernel read (its key) and whether that copy is
+  // valid, the list of intervals the last comparison found changed, and two counters that take turns.  The device-side comparison is
+  // the only thing that declares an interval unchanged; the host only remembers what makes EVERY key void.
+  struct PreintCache {
+    unsigned long long* key = nullptr;  // [pre_cap * 10][preint_key_words(max_samp)], key_cap words
+    size_t key_cap = 0;
+    int32_t *valid = nullptr, *todo = nullptr, *count = nullptr;  // [pre_cap * 10], [pre_cap * 10], [2]
+    bool all_void = true;                                         // buffers (re)allocated, or pre_* written without the comparison
+    int n_windows = -1, max_samp = -1;                            // of the call the keys belong to
+    double noise[4] = {0, 0, 0, 0};                               // acc_n, gyr_n, acc_w, gyr_w of that call
+    int turn = 0;                                                 // which counter the next comparison counts in
+    // avm_debug_preint_cache: the last run_preint and the last slide
+    int64_t examined = 0, recomputed = 0;  // recomputed < 0: on the device, in *last_count
+    const int32_t* last_count = nullptr;
+    int64_t rolled = 0;
+  } pk;
   avm_solve_summary* d_summary = nullptr;
   long long* prof = nullptr;  // [n_slots][32], enabled by AVM_PROFILE=1
   size_t summary_cap = 0;
@@ -260,10 +276,18 @@ int validate_fsel(avm_ctx* c, avm_mem mem, const avm_fsel_batch* b) {
   return AVM_OK;
 }
 
-int ensure_window_buffers(avm_ctx* c, int n_windows, bool tp = false) {
+// AVM_PREINT_CACHE=0: run_preint integrates every interval on every call and keeps no keys (read on every call: tests, A/B runs)
+bool preint_cache_enabled() {
+  const char* e = getenv("AVM_PREINT_CACHE");
+  return !(e && e[0] == '0');
+}
+
+int ensure_window_buffers(avm_ctx* c, int n_windows, int max_samp, bool tp = false) {
   // (the throughput form of the solve runs two workgroups per CU: twice the slots; allocated when a batch first takes it)
   const int want = tp ? 2 * c->n_slots : c->n_slots;
-  if (!c->scratch || c->scratch_slots < want || (size_t)n_windows > c->pre_cap) c->n_allocs++;
+  // the keys of the pre-integration cache: sized by the samples per interval as well, so they grow on their own when only max_samp does
+  const size_t key_want = preint_cache_enabled() && max_samp >= 0 ? (size_t)n_windows * 10 * (size_t)preint_key_words(max_samp) : 0;
+  if (!c->scratch || c->scratch_slots < want || (size_t)n_windows > c->pre_cap || key_want > c->pk.key_cap) c->n_allocs++;
   if (!c->scratch || c->scratch_slots < want) {
     if (c->scratch) (void)hipFree(c->scratch), c->scratch = nullptr;
     if (c->iscratch) (void)hipFree(c->iscratch), c->iscratch = nullptr;
@@ -278,13 +302,27 @@ int ensure_window_buffers(avm_ctx* c, int n_windows, bool tp = false) {
     c->pre_cap = 0;  // a failed hipMalloc below must not leave the old capacity next to freed / partial buffers
     for (double** p : {&c->pre_delta, &c->pre_jac, &c->pre_cov, &c->pre_sqrt, &c->pre_sum})
       if (*p) (void)hipFree(*p), *p = nullptr;
+    for (int32_t** p : {&c->pk.valid, &c->pk.todo, &c->pk.count})
+      if (*p) (void)hipFree(*p), *p = nullptr;
+    c->pk.all_void = true;  // the results the keys stood for are gone
     const size_t iv = (size_t)n_windows * 10;
     HIPCHK(c, hipMalloc(&c->pre_delta, sizeof(double) * iv * 10));
     HIPCHK(c, hipMalloc(&c->pre_jac, sizeof(double) * iv * 225));
     HIPCHK(c, hipMalloc(&c->pre_cov, sizeof(double) * iv * 225));
     HIPCHK(c, hipMalloc(&c->pre_sqrt, sizeof(double) * iv * 225));
     HIPCHK(c, hipMalloc(&c->pre_sum, sizeof(double) * iv));
+    HIPCHK(c, hipMalloc(&c->pk.valid, sizeof(int32_t) * iv));
+    HIPCHK(c, hipMalloc(&c->pk.todo, sizeof(int32_t) * iv));
+    HIPCHK(c, hipMalloc(&c->pk.count, sizeof(int32_t) * 2));
+    HIPCHK(c, hipMemsetAsync(c->pk.count, 0, sizeof(int32_t) * 2, c->stream));
+    c->pk.turn = 0, c->pk.last_count = nullptr, c->pk.recomputed = 0;
     c->pre_cap = n_windows;
+  }
+  if (key_want > c->pk.key_cap) {
+    c->pk.key_cap = 0, c->pk.all_void = true;
+    if (c->pk.key) (void)hipFree(c->pk.key), c->pk.key = nullptr;
+    HIPCHK(c, hipMalloc(&c->pk.key, sizeof(unsigned long long) * key_want));
+    c->pk.key_cap = key_want;
   }
   return AVM_OK;
 }
@@ -597,8 +635,63 @@ int run_preint(avm_ctx* c, const avm_options* opt, const avm_window_batch* d) {
   pa.acc_n = opt->acc_n, pa.gyr_n = opt->gyr_n, pa.acc_w = opt->acc_w, pa.gyr_w = opt->gyr_w;
   pa.out_delta = c->pre_delta, pa.out_jacobian = c->pre_jac, pa.out_covariance = c->pre_cov, pa.out_sum_dt = c->pre_sum,
   pa.out_sqrt_info = c->pre_sqrt;
+  // The stored results depend on the IMU tables and the four noise densities only, and in a stream one image changes one interval of ten:
+  // preint_match_kernel compares every interval's inputs with the copy its stored results were computed from and lists the ones that
+  // differ; the two kernels then work from that list (no host read of its length: their grid is sized for every interval).  The host
+  // only knows what makes every key void: another batch shape, other noise densities, reallocated buffers, a call that went without.
+  avm_ctx::PreintCache& k = c->pk;
+  const int64_t n_iv = (int64_t)d->n_windows * 10;
+  k.examined = n_iv;
+  const bool cached = preint_cache_enabled() && d->max_samp >= 0 && k.key && k.valid &&
+                      (size_t)n_iv * (size_t)preint_key_words(d->max_samp) <= k.key_cap && (size_t)d->n_windows <= c->pre_cap;
+  if (!cached) {
+    k.all_void = true, k.recomputed = n_iv;
+    launch_preint(pa, c->stream);
+    HIPCHK(c, hipGetLastError());
+    return AVM_OK;
+  }
+  const double noise[4] = {opt->acc_n, opt->gyr_n, opt->acc_w, opt->gyr_w};
+  if (k.all_void || k.n_windows != d->n_windows || k.max_samp != d->max_samp || std::memcmp(k.noise, noise, sizeof noise) != 0) {
+    HIPCHK(c, hipMemsetAsync(k.valid, 0, sizeof(int32_t) * (size_t)n_iv, c->stream));
+    k.all_void = false, k.n_windows = d->n_windows, k.max_samp = d->max_samp;
+    std::memcpy(k.noise, noise, sizeof noise);
+  }
+  PreintKeys pk;
+  pk.key = k.key, pk.valid = k.valid, pk.todo = k.todo;
+  pk.count = k.count + k.turn, pk.count_next = k.count + (1 - k.turn);
+  launch_preint_match(pa, pk, c->stream);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+    k.all_void = true;
+    c->err = std::string("launch_preint_match: ") + hipGetErrorString(e);
+    return AVM_ERR_HIP;
+  }
+  k.turn = 1 - k.turn, k.last_count = pk.count, k.recomputed = -1;
+  pa.todo = k.todo, pa.todo_count = pk.count;
   launch_preint(pa, c->stream);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+    k.all_void = true;  // the comparison has stored keys for results that were never computed
+    c->err = std::string("launch_preint: ") + hipGetErrorString(e);
+    return AVM_ERR_HIP;
+  }
+  return AVM_OK;
+}
+
+// The cache follows a roll of the windows (avm_slide_window*), when its keys belong to a batch of this shape: otherwise - and whenever the
+// caller slid other windows than it last pre-integrated - the next comparison simply finds more intervals changed.
+int roll_preint_cache(avm_ctx* c, const avm_window_batch& d, const int32_t* dflags, int flag) {
+  avm_ctx::PreintCache& k = c->pk;
+  k.rolled = 0;
+  c->last_ms["preint_roll"] = 0.0f;
+  if (!preint_cache_enabled() || k.all_void || !k.key || k.n_windows != d.n_windows || k.max_samp != d.max_samp) return AVM_OK;
+  PreintRoll r;
+  r.n_windows = d.n_windows, r.key_words = (int)preint_key_words(d.max_samp), r.flags = dflags, r.flag = flag;
+  r.key = k.key, r.valid = k.valid;
+  r.delta = c->pre_delta, r.jac = c->pre_jac, r.cov = c->pre_cov, r.sqrt_info = c->pre_sqrt, r.sum_dt = c->pre_sum;
+  HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+  launch_preint_roll(r, c->stream);
   HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+  k.rolled = d.n_windows;
   return AVM_OK;
 }
 
@@ -799,7 +892,7 @@ void avm_destroy(avm_ctx* c) {
   for (auto& kv : c->pinned)
     if (kv.second.first) (void)hipHostFree(kv.second.first);
   for (void* p : {(void*)c->scratch, (void*)c->iscratch, (void*)c->pre_delta, (void*)c->pre_jac, (void*)c->pre_cov, (void*)c->pre_sqrt,
-                  (void*)c->pre_sum, (void*)c->d_summary})
+                  (void*)c->pre_sum, (void*)c->d_summary, (void*)c->pk.key, (void*)c->pk.valid, (void*)c->pk.todo, (void*)c->pk.count})
     if (p) (void)hipFree(p);
   for (auto& e : c->ev) (void)hipEventDestroy(e);
   (void)hipStreamDestroy(c->stream);
@@ -907,7 +1000,7 @@ int avm_window_solve_batch_flags(avm_ctx* c, const avm_options* opt, avm_mem mem
   // choose forms (the slots for the throughput forms are sized before the priors' verdict is in: a batch that then takes the latency forms uses half of them)
   const bool extended = opt->estimate_extrinsic != 0 || opt->estimate_td != 0 || batch->relo_n != nullptr;
   SolveForms forms = choose_forms(batch->n_windows, c->n_slots, extended, marg, 0);
-  if ((rc = ensure_window_buffers(c, batch->n_windows, forms.tp || forms.big_x)) != AVM_OK) {
+  if ((rc = ensure_window_buffers(c, batch->n_windows, batch->max_samp, forms.tp || forms.big_x)) != AVM_OK) {
     if (check.dev) (void)hipStreamSynchronize(c->stream);
     return rc;
   }
@@ -994,7 +1087,7 @@ int avm_imu_preintegrate_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, 
   if (rc != AVM_OK) return rc;
   if (batch->n_windows == 0) return AVM_OK;
   if ((rc = validate_windows(c, mem, batch, CHK_IMU)) != AVM_OK) return rc;
-  if ((rc = ensure_window_buffers(c, batch->n_windows)) != AVM_OK) return rc;
+  if ((rc = ensure_window_buffers(c, batch->n_windows, batch->max_samp)) != AVM_OK) return rc;
   avm_window_batch d;
   if ((rc = windows_on_device(c, mem, batch, &d)) != AVM_OK) return rc;
   if ((rc = run_preint(c, opt, &d)) != AVM_OK) return rc;
@@ -1051,6 +1144,20 @@ int avm_debug_counters(avm_ctx* c, int64_t* out) {
     std::vector<int> h((size_t)c->last_marg_windows);
     HIPCHK(c, hipMemcpy(h.data(), it->second.first, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
     for (int v : h) out[1] += v != 0;
+  }
+  return AVM_OK;
+}
+
+// test / bench hook (not in avm.h): out[0] = intervals the last pre-integration examined, out[1] = intervals it integrated (all of them
+// with AVM_PREINT_CACHE=0), out[2] = windows whose cached pre-integrations the last avm_slide_window* rolled (0: it left the cache alone)
+int avm_debug_preint_cache(avm_ctx* c, int64_t* out) {
+  if (!c || !out) return AVM_ERR_INVALID;
+  out[0] = c->pk.examined, out[1] = c->pk.recomputed, out[2] = c->pk.rolled;
+  if (c->pk.recomputed < 0 && c->pk.last_count) {
+    int32_t n = 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&n, c->pk.last_count, sizeof n, hipMemcpyDeviceToHost));
+    out[1] = n;
   }
   return AVM_OK;
 }
@@ -1205,6 +1312,7 @@ namespace {
 // obs_vel_td (when the batch has them) move with those of obs_xy
 int slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, const int32_t* flags, int32_t flag, int32_t shift_depth, double init_depth,
                  int32_t remove_failures, int32_t* feat_id = nullptr) {
+  c->pk.rolled = 0, c->last_ms["preint_roll"] = 0.0f;  // (a slide that returns before its roll reports none)
   if (batch->n_windows == 0) return AVM_OK;
   // (the flags are checked with the tables, before the kernel reads either)
   const FlagRule fr{flags, (1u << AVM_MARGIN_OLD) | (1u << AVM_MARGIN_SECOND_NEW)};
@@ -1225,6 +1333,7 @@ int slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, const int32_t
   HIPCHK(c, launch_slide_window(d, static_cast<const int32_t*>(dflags), flag, shift_depth, init_depth, remove_failures, derr, c->stream,
                                 static_cast<int32_t*>(const_cast<void*>(dfid)), feat_id ? 1 : 0));
   HIPCHK(c, hipEventRecord(c->ev[4], c->stream));
+  if ((rc = roll_preint_cache(c, d, static_cast<const int32_t*>(dflags), flag)) != AVM_OK) return rc;
   int herr = 0;
   HIPCHK(c, hipMemcpyAsync(&herr, derr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if ((rc = copy_back(c, mem, WINDOWS, use, batch, &d, batch)) != AVM_OK) return rc;  // (everything the roll rewrites)
@@ -1232,6 +1341,7 @@ int slide_window(avm_ctx* c, avm_mem mem, avm_window_batch* batch, const int32_t
   HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["slide_window"] = ms;
+  if (c->pk.rolled && hipEventElapsedTime(&ms, c->ev[5], c->ev[6]) == hipSuccess) c->last_ms["preint_roll"] = ms;
   if (herr) return fail(c, AVM_ERR_CAPACITY, "MARGIN_SECOND_NEW: interval 8 + interval 9 exceed max_samp samples");
   return AVM_OK;
 }
@@ -1588,7 +1698,7 @@ int avm_window_eval_factors(avm_ctx* c, const avm_options* opt, avm_mem mem, con
   if (rc != AVM_OK) return rc;
   if (batch->n_windows == 0) return AVM_OK;
   if ((rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR)) != AVM_OK) return rc;
-  if ((rc = ensure_window_buffers(c, batch->n_windows)) != AVM_OK) return rc;
+  if ((rc = ensure_window_buffers(c, batch->n_windows, batch->max_samp)) != AVM_OK) return rc;
   avm_window_batch d;
   if ((rc = windows_on_device(c, mem, batch, &d)) != AVM_OK) return rc;
   const size_t B = batch->n_windows;

@@ -38,6 +38,26 @@ struct PreintArgs {
   const double *imu_dt, *imu_acc, *imu_gyr, *imu_lin_ba, *imu_lin_bg;
   double acc_n, gyr_n, acc_w, gyr_w;
   double *out_delta, *out_jacobian, *out_covariance, *out_sum_dt, *out_sqrt_info;
+  // null: every interval.  Else the intervals launch_preint_match listed, todo[0 .. todo_count[0]) (both device memory): only they are
+  // integrated and stored, the results of the others stay as they are
+  const int32_t *todo = nullptr, *todo_count = nullptr;
+};
+
+// The ctx's record of what the stored pre-integrations were computed from (avm_api.hip, run_preint; preint.hip, preint_match_kernel)
+constexpr long preint_key_words(int max_samp) { return 13 + 7 * (long)max_samp; }  // 64-bit words of an interval's key
+struct PreintKeys {
+  unsigned long long* key;     // [n_windows * 10][preint_key_words(max_samp)]
+  int32_t* valid;              // [n_windows * 10] 1: the key is what the interval's stored results were computed from
+  int32_t* todo;               // [n_windows * 10] out: the intervals to integrate
+  int32_t *count, *count_next; // out: their number (zero on entry); zeroed for the next call
+};
+struct PreintRoll {
+  int n_windows, key_words;
+  const int32_t* flags;  // [n_windows] device, or null: every window takes `flag`
+  int flag;
+  unsigned long long* key;
+  int32_t* valid;
+  double *delta, *jac, *cov, *sqrt_info, *sum_dt;
 };
 
 // per-slot global scratch layout (doubles), one slot per resident workgroup (stays L2 resident)
@@ -241,6 +261,8 @@ hipError_t launch_validate_windows(const avm_window_batch& b, int what, int* fir
 hipError_t launch_validate_fsel(const avm_fsel_batch& b, int* first_bad, hipStream_t stream);
 
 void launch_preint(const PreintArgs& a, hipStream_t stream);
+void launch_preint_match(const PreintArgs& a, const PreintKeys& k, hipStream_t stream);  // before launch_preint with a.todo = k.todo, a.todo_count = k.count
+void launch_preint_roll(const PreintRoll& r, hipStream_t stream);
 hipError_t launch_fsel(const avm_fsel_batch& b, const FselBuffers& w, const avm_fsel_out& out, double* omega_out, bool run_rounds,
                        int frame_mode, const int* vflag, hipStream_t stream);
 bool fsel_horizon_supported(int H);

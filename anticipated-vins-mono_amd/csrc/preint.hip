@@ -39,6 +39,19 @@ struct PreLds {
   double Vi[9 * VS];  // rows p, theta, v of V, noise columns 0..11 (the reference's order); the rows ba, bg are zero there
   double m[72];       // Rd, Rr, Ra0, Ra1, IRw (I - Rw*dt), T1=Rd*Ra0, T2=Rr*Ra1, T3=T2*IRw
 };
+
+// What the two kernels below work on: a.todo == null: every interval, item k is interval k; else the a.todo_count[0] intervals that
+// preint_match_kernel listed, item k is interval a.todo[k] (in whatever order the wavefronts appended them: an interval's arithmetic
+// does not depend on its companions in the wavefront).  The grid is sized for every interval either way.
+AVM_DEV long work_count(const PreintArgs& a) {
+  const long n_all = (long)a.n_windows * 10;
+  return a.todo ? min(max((long)a.todo_count[0], 0L), n_all) : n_all;
+}
+AVM_DEV long work_interval(const PreintArgs& a, long item) {
+  return a.todo ? (long)min(max(a.todo[item], 0), a.n_windows * 10 - 1) : item;
+}
+
+AVM_DEV unsigned long long bits(const double* p) { return (unsigned long long)__double_as_longlong(*p); }
 }  // namespace
 
 // The 15 x 15 state matrices never leave registers: with v_mfma_f64_16x16x4 the accumulator layout
@@ -59,14 +72,14 @@ __global__ __launch_bounds__(64 * PW) void preint_kernel(PreintArgs a) {
   PreLds* all = reinterpret_cast<PreLds*>(smem_raw);
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int li = lane & 15, lk = lane >> 4;
-  const long n_iv = (long)a.n_windows * 10;
-  const long iv0 = ((long)blockIdx.x * PW + wv) * PG;  // first interval of this wavefront (interval index = w*10 + j)
+  const long n_iv = work_count(a);                     // work items: every interval (interval index = w*10 + j), or the listed ones
+  const long iv0 = ((long)blockIdx.x * PW + wv) * PG;  // first work item of this wavefront
   if (iv0 >= n_iv) return;                             // no block-level barriers below
   PreLds* Lw = all + wv * PG;                          // the wavefront's four images
-  // ---- scalar side: this lane works for interval iv0 + lk (clamped: a group past the end repeats the last interval and
+  // ---- scalar side: this lane works for the interval of item iv0 + lk (clamped: a group past the end repeats the last item and
   //      stores nothing)
   const bool gv = iv0 + lk < n_iv;
-  const long iv = gv ? iv0 + lk : n_iv - 1;
+  const long iv = work_interval(a, gv ? iv0 + lk : n_iv - 1);
   PreLds& L = Lw[lk];
   // (clamped to the table's stride: the pre-integration may be enqueued behind the table check whose verdict the host reads while it
   //  runs - avm_api.hip, validate_windows_begin / _end; a batch with a bad imu_n is refused either way, it must only not be read out of bounds)
@@ -242,13 +255,14 @@ __global__ __launch_bounds__(64 * PW) void preint_kernel(PreintArgs a) {
 #pragma unroll
   for (int g = 0; g < PG; g++) {
     if (iv0 + g >= n_iv) continue;
+    const long ivg = __builtin_amdgcn_readlane((int)iv, 16 * g);  // the interval of group g
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int row = lk + 4 * r;
       if (row < 15 && li < 15) {  // back to the reference's order p | theta | v | ba | bg
         const int ro = row < 12 ? row + 3 : row - 12, co = li < 12 ? li + 3 : li - 12;
-        a.out_jacobian[(iv0 + g) * 225 + ro * 15 + co] = Jb[g][r];
-        a.out_covariance[(iv0 + g) * 225 + ro * 15 + co] = Pb[g][r];
+        a.out_jacobian[ivg * 225 + ro * 15 + co] = Jb[g][r];
+        a.out_covariance[ivg * 225 + ro * 15 + co] = Pb[g][r];
       }
     }
   }
@@ -260,12 +274,12 @@ __global__ __launch_bounds__(64 * PW) void sqrt_info_kernel(PreintArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int li = lane & 15, lk = lane >> 4;
-  const long n_iv = (long)a.n_windows * 10;
+  const long n_iv = work_count(a);
   const long iv0 = ((long)blockIdx.x * PW + wv) * PG;
   if (iv0 >= n_iv) return;
   double* buf = reinterpret_cast<double*>(smem_raw) + (wv * PG + lk) * 32;  // the group's pivot-row buffer
   const bool gv = iv0 + lk < n_iv;
-  const long iv = gv ? iv0 + lk : n_iv - 1;
+  const long iv = work_interval(a, gv ? iv0 + lk : n_iv - 1);
   const bool rowv = li < 15;
   double A[15], Iv[15];
   {
@@ -337,12 +351,138 @@ __global__ __launch_bounds__(64 * PW) void sqrt_info_kernel(PreintArgs a) {
     if (rowv && pos >= k) Iv[k] = pos == k ? lkk : sacc / lkk;
     wsync();
   }
-  // U = L^T: the lane at position c writes column c
+  // U = L^T: the lane at position c writes column c.  A covariance with a NaN in it, or a singular one whose elimination makes some
+  // (an interval without samples: P = 0), leaves the pivot search without an order: the positions are then no permutation, and columns
+  // nobody holds would keep what the buffer held before.  Such an interval has no sqrt_info: every entry is NaN.
+  unsigned held = rowv ? 1u << pos : 0u;
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) held |= (unsigned)__shfl_xor((int)held, o, 64);
+  const bool perm = held == 0x7fffu;
   if (gv && rowv) {
     double* out = a.out_sqrt_info + iv * 225;
+    const int col = perm ? pos : li;
 #pragma unroll
-    for (int r = 0; r < 15; r++) out[r * 15 + pos] = r <= pos ? Iv[r] : 0.0;
+    for (int r = 0; r < 15; r++) out[r * 15 + col] = perm ? (r <= pos ? Iv[r] : 0.0) : __builtin_nan("");
   }
+}
+
+// ---- the content-checked cache (avm_api.hip, run_preint): which intervals' inputs differ from the ones their stored results came from ----
+// One 16-lane group per interval compares what preint_kernel reads of it - imu_n, lin_ba, lin_bg, dt[0 .. ns), rows 0 .. ns of acc and
+// gyr, ns the clamped count - with the interval's key, bitwise as 64-bit integers (a NaN equals itself, -0.0 differs from 0.0).  On a
+// difference, or a key that is not valid, the group stores the new key, marks it valid and appends the interval to k.todo: one ballot per
+// wavefront, and one atomic add per BLOCK of sixteen wavefronts - the adds all hit one address and serialize there at about 11 ns each
+// (measured: one per wavefront, 10 240 of them at 4096 windows, made a call in which everything had changed 0.12 ms longer).
+// Key of an interval, preint_key_words(max_samp) words: imu_n | lin_ba 3 | lin_bg 3 | dt [max_samp] |
+// acc [max_samp + 1][3] | gyr [max_samp + 1][3]; the entries beyond ns keep whatever an earlier key left there and are never compared.
+// Thread 0 also zeroes the counter of the NEXT call (k.count_next: the two counters take turns, nothing reads that one any more).
+constexpr int MT = 256;     // threads per block of the roll kernel
+constexpr int MTM = 1024;   // ... of the match kernel
+template <class Visit>
+AVM_DEV void key_walk(const PreintArgs& a, long iv, int n_raw, int ns, int li, Visit&& visit) {
+  const int S = a.max_samp;
+  const double* dts = a.imu_dt + iv * S;
+  const double* acc = a.imu_acc + iv * (S + 1) * 3;
+  const double* gyr = a.imu_gyr + iv * (S + 1) * 3;
+  if (li == 0) visit(0, (unsigned long long)(long long)n_raw);
+  if (li < 3) visit(1 + li, bits(a.imu_lin_ba + iv * 3 + li));
+  else if (li < 6) visit(1 + li, bits(a.imu_lin_bg + iv * 3 + li - 3));
+  for (int k = li; k < ns; k += 16) visit(7 + k, bits(dts + k));
+  for (int k = li; k < 3 * (ns + 1); k += 16) visit(7 + S + k, bits(acc + k));
+  for (int k = li; k < 3 * (ns + 1); k += 16) visit(7 + S + 3 * (S + 1) + k, bits(gyr + k));
+}
+
+__global__ __launch_bounds__(MTM) void preint_match_kernel(PreintArgs a, PreintKeys k) {
+  __shared__ int wave_n[MTM / 64], block_base;
+  const int lane = threadIdx.x & 63, li = lane & 15, wave = threadIdx.x >> 6;
+  const long n_iv = (long)a.n_windows * 10;
+  if (blockIdx.x == 0 && threadIdx.x == 0) k.count_next[0] = 0;
+  const long iv = ((long)blockIdx.x * MTM + threadIdx.x) >> 4;
+  const bool gv = iv < n_iv;
+  bool dirty = false;
+  if (gv) {
+    const int n_raw = a.imu_n[iv], ns = min(max(n_raw, 0), a.max_samp);
+    unsigned long long* key = k.key + iv * preint_key_words(a.max_samp);
+    unsigned long long diff = k.valid[iv] ? 0ull : 1ull;
+    key_walk(a, iv, n_raw, ns, li, [&](int at, unsigned long long cur) { diff |= cur ^ key[at]; });
+    // any lane of the group (the lanes of a group are either all here or all past the end)
+    const unsigned long long m = __ballot(diff != 0);
+    dirty = ((m >> (lane & 48)) & 0xffffull) != 0;
+    if (dirty) {
+      key_walk(a, iv, n_raw, ns, li, [&](int at, unsigned long long cur) { key[at] = cur; });
+      if (li == 0) k.valid[iv] = 1;
+    }
+  }
+  // the append: this wavefront's intervals behind those of the block's earlier wavefronts, the block's behind whatever the counter says
+  const bool lead = dirty && li == 0;
+  const unsigned long long m = __ballot(lead);
+  if (lane == 0) wave_n[wave] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int n = 0;
+    for (int w = 0; w < MTM / 64; w++) n += wave_n[w];
+    block_base = n ? atomicAdd(k.count, n) : 0;
+  }
+  __syncthreads();
+  if (lead) {
+    int at = block_base + __popcll(m & ((1ull << lane) - 1));
+    for (int w = 0; w < wave; w++) at += wave_n[w];
+    k.todo[at] = (int)iv;  // (every interval is appended at most once: at < n_iv)
+  }
+}
+
+// ---- the cache follows the window (avm_slide_window*): one wavefront per window, j = 0 .. 8 in order ----
+// MARGIN_OLD: key, validity and the five results of interval j <- those of j + 1, interval 9 not valid.  MARGIN_SECOND_NEW: the roll
+// merged interval 9 into 8: both not valid.  A result only ever moves together with its key and its validity, and a lane moves the same
+// words at every j, so its own program order keeps the copies of j and j + 1 apart; the match kernel still compares every key.
+template <class T>
+AVM_DEV void roll_words(T* base, long j, int n, int lane) {  // words of interval j <- those of j + 1, n words each
+  T* dst = base + j * n;
+  const T* src = dst + n;
+  int i = lane;
+  for (; i + 192 < n; i += 256) {
+    const T v0 = src[i], v1 = src[i + 64], v2 = src[i + 128], v3 = src[i + 192];
+    dst[i] = v0, dst[i + 64] = v1, dst[i + 128] = v2, dst[i + 192] = v3;
+  }
+  for (; i < n; i += 64) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(MT) void preint_roll_kernel(PreintRoll r) {
+  const int lane = threadIdx.x & 63;
+  const long w = (long)blockIdx.x * (MT / 64) + (threadIdx.x >> 6);
+  if (w >= r.n_windows) return;
+  const int flag = r.flags ? r.flags[w] : r.flag;
+  int32_t* valid = r.valid + w * 10;
+  if (flag == AVM_MARGIN_OLD) {
+    unsigned v = 0;  // bit j: interval j is valid (read before any of them is rewritten)
+#pragma unroll
+    for (int j = 0; j < 10; j++) v |= (valid[j] != 0 ? 1u : 0u) << j;
+    for (int j = 0; j < 9; j++) {
+      const long iv = w * 10 + j;
+      if ((v >> (j + 1)) & 1u) {  // (wave-uniform; what is not valid is not worth moving)
+        roll_words(r.key, iv, r.key_words, lane);
+        roll_words(r.delta, iv, 10, lane);
+        roll_words(r.jac, iv, 225, lane);
+        roll_words(r.cov, iv, 225, lane);
+        roll_words(r.sqrt_info, iv, 225, lane);
+        roll_words(r.sum_dt, iv, 1, lane);
+      }
+      if (lane == 0) valid[j] = (int32_t)((v >> (j + 1)) & 1u);
+    }
+    if (lane == 0) valid[9] = 0;
+  } else if (flag == AVM_MARGIN_SECOND_NEW) {
+    if (lane < 2) valid[8 + lane] = 0;
+  }
+}
+
+void launch_preint_match(const PreintArgs& a, const PreintKeys& k, hipStream_t stream) {
+  const long n_iv = (long)a.n_windows * 10;
+  const int blocks = (int)((n_iv * 16 + MTM - 1) / MTM);
+  hipLaunchKernelGGL(preint_match_kernel, dim3(blocks), dim3(MTM), 0, stream, a, k);
+}
+
+void launch_preint_roll(const PreintRoll& r, hipStream_t stream) {
+  const int blocks = (r.n_windows + MT / 64 - 1) / (MT / 64);
+  hipLaunchKernelGGL(preint_roll_kernel, dim3(blocks), dim3(MT), 0, stream, r);
 }
 
 void launch_preint(const PreintArgs& a, hipStream_t stream) {

@@ -70,6 +70,7 @@ def lib():
         L.avm_debug_last_marg_form.argtypes = [vp]
         L.avm_debug_last_fsel_form.argtypes = [vp]
         L.avm_debug_counters.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.avm_debug_preint_cache.argtypes = [vp, C.POINTER(C.c_int64)]
         L.avm_debug_fsel_evaluations.argtypes = [vp, C.POINTER(C.c_int64)]
         L.avm_debug_solve_tp_occupancy.argtypes = [C.POINTER(C.c_int)]
         L.avm_slide_window.argtypes = [vp, C.c_int, C.POINTER(abi.WindowBatch), C.c_int32, C.c_int32, C.c_double]
@@ -188,6 +189,14 @@ class Context:
         self.check(self._L.avm_debug_counters(self.h, out), "avm_debug_counters")
         return {"allocations": int(out[0]), "prior_one_wavefront": int(out[1]), "prior_windows": int(out[2]),
                 "prior_pivoted_path": int(out[2] - out[1]), "solve_form": "throughput" if out[3] else "latency"}
+
+    def preint_cache(self) -> dict:
+        """The ctx's pre-integration cache: intervals the last pre-integration examined and how many of them it integrated (the ones
+        whose IMU samples or linearization biases differ from what the stored results came from; all of them with AVM_PREINT_CACHE=0),
+        and the windows whose cached intervals the last slide_window rolled (0: it left the cache alone)."""
+        out = (C.c_int64 * 3)()
+        self.check(self._L.avm_debug_preint_cache(self.h, out), "avm_debug_preint_cache")
+        return {"examined": int(out[0]), "recomputed": int(out[1]), "rolled_windows": int(out[2])}
 
     def kernel_ms(self, which: str) -> float:
         ms = C.c_float(0)

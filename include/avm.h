@@ -375,7 +375,16 @@ int avm_window_solve(avm_ctx* ctx, const avm_options* opt, avm_mem mem, const av
                      avm_prior_out* prior_out, avm_solve_summary* summary);
 
 /* A4 only: IntegrationBase for every interval of every window (integration_base.h:13-158).
- * out_* are [B][10][...]: delta (p3,q4 xyzw,v3 = 10), jacobian 15x15, covariance 15x15, sum_dt. */
+ * out_* are [B][10][...]: delta (p3,q4 xyzw,v3 = 10), jacobian 15x15, covariance 15x15, sum_dt.
+ *
+ * The ctx remembers its last pre-integration - this call's, and the one inside avm_window_solve_batch* and
+ * avm_window_eval_factors - together with a copy of the inputs every interval was integrated from (imu_n, the samples and
+ * dt up to imu_n, imu_lin_ba / imu_lin_bg; about 1.2 KB per interval at max_samp = 20).  The next call compares every
+ * interval's inputs with that copy, bit by bit, on the device, and integrates only the intervals that differ; a call with
+ * another n_windows, max_samp or noise density integrates all of them, and avm_slide_window* moves the remembered
+ * intervals with the window.  Content decides, nothing else: there is nothing to invalidate or to tell the ctx, the
+ * results are those of integrating everything, and changing a sample in place is seen.  AVM_PREINT_CACHE=0 in the
+ * environment (read on every call) integrates every interval on every call. */
 int avm_imu_preintegrate_batch(avm_ctx* ctx, const avm_options* opt, avm_mem mem,
                                const avm_window_batch* batch, double* out_delta, double* out_jacobian,
                                double* out_covariance, double* out_sum_dt);
