@@ -294,6 +294,18 @@ TRACK_PROTOTYPES = {
 }
 
 
+class SelectState(C.Structure):
+    """avm_select_state (include/avm.h): the members of FeatureSelector that outlive a call, one row per stream."""
+    _fields_ = [("max_tracked", C.c_int32), ("last_feature_id", c_ip), ("n_tracked", c_ip), ("tracked_id", c_ip), ("first_image", c_ip)]
+
+
+# FeatureSelector::select() on device-resident images (include/avm.h).  A dict of its own again; lib.py applies it like the other two.
+SELECT_PROTOTYPES = {
+    "avm_fsel_select_image_batch": [C.c_void_p, C.c_int, C.POINTER(ImageBatch), c_dp, c_ip, C.c_int32, C.c_int32, C.POINTER(SelectState),
+                                    C.POINTER(FselBatch), C.POINTER(FselOut), C.POINTER(ImageBatch)],
+}
+
+
 def default_options() -> Options:
     """Values the reference runs with (estimator.cpp:794-806, euroc_config.yaml:54-63) + Ceres defaults.
 

@@ -90,7 +90,8 @@ TRACK_KEYS = ("n_feat", "feat_start", "feat_nobs", "feat_obs_begin", "obs_xy", "
 
 class ImageArrays(_Arrays):
     """avm_image_batch: one image per window, what processImage gets from the tracker (camera 0): n_pts [B], feature_id [B, max_pts]
-    strictly ascending, xy [B, max_pts, 2] and, with the time offset, vel_td [B, max_pts, 4] (velocity.x, velocity.y, cur_td, uv.y)."""
+    strictly ascending, xy [B, max_pts, 2] and, with the time offset, vel_td [B, max_pts, 4] (velocity.x, velocity.y, cur_td, uv.y).
+    Optionally `prob` [B, max_pts], the fPROB channel: not a member of the struct, the array FeatureSelector.select_stream takes beside it."""
 
     F64, I32 = ["xy", "vel_td"], ["n_pts", "feature_id"]
 
@@ -102,12 +103,17 @@ class ImageArrays(_Arrays):
         return self.dims["n_windows"]
 
     @staticmethod
-    def from_maps(images, max_pts: int, with_td: bool = False) -> "ImageArrays":
-        """images: per window a dict {feature id: (x, y)} or, with_td, {feature id: (x, y, vx, vy, cur_td, v)}; std::map order = sorted ids."""
+    def from_maps(images, max_pts: int, with_td: bool = False, prob=None) -> "ImageArrays":
+        """images: per window a dict {feature id: (x, y)} or, with_td, {feature id: (x, y, vx, vy, cur_td, v)}; std::map order = sorted ids.
+        prob: per window a dict {feature id: probability} (the `prob` array), or None."""
         B = len(images)
         a = {"n_pts": np.zeros(B, np.int32), "feature_id": np.zeros((B, max_pts), np.int32), "xy": np.zeros((B, max_pts, 2))}
         if with_td:
             a["vel_td"] = np.zeros((B, max_pts, 4))
+        if prob is not None:
+            a["prob"] = np.zeros((B, max_pts))
+            for b, im in enumerate(images):
+                a["prob"][b, :len(im)] = [prob[b][fid] for fid in sorted(im)]
         for b, im in enumerate(images):
             ids = sorted(im)
             assert len(ids) <= max_pts
@@ -118,6 +124,28 @@ class ImageArrays(_Arrays):
                 if with_td:
                     a["vel_td"][b, i] = im[fid][2:6]
         return ImageArrays({"n_windows": B, "max_pts": max_pts}, a)
+
+
+class SelectorState(_Arrays):
+    """avm_select_state: the members of FeatureSelector that outlive a call, one row per stream - last_feature_id [B] (lastFeatureId_),
+    n_tracked [B] and tracked_id [B, max_tracked] (trackedFeatures_, append order), first_image [B] (firstImage_).  alloc() gives the
+    state of freshly constructed selectors; copy / to_device / to_host as every *Arrays."""
+
+    I32 = ["last_feature_id", "n_tracked", "tracked_id", "first_image"]
+
+    @staticmethod
+    def alloc(n_windows: int, max_tracked: int, device=None) -> "SelectorState":
+        a = {"last_feature_id": np.zeros(n_windows, np.int32), "n_tracked": np.zeros(n_windows, np.int32),
+             "tracked_id": np.zeros((n_windows, max_tracked), np.int32), "first_image": np.ones(n_windows, np.int32)}
+        s = SelectorState({"max_tracked": max_tracked}, a)
+        return s.to_device(device) if device else s
+
+    def struct(self) -> abi.SelectState:
+        return self._fill(abi.SelectState())
+
+    @property
+    def n_windows(self) -> int:
+        return self.a["n_tracked"].shape[0]
 
 
 class TrackTables:

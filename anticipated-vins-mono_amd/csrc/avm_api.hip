@@ -16,6 +16,7 @@
 #include <rccl/rccl.h>  // types only: the library is dlopen'ed (avm_comm_*), a single-GPU host never needs it
 
 #include "kernels.hpp"
+#include "select_image.hpp"
 
 using namespace avm;
 
@@ -1783,25 +1784,13 @@ int fsel_buffers(avm_ctx* c, const avm_fsel_batch* b, FselBuffers* w, bool may_s
   return AVM_OK;
 }
 
-}  // namespace
-
-int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, avm_fsel_out* out) {
-  if (!c) return AVM_ERR_INVALID;
-  (void)hipSetDevice(c->device);
-  int rc = check_fsel(c, batch);
-  if (rc != AVM_OK) return rc;
-  if (!out || !out->n_selected || !out->selected_ids) return fail(c, AVM_ERR_INVALID, "null output");
-  if (batch->n_problems == 0) return AVM_OK;
-  // Host tables are checked on the host.  Device-resident ones by a kernel that runs AHEAD of the select on the same stream:
-  // every kernel of the select looks at its flag before it indexes with a table, and the host reads the verdict behind the
-  // synchronization that brings the results (no extra round trip for the check).
-  FlagCheck check;
-  if ((rc = mem == AVM_MEM_HOST ? validate_fsel(c, mem, batch) : validate_fsel_begin(c, batch, &check)) != AVM_OK) return rc;
+// The selection of avm_fsel_select_batch, from the choice of its mode to the re-runs and the fallback counters: what that entry point and
+// avm_fsel_select_image_batch share.  d / dout: the problem and its outputs on the device; batch / out: the caller's (the outputs travel
+// back to `out` in host mode); check: the table check in flight on the stream (check.dev == null: the tables were checked on the host).
+int run_fsel_select(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, const avm_fsel_batch& d, avm_fsel_out* out, const avm_fsel_out& dout,
+                    const FlagCheck& check) {
+  int rc;
   int* const vflag = check.dev;
-  avm_fsel_batch d;
-  if ((rc = on_device(c, mem, FSEL, U_WHOLE, batch, &d, "f_pack")) != AVM_OK) return rc;
-  avm_fsel_out dout = *out;
-  if (mem == AVM_MEM_HOST && alloc_out(c, FSEL_OUT, out, &dout, batch) != AVM_OK) return fail(c, AVM_ERR_HIP, "hipMalloc failed (selector out)");
   const size_t P = batch->n_problems, mf = batch->max_features;
   FselBuffers w;
   if ((rc = fsel_buffers(c, &d, &w, fsel_takes_solo(&d))) != AVM_OK) return rc;
@@ -1867,6 +1856,129 @@ int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, 
   if (rerun) c->fsel_reruns++;
   float ms = 0;
   if (hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) c->last_ms["fsel_select"] = ms;
+  return AVM_OK;
+}
+
+const TrackRule SELECT_IMAGE_RULES[8] = {
+    {AVM_ERR_INVALID, "bad table"},
+    {AVM_ERR_INVALID, "n_pts outside [0, max_pts]"},
+    {AVM_ERR_INVALID, "the image's feature ids must be strictly ascending (std::map order)"},
+    {AVM_ERR_INVALID, "n_tracked outside [0, max_tracked]"},
+    {AVM_ERR_CAPACITY, "more new points than problem->max_cand"},
+    {AVM_ERR_CAPACITY, "more tracked points in the image than problem->max_used"},
+    {AVM_ERR_CAPACITY, "the subset and the points the selection can add do not fit image_out->max_pts"},
+    {AVM_ERR_CAPACITY, "the tracked ids kept and the ids the call can append do not fit state->max_tracked"}};
+
+}  // namespace
+
+int avm_fsel_select_batch(avm_ctx* c, avm_mem mem, const avm_fsel_batch* batch, avm_fsel_out* out) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  int rc = check_fsel(c, batch);
+  if (rc != AVM_OK) return rc;
+  if (!out || !out->n_selected || !out->selected_ids) return fail(c, AVM_ERR_INVALID, "null output");
+  if (batch->n_problems == 0) return AVM_OK;
+  // Host tables are checked on the host.  Device-resident ones by a kernel that runs AHEAD of the select on the same stream:
+  // every kernel of the select looks at its flag before it indexes with a table, and the host reads the verdict behind the
+  // synchronization that brings the results (no extra round trip for the check).
+  FlagCheck check;
+  if ((rc = mem == AVM_MEM_HOST ? validate_fsel(c, mem, batch) : validate_fsel_begin(c, batch, &check)) != AVM_OK) return rc;
+  avm_fsel_batch d;
+  if ((rc = on_device(c, mem, FSEL, U_WHOLE, batch, &d, "f_pack")) != AVM_OK) return rc;
+  avm_fsel_out dout = *out;
+  if (mem == AVM_MEM_HOST && alloc_out(c, FSEL_OUT, out, &dout, batch) != AVM_OK) return fail(c, AVM_ERR_HIP, "hipMalloc failed (selector out)");
+  return run_fsel_select(c, mem, batch, d, out, dout, check);
+}
+
+// FeatureSelector::select() around that selection, on device-resident images (tracks.hip: check, split, merge)
+int avm_fsel_select_image_batch(avm_ctx* c, avm_mem mem, const avm_image_batch* img, const double* prob, const int32_t* initialized,
+                                int32_t init_thresh, int32_t prune_lost, avm_select_state* st, avm_fsel_batch* problem, avm_fsel_out* out,
+                                avm_image_batch* img_out) {
+  if (!c) return AVM_ERR_INVALID;
+  (void)hipSetDevice(c->device);
+  if (!img || !st || !problem || !img_out || img->n_windows < 0) return fail(c, AVM_ERR_INVALID, "null/negative argument");
+  int rc = check_fsel(c, problem);
+  if (rc != AVM_OK) return rc;
+  if (!out || !out->n_selected || !out->selected_ids) return fail(c, AVM_ERR_INVALID, "null output");
+  if (problem->n_problems != img->n_windows) return fail(c, AVM_ERR_INVALID, "problem->n_problems differs from image->n_windows");
+  if (img_out->n_windows != img->n_windows) return fail(c, AVM_ERR_INVALID, "image_out->n_windows differs from image->n_windows");
+  if (img->max_pts < 0 || img_out->max_pts < 0 || st->max_tracked < 0 || problem->max_used < 0)
+    return fail(c, AVM_ERR_INVALID, "negative stride (max_pts / max_tracked / max_used)");
+  if (img->max_pts > AVM_MAX_IMAGE_PTS) return fail(c, AVM_ERR_CAPACITY, "max_pts > 1024 (AVM_MAX_IMAGE_PTS)");
+  if (!img->n_pts || (img->max_pts > 0 && (!img->feature_id || !img->xy || !prob))) return fail(c, AVM_ERR_INVALID, "null image table / prob");
+  if (!st->last_feature_id || !st->n_tracked || !st->first_image || (st->max_tracked > 0 && !st->tracked_id))
+    return fail(c, AVM_ERR_INVALID, "null member of state");
+  if (!problem->n_cand || !problem->cand_id || !problem->cand_xy || !problem->cand_prob || !problem->n_used ||
+      (problem->max_used > 0 && (!problem->used_id || !problem->used_xy)))
+    return fail(c, AVM_ERR_INVALID, "null member of problem (n_cand, cand_*, n_used, used_* are written)");
+  if (!img_out->n_pts || (img_out->max_pts > 0 && (!img_out->feature_id || !img_out->xy))) return fail(c, AVM_ERR_INVALID, "null table of image_out");
+  if ((img->vel_td != nullptr) != (img_out->vel_td != nullptr))
+    return fail(c, AVM_ERR_INVALID, "image_out->vel_td must be given if and only if image->vel_td is");
+  if (img_out->n_pts == img->n_pts || (img_out->feature_id && img_out->feature_id == img->feature_id) || (img_out->xy && img_out->xy == img->xy) ||
+      (img_out->vel_td && img_out->vel_td == img->vel_td))
+    return fail(c, AVM_ERR_INVALID, "image_out's tables must not be image's own arrays");
+  if (img->n_windows == 0) return AVM_OK;
+  const size_t B = img->n_windows, P = (size_t)img->max_pts, PO = (size_t)img_out->max_pts, T = (size_t)st->max_tracked;
+  SelectImageArgs a;
+  a.image = *img, a.init_thresh = init_thresh, a.prune_lost = prune_lost, a.state = *st, a.image_out = *img_out;
+  if ((rc = array_in(c, mem, "si_n_pts", img->n_pts, B, &a.image.n_pts)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "si_ids", img->feature_id, B * P, &a.image.feature_id)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "si_xy", img->xy, B * P * 2, &a.image.xy)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "si_vel_td", img->vel_td, B * P * 4, &a.image.vel_td)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "si_prob", prob, B * P, &a.prob)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "si_init", initialized, B, &a.initialized)) != AVM_OK) return rc;
+  // (what the call writes travels in as well: the slots it does not write keep what they held)
+  const int32_t *s_last, *s_nt, *s_ids, *s_first, *o_n, *o_ids;
+  const double *o_xy, *o_td;
+  if ((rc = array_in(c, mem, "ss_last", static_cast<const int32_t*>(st->last_feature_id), B, &s_last)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ss_n", static_cast<const int32_t*>(st->n_tracked), B, &s_nt)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ss_ids", static_cast<const int32_t*>(st->tracked_id), B * T, &s_ids)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "ss_first", static_cast<const int32_t*>(st->first_image), B, &s_first)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "so_n_pts", img_out->n_pts, B, &o_n)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "so_ids", img_out->feature_id, B * PO, &o_ids)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "so_xy", img_out->xy, B * PO * 2, &o_xy)) != AVM_OK) return rc;
+  if ((rc = array_in(c, mem, "so_vel_td", img_out->vel_td, B * PO * 4, &o_td)) != AVM_OK) return rc;
+  a.state.last_feature_id = const_cast<int32_t*>(s_last), a.state.n_tracked = const_cast<int32_t*>(s_nt);
+  a.state.tracked_id = const_cast<int32_t*>(s_ids), a.state.first_image = const_cast<int32_t*>(s_first);
+  a.image_out.n_pts = o_n, a.image_out.feature_id = o_ids, a.image_out.xy = o_xy, a.image_out.vel_td = o_td;
+  if ((rc = on_device(c, mem, FSEL, U_WHOLE, static_cast<const avm_fsel_batch*>(problem), &a.problem)) != AVM_OK) return rc;
+  a.out = *out;
+  if (mem == AVM_MEM_HOST && alloc_out(c, FSEL_OUT, out, &a.out, problem) != AVM_OK) return fail(c, AVM_ERR_HIP, "hipMalloc failed (selector out)");
+  // the check on its own, its verdict on the host before the first kernel that writes; then the split, which writes `problem` only
+  if ((rc = track_check(c, [&](int* flag) { return launch_select_image_check(a, flag, c->stream); }, SELECT_IMAGE_RULES)) != AVM_OK) return rc;
+  HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+  HIPCHK(c, launch_select_split(a, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+  // the caller's tables of the problem (n_cloud, nr_imu) with the counts the split wrote: the selection's own check, ahead of it on the stream
+  FlagCheck check;
+  if ((rc = validate_fsel_begin(c, &a.problem, &check)) != AVM_OK) return rc;
+  if ((rc = run_fsel_select(c, mem, problem, a.problem, out, a.out, check)) != AVM_OK) return rc;
+  float t_check = 0, t_split = 0, t_merge = 0;
+  if (hipEventElapsedTime(&t_check, c->ev[0], c->ev[1]) == hipSuccess && hipEventElapsedTime(&t_split, c->ev[5], c->ev[6]) == hipSuccess)
+    c->last_ms["select_split"] = t_check + t_split;
+  // the selection has finished, its re-runs included: image_out and the state
+  HIPCHK(c, hipEventRecord(c->ev[5], c->stream));
+  HIPCHK(c, launch_select_merge(a, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
+  const avm_fsel_batch& dp = a.problem;
+  const size_t mc = (size_t)problem->max_cand, mu = (size_t)problem->max_used;
+  if ((rc = array_back(c, mem, const_cast<int32_t*>(problem->n_cand), dp.n_cand, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<int32_t*>(problem->cand_id), dp.cand_id, B * mc)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<double*>(problem->cand_xy), dp.cand_xy, B * mc * 2)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<double*>(problem->cand_prob), dp.cand_prob, B * mc)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<int32_t*>(problem->n_used), dp.n_used, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<int32_t*>(problem->used_id), dp.used_id, B * mu)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<double*>(problem->used_xy), dp.used_xy, B * mu * 2)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, st->last_feature_id, s_last, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, st->n_tracked, s_nt, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, st->tracked_id, s_ids, B * T)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, st->first_image, s_first, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<int32_t*>(img_out->n_pts), o_n, B)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<int32_t*>(img_out->feature_id), o_ids, B * PO)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<double*>(img_out->xy), o_xy, B * PO * 2)) != AVM_OK) return rc;
+  if ((rc = array_back(c, mem, const_cast<double*>(img_out->vel_td), o_td, B * PO * 4)) != AVM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (hipEventElapsedTime(&t_merge, c->ev[5], c->ev[6]) == hipSuccess) c->last_ms["select_merge"] = t_merge;
   return AVM_OK;
 }
 

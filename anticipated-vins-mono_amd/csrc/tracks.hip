@@ -1,11 +1,13 @@
 // tracks.hip — the feature manager's per-image bookkeeping on device-resident tables (include/avm.h, "the feature manager on
 // device-resident tables"): FeatureManager::addFeatureCheckParallax's append by feature id (feature_manager.cpp:45-72), the buffer half of
 // Estimator::processIMU (estimator.cpp:92-98), the solve's filtered view of the whole list (estimator.cpp:715) and setDepth's copy back
-// (feature_manager.cpp:141-159).  Integer bookkeeping and copies only: no floating-point operation in this file.
+// (feature_manager.cpp:141-159); and FeatureSelector::select()'s bookkeeping around the selection on the tracker's image
+// (feature_selector.cpp:98-120, 156-196, 208-219; select_image.hpp).  Integer bookkeeping and copies only: no floating-point operation in this file.
 // One 256-thread workgroup per window in the kernels that walk a list; every call has a check kernel of the same shape that runs first,
 // on its own, and writes nothing but the verdict (kernels.hpp), so that a refused batch leaves every table of every window as it was.
 #include "devmath.hpp"
 #include "kernels.hpp"
+#include "select_image.hpp"
 
 namespace avm {
 namespace {
@@ -326,6 +328,197 @@ __global__ __launch_bounds__(TRK_NT) void store_depths_kernel(avm_window_batch F
     F.inv_depth[(size_t)w * F.max_feat + view_row[(size_t)w * V.max_feat + k]] = V.inv_depth[(size_t)w * V.max_feat + k];
 }
 
+// ---- avm_fsel_select_image_batch -----------------------------------------------------------------------------------------------------
+// FeatureSelector::select()'s bookkeeping (feature_selector.cpp:98-120, 156-196) around the selection: check, split (image -> the
+// selector problem), merge (selection -> image_out and the selector's state).  The three kernels see a window the same way, through
+// SelWindow: counts clamped to the strides, so that every index below is inside its table whatever the tables hold.
+struct SelWindow {
+  int np, nt, s;  // image points, tracked ids, old points: ids[0 .. s) <= last_feature_id < ids[s .. np)  (splitOnFeatureId, :208-219)
+  bool init, first;
+};
+
+// number of ids[0 .. n) that are <= k: std::map::upper_bound (memory-safe on any input)
+AVM_DEV int upper_bound_id(const int* ids, int n, int k) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ids[mid] <= k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Stages the window's ids in s_id, clears s_mark and splits; ends with a workgroup barrier.  Every member is uniform over the workgroup.
+AVM_DEV SelWindow sel_stage(const SelectImageArgs& a, int w, int* s_id, int* s_mark) {
+  SelWindow q;
+  q.np = min(max(a.image.n_pts[w], 0), min(a.image.max_pts, AVM_MAX_IMAGE_PTS));
+  q.nt = min(max(a.state.n_tracked[w], 0), a.state.max_tracked);
+  q.init = a.initialized ? a.initialized[w] != 0 : true;
+  q.first = a.state.first_image[w] != 0;
+  const int last = a.state.last_feature_id[w];
+  const int32_t* ids = a.image.feature_id + (size_t)w * a.image.max_pts;
+  for (int i = threadIdx.x; i < q.np; i += TRK_NT) s_id[i] = ids[i], s_mark[i] = 0;
+  __syncthreads();
+  q.s = upper_bound_id(s_id, q.np, last);
+  return q;
+}
+
+// s_mark[p] = 1 for the old points whose id is in the tracked list: one thread per TRACKED id looks it up in the image (the list is in
+// append order, unsorted).  No barrier.
+AVM_DEV void sel_mark_tracked(const SelWindow& q, const int32_t* tracked, const int* s_id, int* s_mark) {
+  for (int t = threadIdx.x; t < q.nt; t += TRK_NT) {
+    const int p = find_id(s_id, q.s, tracked[t]);
+    if (p >= 0) s_mark[p] = 1;
+  }
+}
+
+// The same walk TRK_NT entries at a time in list order, with the entries that stay in the list ranked (all of them, or with `prune` the
+// ones found in the image): emit(id, rank) for each, their number returned to every thread.  Item i of a chunk is ranked by thread i, so
+// `id` is the thread's own register, read behind sources_read_barrier() before the chunk's first emit: emit may write the list in place.
+// s_keep: TRK_NT ints of LDS.  Ends with a workgroup barrier unless the list is empty.
+template <class Emit>
+AVM_DEV int sel_walk_tracked(const SelWindow& q, const int32_t* tracked, int prune, const int* s_id, int* s_mark, int* s_keep, int* s_tot,
+                             Emit emit) {
+  int kept = 0;
+  for (int base = 0; base < q.nt; base += TRK_NT) {  // (uniform bounds)
+    const int t = base + threadIdx.x;
+    int id = 0, keep = 0;
+    if (t < q.nt) {
+      id = tracked[t];
+      const int p = find_id(s_id, q.s, id);
+      if (p >= 0) s_mark[p] = 1;
+      keep = p >= 0 || !prune;
+    }
+    s_keep[threadIdx.x] = keep;
+    sources_read_barrier();
+    const int n = block_compact(min(TRK_NT, q.nt - base), s_tot, [&](int i) { return s_keep[i] != 0; }, [&](int, int rank) { emit(id, kept + rank); });
+    kept += n;
+  }
+  return kept;
+}
+
+__global__ __launch_bounds__(TRK_NT) void select_image_check_kernel(SelectImageArgs a, int* first_bad) {
+  __shared__ int s_id[AVM_MAX_IMAGE_PTS], s_mark[AVM_MAX_IMAGE_PTS], s_tot[TRK_MAX_CHUNKS], s_keep[TRK_NT], s_bad;
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int np = a.image.n_pts[w], nt = a.state.n_tracked[w];
+  if (np < 0 || np > a.image.max_pts || nt < 0 || nt > a.state.max_tracked) {  // (uniform over the workgroup)
+    if (tid == 0) report(first_bad, w, np < 0 || np > a.image.max_pts ? SEL_BAD_NPTS : SEL_BAD_NTRACKED);
+    return;
+  }
+  if (tid == 0) s_bad = 0;
+  const SelWindow q = sel_stage(a, w, s_id, s_mark);
+  bool bad = false;
+  for (int i = tid + 1; i < q.np; i += TRK_NT) bad = bad || s_id[i] <= s_id[i - 1];
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (s_bad) {  // (uniform; the lookups below want ascending ids)
+    if (tid == 0) report(first_bad, w, SEL_BAD_IDS);
+    return;
+  }
+  const int kept = sel_walk_tracked(q, a.state.tracked_id + (size_t)w * a.state.max_tracked, a.prune_lost, s_id, s_mark, s_keep, s_tot, [](int, int) {});
+  const int n_used = block_compact(q.s, s_tot, [&](int i) { return s_mark[i] != 0; }, [](int, int) {});
+  if (tid != 0) return;
+  const int n_new = q.np - q.s, n_old = q.s;
+  const int picks = min(max(0, a.problem.max_features - n_used), n_new);  // min(kappa, n_new): the most the selection can return
+  int n_out, n_app;
+  if (q.init) n_out = n_used + picks, n_app = picks;
+  else {
+    n_out = q.first ? n_new : n_used, n_app = q.first ? n_new : 0;
+    if (n_out < a.init_thresh) n_out = q.first ? q.np : n_old;
+  }
+  int rule = 1 << 30;
+  if (q.init && n_new > a.problem.max_cand) rule = min(rule, (int)SEL_CAP_CAND);
+  if (n_used > a.problem.max_used) rule = min(rule, (int)SEL_CAP_USED);
+  if (n_out > a.image_out.max_pts) rule = min(rule, (int)SEL_CAP_IMAGE);
+  if (kept + n_app > a.state.max_tracked) rule = min(rule, (int)SEL_CAP_TRACKED);
+  if (rule != 1 << 30) report(first_bad, w, rule);
+}
+
+// Writes problem.n_used / used_* (every window) and n_cand / cand_* (initialized windows; the others get n_cand = 0): nothing else.
+__global__ __launch_bounds__(TRK_NT) void select_split_kernel(SelectImageArgs a) {
+  __shared__ int s_id[AVM_MAX_IMAGE_PTS], s_mark[AVM_MAX_IMAGE_PTS], s_tot[TRK_MAX_CHUNKS];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const SelWindow q = sel_stage(a, w, s_id, s_mark);
+  sel_mark_tracked(q, a.state.tracked_id + (size_t)w * a.state.max_tracked, s_id, s_mark);
+  __syncthreads();
+  const avm_fsel_batch& F = a.problem;
+  const double* ixy = a.image.xy + (size_t)w * a.image.max_pts * 2;
+  int32_t* used_id = const_cast<int32_t*>(F.used_id) + (size_t)w * F.max_used;
+  double* used_xy = const_cast<double*>(F.used_xy) + (size_t)w * F.max_used * 2;
+  const int n_used = block_compact(q.s, s_tot, [&](int i) { return s_mark[i] != 0; },
+                                   [&](int i, int rank) {
+                                     if (rank >= F.max_used) return;
+                                     used_id[rank] = s_id[i];
+                                     *reinterpret_cast<d2*>(used_xy + 2 * (size_t)rank) = *reinterpret_cast<const d2*>(ixy + 2 * (size_t)i);
+                                   });
+  // the new points are the tail of the image: their rank in index order is i - s
+  const int n_cand = q.init ? min(q.np - q.s, F.max_cand) : 0;
+  int32_t* cand_id = const_cast<int32_t*>(F.cand_id) + (size_t)w * F.max_cand;
+  double* cand_xy = const_cast<double*>(F.cand_xy) + (size_t)w * F.max_cand * 2;
+  double* cand_prob = const_cast<double*>(F.cand_prob) + (size_t)w * F.max_cand;
+  const double* prob = a.prob + (size_t)w * a.image.max_pts;
+  for (int j = tid; j < n_cand; j += TRK_NT) {
+    const int i = q.s + j;
+    cand_id[j] = s_id[i];
+    *reinterpret_cast<d2*>(cand_xy + 2 * (size_t)j) = *reinterpret_cast<const d2*>(ixy + 2 * (size_t)i);
+    cand_prob[j] = prob[i];
+  }
+  if (tid == 0) const_cast<int32_t*>(F.n_used)[w] = min(n_used, F.max_used), const_cast<int32_t*>(F.n_cand)[w] = n_cand;
+}
+
+// The selection is in a.out: image_out and the selector's state.  The tracked list is compacted in place, TRK_NT entries at a time in
+// list order: a kept entry moves left or stays, so a chunk's destinations are entries of this chunk or of earlier ones, all of which
+// have been read - this chunk's into registers, behind sources_read_barrier().
+__global__ __launch_bounds__(TRK_NT) void select_merge_kernel(SelectImageArgs a) {
+  __shared__ int s_id[AVM_MAX_IMAGE_PTS], s_mark[AVM_MAX_IMAGE_PTS], s_tot[TRK_MAX_CHUNKS], s_keep[TRK_NT];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const SelWindow q = sel_stage(a, w, s_id, s_mark);
+  const int n_new = q.np - q.s, max_tracked = a.state.max_tracked;
+  int32_t* tracked = a.state.tracked_id + (size_t)w * max_tracked;
+  const int kept = sel_walk_tracked(q, tracked, a.prune_lost, s_id, s_mark, s_keep, s_tot, [&](int id, int pos) { tracked[pos] = id; });
+  __syncthreads();
+  int n_app = 0;  // ids appended behind the kept ones
+  if (q.init) {
+    // the selected ids, in selection order: marked among the new points, appended to the list (:196)
+    n_app = min(max(a.out.n_selected[w], 0), a.problem.max_features);
+    const int32_t* sel = a.out.selected_ids + (size_t)w * a.problem.max_features;
+    for (int k = tid; k < n_app; k += TRK_NT) {
+      const int id = sel[k], p = find_id(s_id + q.s, n_new, id);
+      if (p >= 0) s_mark[q.s + p] = 1;
+      if (kept + k < max_tracked) tracked[kept + k] = id;
+    }
+  } else {
+    // :172-187 - the first image: the subset becomes the new points, all of them tracked from now on; too few points: every old one joins
+    const int n_used = block_compact(q.s, s_tot, [&](int i) { return s_mark[i] != 0; }, [](int, int) {});
+    const bool all_old = (q.first ? n_new : n_used) < a.init_thresh;
+    for (int i = tid; i < q.np; i += TRK_NT) s_mark[i] = i >= q.s ? q.first : (all_old || (!q.first && s_mark[i] != 0));
+    if (q.first) {
+      n_app = n_new;
+      for (int j = tid; j < n_new; j += TRK_NT)
+        if (kept + j < max_tracked) tracked[kept + j] = s_id[q.s + j];
+    }
+  }
+  __syncthreads();
+  const avm_image_batch& O = a.image_out;
+  const double* ixy = a.image.xy + (size_t)w * a.image.max_pts * 2;
+  const double* itd = a.image.vel_td ? a.image.vel_td + (size_t)w * a.image.max_pts * 4 : nullptr;
+  int32_t* oid = const_cast<int32_t*>(O.feature_id) + (size_t)w * O.max_pts;
+  double* oxy = const_cast<double*>(O.xy) + (size_t)w * O.max_pts * 2;
+  double* otd = itd ? const_cast<double*>(O.vel_td) + (size_t)w * O.max_pts * 4 : nullptr;
+  const int n_out = block_compact(q.np, s_tot, [&](int i) { return s_mark[i] != 0; },
+                                  [&](int i, int rank) {
+                                    if (rank >= O.max_pts) return;
+                                    oid[rank] = s_id[i];
+                                    *reinterpret_cast<d2*>(oxy + 2 * (size_t)rank) = *reinterpret_cast<const d2*>(ixy + 2 * (size_t)i);
+                                    if (otd) *reinterpret_cast<d4*>(otd + 4 * (size_t)rank) = *reinterpret_cast<const d4*>(itd + 4 * (size_t)i);
+                                  });
+  if (tid != 0) return;
+  const_cast<int32_t*>(O.n_pts)[w] = min(n_out, O.max_pts);
+  a.state.n_tracked[w] = min(kept + n_app, max_tracked);
+  if (n_new > 0) a.state.last_feature_id[w] = s_id[q.np - 1];
+  if (!q.init && q.first) a.state.first_image[w] = 0;
+}
+
 }  // namespace
 
 hipError_t launch_add_image_check(const avm_window_batch& b, const int32_t* feat_id, const avm_image_batch& img, int* first_bad, hipStream_t stream) {
@@ -367,6 +560,21 @@ hipError_t launch_store_depths_check(const avm_window_batch& full, const avm_win
 
 hipError_t launch_store_depths(const avm_window_batch& full, const avm_window_batch& view, const int32_t* view_row, hipStream_t stream) {
   hipLaunchKernelGGL(store_depths_kernel, dim3(full.n_windows), dim3(TRK_NT), 0, stream, full, view, view_row);
+  return hipGetLastError();
+}
+
+hipError_t launch_select_image_check(const SelectImageArgs& a, int* first_bad, hipStream_t stream) {
+  hipLaunchKernelGGL(select_image_check_kernel, dim3(a.image.n_windows), dim3(TRK_NT), 0, stream, a, first_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_select_split(const SelectImageArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(select_split_kernel, dim3(a.image.n_windows), dim3(TRK_NT), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_select_merge(const SelectImageArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(select_merge_kernel, dim3(a.image.n_windows), dim3(TRK_NT), 0, stream, a);
   return hipGetLastError();
 }
 

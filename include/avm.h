@@ -545,6 +545,60 @@ int avm_solve_view_store_depths(avm_ctx* ctx, avm_mem mem, avm_window_batch* ful
 int avm_slide_window_tracks(avm_ctx* ctx, avm_mem mem, avm_window_batch* windows, int32_t* feat_id /* [B][max_feat] in/out */,
                             const int32_t* marginalization_flags /* [B] */, int32_t shift_depth, double init_depth, int32_t remove_failures);
 
+/* ---- the selector in the stream loop: FeatureSelector::select() (feature_selector.cpp:74-202) on device-resident images ------------
+ * In the reference every image goes through select() before processImage (estimator_node.cpp:331-360).  This call is its bookkeeping
+ * around the selection - splitOnFeatureId (:208-219), the tracked-feature list (:108-120, 192-196), image.swap(subset) (:192) - for
+ * one image per window: it writes the selector problem from the image, runs the selection of avm_fsel_select_batch on it, and emits the
+ * image avm_add_image_batch takes.  Everything is in `mem` space. */
+typedef struct avm_select_state {  /* the members of FeatureSelector that outlive a call, one row per stream; in/out, `mem` space */
+  int32_t max_tracked;
+  int32_t* last_feature_id;  /* [B]               lastFeatureId_ */
+  int32_t* n_tracked;        /* [B] */
+  int32_t* tracked_id;       /* [B][max_tracked]  trackedFeatures_, in the reference's order (append order) */
+  int32_t* first_image;      /* [B]               firstImage_ */
+} avm_select_state;
+
+/* prob: [B][image->max_pts], the fPROB channel of the image's points.  initialized: [B] (NULL: every window), non-zero where
+ * solver_flag == NON_LINEAR.  init_thresh: initThresh_.
+ * `problem` is the caller's avm_fsel_batch with n_problems == image->n_windows.  The caller gives the horizon, nr_imu, delta_imu, the
+ * noise, camera and extrinsics, the cloud, max_features and the strides; the library WRITES n_cand, cand_id, cand_xy, cand_prob, n_used,
+ * used_id, used_xy into the caller's buffers (the const qualifiers are cast away, as in avm_solve_view_batch).  `image_out` is the
+ * caller's buffers in the same way: n_pts, feature_id, xy and, if and only if image->vel_td is given, vel_td are written.  None of its
+ * arrays may be an array of `image` (AVM_ERR_INVALID).  Slots of these arrays that the call does not write keep what they held.
+ * For every window, feature_selector.cpp:98-120, 156-196:
+ *   1. split: the points with id > last_feature_id (upper_bound) are NEW, the others OLD; if any are new, last_feature_id becomes the
+ *      image's last id.  A tracked id is looked up among the old points only (the reference searches `image` after the split), so a
+ *      tracked id above last_feature_id is never found.
+ *   2. used_* = the old points whose id is in tracked_id[0 .. n_tracked), ascending (n_used of every window).  An initialized window:
+ *      cand_* = the new points, ascending, with their prob, n_cand their number.  An uninitialized window: n_cand = 0 (that is what the
+ *      selection sees and the caller reads back; nothing is selected), its cand_* rows are not written.
+ *   3. the selection of avm_fsel_select_batch on exactly these arrays, kappa = max(0, max_features - n_used); `out` is its avm_fsel_out.
+ *   4. an uninitialized window with first_image != 0: the subset BECOMES the new points, every new id is appended to tracked_id in
+ *      ascending order, first_image = 0 (:172-181).  Then, for any uninitialized window whose subset has fewer than init_thresh points,
+ *      every old point joins the subset (:185-187).
+ *   5. image_out = the subset (the used points, or rule 4's) plus the selected points, in ascending id order (std::map order), which
+ *      is what avm_add_image_batch takes; xy and vel_td rows are copied bit for bit.
+ *   6. the selected ids are appended to tracked_id in selection order (:196).  prune_lost != 0: the tracked ids that were not found in
+ *      this image are dropped first, the others keeping their order.  The reference never prunes; its list grows without bound.  Pruning
+ *      gives the same `problem`, `out` and image_out on every later image as long as the tracker never issues a lost id again (the rule
+ *      avm_add_image_batch already requires of its caller) and no tracked id lies above last_feature_id: a dropped id could never be
+ *      found again.
+ * The state - last_feature_id, n_tracked, tracked_id, first_image - and image_out are written by the last kernel, after the selection
+ * (its re-runs in a slower mode included) has finished: a refused or failed call leaves them as they were.
+ * A check runs first and refuses the batch as a whole, naming the first offending window, before anything is written.  AVM_ERR_INVALID:
+ * n_pts outside [0, max_pts]; ids not strictly ascending; n_tracked outside [0, max_tracked]; a NULL member; image_out sharing an array
+ * with image.  AVM_ERR_CAPACITY: max_pts > AVM_MAX_IMAGE_PTS; an initialized window with more new points than problem->max_cand; more
+ * used points than problem->max_used; a window whose image_out can exceed image_out->max_pts, or whose tracked list can exceed
+ * state->max_tracked.  These two bounds are decided BEFORE the selection and are conservative on purpose: they take the selection to
+ * pick min(kappa, new points) ids, although it may end with fewer.  image_out: n_used + min(kappa, n_new) when initialized, what rule 4
+ * gives when not.  tracked list: the ids kept (n_tracked; with prune_lost the entries found in the image) plus min(kappa, n_new) when
+ * initialized, plus n_new when uninitialized with first_image != 0, plus nothing otherwise.
+ * (The tables of `problem` the caller gives - n_cloud, nr_imu - are checked as avm_fsel_select_batch checks them, behind the split.)
+ * avm_last_kernel_ms keys: "select_split" (the check and the split), "select_merge"; "fsel_select" is the selection's, as ever. */
+int avm_fsel_select_image_batch(avm_ctx* ctx, avm_mem mem, const avm_image_batch* image, const double* prob /* [B][image->max_pts] */,
+                                const int32_t* initialized /* [B], nullable */, int32_t init_thresh, int32_t prune_lost,
+                                avm_select_state* state, avm_fsel_batch* problem, avm_fsel_out* out, avm_image_batch* image_out);
+
 /* ---- Estimator::visualInitialAlign (estimator.cpp:355-431) with VisualIMUAlignment (initial/initial_aligment.cpp): the step that
  * moves solver_flag from INITIAL to NON_LINEAR.  It starts from the up-to-scale camera trajectory of initialStructure (relativePose,
  * GlobalSFM, solvePnP stay with the host: OpenCV and a Ceres BA) and is dense FP64 algebra on the raw IMU of all_image_frame. */
