@@ -17,7 +17,7 @@ from helpers import abi, buffers, synth
 
 pytestmark = pytest.mark.gpu
 
-PACK_LIMIT = 4 << 20  # csrc/avm_api.hip: batches up to 4 MiB travel packed, every table rounded up to 64 bytes
+PACK_LIMIT = 4 << 20  # csrc/api/staging.hpp: batches up to 4 MiB travel packed, every table rounded up to 64 bytes
 SUMMARY_FIELDS = ("num_iterations", "num_successful", "accept_mask", "termination", "cost_trace", "radius_trace")
 PRIOR_FIELDS = ("n", "nblk", "blk_kind", "blk_frame", "J", "r", "x0")
 
@@ -98,6 +98,64 @@ def test_a_second_identical_host_call_allocates_nothing(marg_solve_modes):
     print("allocations: fresh ctx %d, after the first host-mode call %d, after the second %d" % (c0, c1, c2))
     assert c2 - c1 == 0
     assert c1 == FIRST_CALL_ALLOCATIONS[marg_solve_modes["path"]]
+
+
+# The same for the entry points whose staging was moved onto the descriptor tables and array_in / array_out / array_back with the split
+# of avm_api.hip into csrc/api/*.hpp: 3 windows, max_feat 16, max_pts 8.  The counts come from a run of these calls against a build of
+# commit af70961 (the last one with the single avm_api.hip), not from the code under test.
+STAGING_FIRST_CALL_ALLOCATIONS = {"add_image": 15, "imu_push": 10, "solve_view": 15, "store_depths": 7, "keyframe_decision": 8,
+                                  "failure_detection": 4, "build_cloud": 12, "select_image": 52}
+
+
+@pytest.fixture(scope="module")
+def staging_calls(ctx):
+    """name -> call(ctx): one host-mode call of the entry point on fresh copies of the same small inputs (built once for the eight cases)"""
+    import copy
+
+    from test_mixed_batch import MIN_PARALLAX
+    from test_select_image import Case
+    from test_tracks import GOOD, _image, _set_tracks
+
+    from helpers import blank_windows
+
+    # (the rows of test_tracks._small in tables of strides 16 / 64: four of the five pass the solve's filter)
+    w = blank_windows(3, max_feat=16, max_obs=64, max_samp=8)
+    feats = [dict(id=i, start=st, obs=[(0.1 * i, 0.01 * k) for k in range(no)], inv_depth=0.5)
+             for i, st, no in ((10, 0, 10), (4, 2, 8), (2, 3, 3), (8, 7, 3), (6, 9, 1))]
+    fid = _set_tracks(w, [copy.deepcopy(feats) for _ in range(3)], False)
+    w.a["imu_n"][:] = 4
+    img = _image(GOOD, max_pts=8)
+    E = lambda ctx: _mod("estimator").Estimator(ctx=ctx, options=abi.default_options())
+    tables = lambda: buffers.TrackTables(w.copy(), fid.copy(), 16, 64)
+    viewed = tables()
+    E(ctx).solve_view(viewed)
+    assert viewed.view.a["n_feat"].tolist() == [4, 4, 4]
+    case = Case([(0, 0, 0, 0, 1, 0), (1, 1, 0, 1, 1, 0), (8, 5, 2, 4, 1, 1)], max_pts=8, max_used=8, max_tracked=16)
+    k1_pos, k1_quat = w.a["pose"][:, 10, :3].copy(), w.a["pose"][:, 10, 3:].copy()
+    return {
+        "add_image": lambda ctx: E(ctx).addFeatureCheckParallax(w.copy(), fid.copy(), img.copy(), MIN_PARALLAX),
+        "imu_push": lambda ctx: E(ctx).push_imu(w.copy(), np.full(3, 2), np.full((3, 4), 0.005), np.zeros((3, 4, 3)), np.zeros((3, 4, 3))),
+        "solve_view": lambda ctx: E(ctx).solve_view(tables()),
+        "store_depths": lambda ctx: E(ctx).setDepth(viewed),
+        "keyframe_decision": lambda ctx: E(ctx).keyframe_decision(w.copy(), MIN_PARALLAX),
+        "failure_detection": lambda ctx: E(ctx).failureDetection(w.copy(), np.zeros((3, 3))),
+        "build_cloud": lambda ctx: _mod("feature_selector").FeatureSelector(ctx=ctx).initKDTree(w.copy(), k1_pos, k1_quat, max_cloud=9),
+        "select_image": lambda ctx: case.run(ctx, "host", False),
+    }
+
+
+@pytest.mark.parametrize("name", sorted(STAGING_FIRST_CALL_ALLOCATIONS))
+def test_staging_allocations_of_the_smaller_entry_points(staging_calls, name):
+    call = staging_calls[name]
+    fresh = _mod("lib").Context(0)
+    counts = [fresh.counters()["allocations"]]
+    for _ in range(2):
+        call(fresh)
+        counts.append(fresh.counters()["allocations"])
+    fresh.close()
+    print("allocations of %s: fresh ctx %d, after the first host-mode call %d, after the second %d" % ((name,) + tuple(counts)))
+    assert counts[2] - counts[1] == 0
+    assert counts[1] - counts[0] == STAGING_FIRST_CALL_ALLOCATIONS[name]
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""GPU tier (-m gpu): the context's content-checked cache of the pre-integration (csrc/avm_api.hip run_preint,
+"""GPU tier (-m gpu): the context's content-checked cache of the pre-integration (csrc/api/preint.hpp run_preint,
 csrc/preint.hip preint_match_kernel / preint_roll_kernel).
 
 A context remembers, per (window, interval), the IMU inputs its stored pre-integration was computed from.  A later
