@@ -306,6 +306,31 @@ SELECT_PROTOTYPES = {
 }
 
 
+class ReloMsgBatch(C.Structure):
+    """avm_relo_msg_batch (include/avm.h): the loop-closure message of estimator_node.cpp:274-297, one row per stream."""
+    _fields_ = [("n_windows", C.c_int32), ("max_match", C.c_int32), ("has_msg", c_ip), ("frame_stamp", c_dp), ("n_match", c_ip),
+                ("match_id", c_ip), ("match_xy", c_dp), ("prev_relo_t", c_dp), ("prev_relo_q", c_dp)]
+
+
+class ReloState(C.Structure):
+    """avm_relo_state (include/avm.h): the Estimator members of the relocalization that outlive a call, one row per stream."""
+    _fields_ = [("max_match", C.c_int32), ("relocalization_info", c_ip), ("relo_frame", c_ip), ("relo_stamp", c_dp), ("n_match", c_ip),
+                ("match_id", c_ip), ("match_xy", c_dp), ("prev_relo_t", c_dp), ("prev_relo_q", c_dp), ("relo_pose", c_dp),
+                ("drift_correct_yaw", c_dp), ("drift_correct_t", c_dp), ("relo_relative_t", c_dp), ("relo_relative_q", c_dp),
+                ("relo_relative_yaw", c_dp)]
+
+
+# Relocalization and the prior hand-over in the stream loop (include/avm.h).  A dict of its own once more; lib.py applies it like the others.
+RELO_PROTOTYPES = {
+    "avm_headers_step_batch": [C.c_void_p, C.c_int, C.c_int32, c_dp, c_ip, c_dp],
+    "avm_set_relo_frame_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_dp, C.POINTER(ReloMsgBatch), C.POINTER(ReloState)],
+    "avm_relo_resolve_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.c_int32, c_ip, C.POINTER(ReloState), c_ip, c_ip, c_ip, c_dp,
+                               C.POINTER(C.c_int32)],
+    "avm_relo_finish_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(ReloState)],
+    "avm_prior_keep_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(PriorOut)],
+}
+
+
 def default_options() -> Options:
     """Values the reference runs with (estimator.cpp:794-806, euroc_config.yaml:54-63) + Ceres defaults.
 

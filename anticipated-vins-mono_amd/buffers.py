@@ -148,6 +148,69 @@ class SelectorState(_Arrays):
         return self.a["n_tracked"].shape[0]
 
 
+class ReloMsgArrays(_Arrays):
+    """avm_relo_msg_batch: the loop-closure message of estimator_node.cpp:274-297, one row per stream - has_msg [B], frame_stamp [B],
+    n_match [B], match_id [B, max_match] strictly ascending, match_xy [B, max_match, 2], prev_relo_t [B, 3], prev_relo_q [B, 4] (x y z w)."""
+
+    F64, I32 = ["frame_stamp", "match_xy", "prev_relo_t", "prev_relo_q"], ["has_msg", "n_match", "match_id"]
+
+    def struct(self) -> abi.ReloMsgBatch:
+        return self._fill(abi.ReloMsgBatch())
+
+    @property
+    def n_windows(self) -> int:
+        return self.dims["n_windows"]
+
+    @staticmethod
+    def from_messages(messages, max_match: int) -> "ReloMsgArrays":
+        """messages: per window None (no message) or a dict with frame_stamp, matches [(id, x, y), ...] in the message's order (match_points:
+        ascending ids), prev_relo_t (3) and prev_relo_q (x y z w)."""
+        B = len(messages)
+        a = {"has_msg": np.zeros(B, np.int32), "frame_stamp": np.zeros(B), "n_match": np.zeros(B, np.int32),
+             "match_id": np.zeros((B, max_match), np.int32), "match_xy": np.zeros((B, max_match, 2)), "prev_relo_t": np.zeros((B, 3)),
+             "prev_relo_q": np.tile([0.0, 0.0, 0.0, 1.0], (B, 1))}
+        for b, m in enumerate(messages):
+            if m is None:
+                continue
+            n = len(m["matches"])
+            assert n <= max_match
+            a["has_msg"][b], a["frame_stamp"][b], a["n_match"][b] = 1, m["frame_stamp"], n
+            for k, (fid, x, y) in enumerate(m["matches"]):
+                a["match_id"][b, k], a["match_xy"][b, k] = fid, (x, y)
+            a["prev_relo_t"][b], a["prev_relo_q"][b] = m["prev_relo_t"], m["prev_relo_q"]
+        return ReloMsgArrays({"n_windows": B, "max_match": max_match}, a)
+
+
+class ReloState(_Arrays):
+    """avm_relo_state: the Estimator members of the relocalization that outlive a call, one row per stream.  alloc() gives the state of
+    freshly constructed estimators: no relocalization pending, relo_pose rows (0, 0, 0, 0, 0, 0, 1)."""
+
+    F64 = ["relo_stamp", "match_xy", "prev_relo_t", "prev_relo_q", "relo_pose", "drift_correct_yaw", "drift_correct_t", "relo_relative_t",
+           "relo_relative_q", "relo_relative_yaw"]
+    I32 = ["relocalization_info", "relo_frame", "n_match", "match_id"]
+
+    @staticmethod
+    def alloc(n_windows: int, max_match: int, device=None) -> "ReloState":
+        B, unit = n_windows, [0.0, 0.0, 0.0, 1.0]
+        a = {"relocalization_info": np.zeros(B, np.int32), "relo_frame": np.zeros(B, np.int32), "relo_stamp": np.zeros(B),
+             "n_match": np.zeros(B, np.int32), "match_id": np.zeros((B, max_match), np.int32), "match_xy": np.zeros((B, max_match, 2)),
+             "prev_relo_t": np.zeros((B, 3)), "prev_relo_q": np.tile(unit, (B, 1)), "relo_pose": np.tile([0.0, 0.0, 0.0] + unit, (B, 1)),
+             "drift_correct_yaw": np.zeros(B), "drift_correct_t": np.zeros((B, 3)), "relo_relative_t": np.zeros((B, 3)),
+             "relo_relative_q": np.tile(unit, (B, 1)), "relo_relative_yaw": np.zeros(B)}
+        s = ReloState({"max_match": max_match}, a)
+        return s.to_device(device) if device else s
+
+    def struct(self) -> abi.ReloState:
+        return self._fill(abi.ReloState())
+
+    @property
+    def n_windows(self) -> int:
+        return self.a["n_match"].shape[0]
+
+
+PRIOR_KEYS = ("n", "nblk", "blk_kind", "blk_frame", "J", "r", "x0")   # avm_prior_out's arrays; the batch's are prior_<key>
+
+
 class TrackTables:
     """The tables of a batch of streams whose feature manager lives in the library (include/avm.h, "the feature manager on
     device-resident tables"): `full` holds the whole f_manager.feature list of every window (strides up to MAX_FEAT_WIDE /
@@ -181,6 +244,18 @@ class TrackTables:
     @property
     def on_device(self) -> bool:
         return self.full.on_device
+
+    def swap_prior(self, prior: "PriorOutArrays"):
+        """The prior hand-over behind Estimator.keep_prior(): the seven arrays of `prior` and the batch's prior_* change places, in `full` and
+        in `view` (they share them).  `prior` then holds the slots the next solve may write.  Raises on unequal strides."""
+        d = self.full.dims
+        if (prior.dims["max_prior"], prior.dims["max_pblk"]) != (d["max_prior"], d["max_pblk"]):
+            raise ValueError("swap_prior: the prior slots' strides %r differ from the batch's %r" %
+                             ((prior.dims["max_prior"], prior.dims["max_pblk"]), (d["max_prior"], d["max_pblk"])))
+        for k in PRIOR_KEYS:
+            mine = self.full.a["prior_" + k]
+            self.full.a["prior_" + k] = self.view.a["prior_" + k] = prior.a[k]
+            prior.a[k] = mine
 
     def _rebuilt(self, conv, full):
         d = self.view.dims

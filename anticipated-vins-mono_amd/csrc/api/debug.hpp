@@ -94,6 +94,17 @@ int avm_debug_track_struct_sizes(int* out) {
   return n;
 }
 
+// test hook (not in avm.h): sizeof of avm_relo_msg_batch / avm_relo_state and the offsets of their first and last pointer members, for the
+// ctypes mirror check; out: >= 6 ints
+int avm_debug_relo_struct_sizes(int* out) {
+  int n = 0;
+  out[n++] = (int)sizeof(avm_relo_msg_batch), out[n++] = (int)sizeof(avm_relo_state);
+  for (size_t o : {offsetof(avm_relo_msg_batch, has_msg), offsetof(avm_relo_msg_batch, prev_relo_q), offsetof(avm_relo_state, relocalization_info),
+                   offsetof(avm_relo_state, relo_relative_yaw)})
+    out[n++] = (int)o;
+  return n;
+}
+
 // test hook (not in avm.h): sizeof and the member offsets of avm_align_batch / avm_align_out, for the ctypes mirror check; out: >= 23 ints
 int avm_debug_align_layout(int* out) {
   int n = 0;

@@ -32,9 +32,11 @@ inline void set_ptr(void* s, const Field& f, const void* p) { std::memcpy(static
 // that take a subset of the window tables (U_KEYF: the keyframe decision, U_FAIL: the failure detection; the feature manager's calls -
 // U_TRK: the track tables of a window with its depths and td rows - and the image appended to them -, U_DEPTH: setDepth, U_PUSH: the raw
 // IMU samples, U_SLIDE_TD: the td rows beside U_SLIDE in avm_slide_window_tracks; avm_fsel_select_image_batch - U_SELECT: what travels in,
-// U_SELECT_BACK: what it writes and returns)
+// U_SELECT_BACK: what it writes and returns; the relocalization's calls - U_RELO_SET: avm_set_relo_frame_batch, U_RELO_RESOLVE:
+// avm_relo_resolve_batch, U_RELO_FINISH: avm_relo_finish_batch; U_KEEP: avm_prior_keep_batch)
 enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32, U_KEYF = 64, U_FAIL = 128,
-                  U_TRK = 256, U_DEPTH = 512, U_PUSH = 1024, U_SLIDE_TD = 2048, U_SELECT = 4096, U_SELECT_BACK = 8192 };
+                  U_TRK = 256, U_DEPTH = 512, U_PUSH = 1024, U_SLIDE_TD = 2048, U_SELECT = 4096, U_SELECT_BACK = 8192,
+                  U_RELO_SET = 16384, U_RELO_RESOLVE = 32768, U_RELO_FINISH = 65536, U_KEEP = 131072 };
 constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE | U_SLIDE | U_PROP;
 
 // S: the struct of the member; D, nmember: the struct the dims come from (`d` in `count`) and its batch size (`N` in `count`)
@@ -52,12 +54,12 @@ constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE
 // avm_window_batch.  The four state arrays come first so that the packed path can bring them back with one copy (N_STATES).
 #define WIN(member, type, count, in, out) FIELD(avm_window_batch, avm_window_batch, n_windows, "w_" #member, member, type, count, in, out)
 const Field WINDOW_FIELDS[] = {
-    WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
+    WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN | U_FAIL | U_RELO_SET | U_RELO_FINISH, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
     WIN(speedbias, double, N * 99, U_IMU | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
     WIN(ex_pose, double, N * 7, U_GEOM | U_ALIGN, U_WHOLE | U_SLIDE)
     WIN(inv_depth, double, N * d.max_feat, U_GEOM | U_ALIGN | U_TRK | U_DEPTH, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_TRK | U_DEPTH)
-    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_KEYF | U_TRK | U_DEPTH, U_SLIDE | U_TRK)
-    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_KEYF | U_TRK | U_DEPTH | U_RELO_RESOLVE, U_SLIDE | U_TRK)
+    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK | U_RELO_RESOLVE, U_SLIDE | U_TRK)
     WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
     WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
     WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
@@ -67,13 +69,13 @@ const Field WINDOW_FIELDS[] = {
     WIN(imu_gyr, double, N * 10 * (d.max_samp + 1) * 3, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
     WIN(imu_lin_ba, double, N * 30, U_WHOLE | U_SLIDE, U_SLIDE)
     WIN(imu_lin_bg, double, N * 30, U_WHOLE | U_SLIDE, U_SLIDE)
-    WIN(prior_n, int32_t, N, U_WHOLE, 0)
-    WIN(prior_nblk, int32_t, N, U_WHOLE, 0)
-    WIN(prior_blk_kind, int32_t, N * d.max_pblk, U_WHOLE, 0)
-    WIN(prior_blk_frame, int32_t, N * d.max_pblk, U_WHOLE, 0)
-    WIN(prior_J, double, N * d.max_prior * d.max_prior, U_WHOLE, 0)
-    WIN(prior_r, double, N * d.max_prior, U_WHOLE, 0)
-    WIN(prior_x0, double, N * d.max_pblk * 9, U_WHOLE, 0)
+    WIN(prior_n, int32_t, N, U_WHOLE | U_KEEP, 0)
+    WIN(prior_nblk, int32_t, N, U_WHOLE | U_KEEP, 0)
+    WIN(prior_blk_kind, int32_t, N * d.max_pblk, U_WHOLE | U_KEEP, 0)
+    WIN(prior_blk_frame, int32_t, N * d.max_pblk, U_WHOLE | U_KEEP, 0)
+    WIN(prior_J, double, N * d.max_prior * d.max_prior, U_WHOLE | U_KEEP, 0)
+    WIN(prior_r, double, N * d.max_prior, U_WHOLE | U_KEEP, 0)
+    WIN(prior_x0, double, N * d.max_pblk * 9, U_WHOLE | U_KEEP, 0)
     WIN(obs_vel_td, double, N * d.max_obs * 4, U_WHOLE | U_TRK | U_SLIDE_TD, U_TRK | U_SLIDE_TD)
     WIN(td, double, N, U_WHOLE, U_WHOLE)  // para_Td: in/out
     WIN(relo_n, int32_t, N, U_WHOLE, 0)
@@ -87,8 +89,9 @@ const Field WINDOW_FIELDS[] = {
 constexpr Table WINDOWS = table_of(WINDOW_FIELDS);
 constexpr int N_STATES = 4;  // pose | speedbias | ex_pose | inv_depth
 
-// avm_prior_out of a batch (one device block "po_pack" in host mode: one memset, and for small batches one copy back)
-#define PO(member, type, count) FIELD(avm_prior_out, avm_window_batch, n_windows, "po_" #member, member, type, count, 0, U_WHOLE)
+// avm_prior_out of a batch (one device block "po_pack" in host mode: one memset, and for small batches one copy back); avm_prior_keep_batch
+// rewrites slots of it in place: there it travels both ways
+#define PO(member, type, count) FIELD(avm_prior_out, avm_window_batch, n_windows, "po_" #member, member, type, count, U_KEEP, U_WHOLE | U_KEEP)
 const Field PRIOR_OUT_FIELDS[] = {
     PO(n, int32_t, N) PO(nblk, int32_t, N) PO(blk_kind, int32_t, N * s.max_pblk) PO(blk_frame, int32_t, N * s.max_pblk)
     PO(J, double, N * s.max_prior * s.max_prior) PO(r, double, N * s.max_prior) PO(x0, double, N * s.max_pblk * 9)};
@@ -152,8 +155,31 @@ const Field SELECT_STATE_FIELDS[] = {SS("ss_last", last_feature_id, N) SS("ss_n"
                                      SS("ss_first", first_image, N)};
 #undef SS
 constexpr Table SELECT_STATE = table_of(SELECT_STATE_FIELDS);
+// avm_relo_msg_batch and avm_relo_state (the state's batch size is the windows'); which of the three calls reads / returns a member
+#define RM(member, type, count) FIELD(avm_relo_msg_batch, avm_relo_msg_batch, n_windows, "rm_" #member, member, type, count, U_RELO_SET, 0)
+const Field RELO_MSG_FIELDS[] = {RM(has_msg, int32_t, N) RM(frame_stamp, double, N) RM(n_match, int32_t, N) RM(match_id, int32_t, N * d.max_match)
+                                 RM(match_xy, double, N * d.max_match * 2) RM(prev_relo_t, double, N * 3) RM(prev_relo_q, double, N * 4)};
+#undef RM
+constexpr Table RELO_MSG = table_of(RELO_MSG_FIELDS);
+#define RS(member, type, count, in, out) FIELD(avm_relo_state, avm_window_batch, n_windows, "rs_" #member, member, type, count, in, out)
+constexpr unsigned U_RELO_ALL = U_RELO_SET | U_RELO_RESOLVE | U_RELO_FINISH;
+const Field RELO_STATE_FIELDS[] = {
+    RS(relocalization_info, int32_t, N, U_RELO_ALL, U_RELO_SET | U_RELO_FINISH) RS(relo_frame, int32_t, N, U_RELO_ALL, U_RELO_SET)
+    RS(relo_stamp, double, N, U_RELO_SET, U_RELO_SET) RS(n_match, int32_t, N, U_RELO_SET | U_RELO_RESOLVE, U_RELO_SET)
+    RS(match_id, int32_t, N * s.max_match, U_RELO_SET | U_RELO_RESOLVE, U_RELO_SET)
+    RS(match_xy, double, N * s.max_match * 2, U_RELO_SET | U_RELO_RESOLVE, U_RELO_SET)
+    RS(prev_relo_t, double, N * 3, U_RELO_SET | U_RELO_FINISH, U_RELO_SET) RS(prev_relo_q, double, N * 4, U_RELO_SET | U_RELO_FINISH, U_RELO_SET)
+    RS(relo_pose, double, N * 7, U_RELO_SET | U_RELO_FINISH, U_RELO_SET)
+    RS(drift_correct_yaw, double, N, U_RELO_FINISH, U_RELO_FINISH) RS(drift_correct_t, double, N * 3, U_RELO_FINISH, U_RELO_FINISH)
+    RS(relo_relative_t, double, N * 3, U_RELO_FINISH, U_RELO_FINISH) RS(relo_relative_q, double, N * 4, U_RELO_FINISH, U_RELO_FINISH)
+    RS(relo_relative_yaw, double, N, U_RELO_FINISH, U_RELO_FINISH)};
+#undef RS
+constexpr Table RELO_STATE = table_of(RELO_STATE_FIELDS);
 // (no pointer member the tables lack: the scalar header, then one pointer per field)
 static_assert(sizeof(avm_image_batch) == offsetof(avm_image_batch, n_pts) + IMAGE.n * sizeof(void*), "IMAGE names every array of avm_image_batch");
 static_assert(sizeof(avm_select_state) == offsetof(avm_select_state, last_feature_id) + SELECT_STATE.n * sizeof(void*),
               "SELECT_STATE names every array of avm_select_state");
+static_assert(sizeof(avm_relo_msg_batch) == offsetof(avm_relo_msg_batch, has_msg) + RELO_MSG.n * sizeof(void*), "RELO_MSG names every array of avm_relo_msg_batch");
+static_assert(sizeof(avm_relo_state) == offsetof(avm_relo_state, relocalization_info) + RELO_STATE.n * sizeof(void*),
+              "RELO_STATE names every array of avm_relo_state");
 }  // namespace

@@ -30,6 +30,7 @@ using namespace avm;
 #include "api/solve.hpp"
 #include "api/window_ops.hpp"
 #include "api/tracks.hpp"
+#include "api/relo.hpp"
 #include "api/align.hpp"
 #include "api/fsel.hpp"
 #include "api/debug.hpp"

@@ -325,4 +325,34 @@ hipError_t launch_prior_eig(const avm_prior_out& po, int n_windows, double eps, 
                             int* done /* [n_windows] device scratch, may be null */, hipStream_t stream);
 int window_solve_lds_bytes();
 
+// ---- relocalization and the prior hand-over in the stream loop (relo.hip; the copy-only prior kernel: tracks.hip) ----------------------
+// Every struct holds device pointers.  The checks write first_bad like the feature manager's: min over the failing windows of
+// (window * 8 + rule); they run on their own, before the kernel that writes.
+enum { HDR_BAD_FLAG = 1 };                                                                                             // headers_step
+enum { SETRELO_BAD_NMATCH = 1, SETRELO_BAD_IDS = 2 };                                                                  // set_relo_frame
+enum { RESOLVE_BAD_ROW = 1, RESOLVE_BAD_FRAME = 2, RESOLVE_BAD_NMATCH = 3, RESOLVE_BAD_VIEW_IDS = 4, RESOLVE_BAD_MATCH_IDS = 5 };  // relo_resolve
+enum { FINISH_BAD_FRAME = 1 };                                                                                         // relo_finish
+enum { KEEP_BAD_NBLK = 1, KEEP_CAP = 2 };                                                                              // prior_keep
+struct ReloResolveArgs {
+  avm_window_batch view;  // n_feat, feat_start are read (validated: CHK_TRACKS)
+  const int32_t *feat_id, *view_row;
+  int full_max_feat;
+  avm_relo_state state;
+  int32_t *relo_n, *relo_frame, *relo_feat;
+  double* relo_xy;
+  int32_t* n_active;  // one int, zero on entry: counts the windows with relocalization_info != 0
+};
+hipError_t launch_headers_step_check(int n_windows, const int32_t* flags, int* first_bad, hipStream_t stream);
+hipError_t launch_headers_step(int n_windows, double* stamp, const int32_t* flags, const double* new_stamp, hipStream_t stream);
+hipError_t launch_set_relo_frame_check(const avm_relo_msg_batch& msg, int* first_bad, hipStream_t stream);
+hipError_t launch_set_relo_frame(const avm_window_batch& b, const double* stamp, const avm_relo_msg_batch& msg, const avm_relo_state& state,
+                                 hipStream_t stream);
+hipError_t launch_relo_resolve_check(const ReloResolveArgs& a, int* first_bad, hipStream_t stream);
+hipError_t launch_relo_resolve(const ReloResolveArgs& a, hipStream_t stream);
+hipError_t launch_relo_finish_check(int n_windows, const avm_relo_state& state, int* first_bad, hipStream_t stream);
+hipError_t launch_relo_finish(const avm_window_batch& b, const avm_relo_state& state, hipStream_t stream);
+// b's prior tables have passed CHK_PRIOR
+hipError_t launch_prior_keep_check(const avm_window_batch& b, const avm_prior_out& po, int* first_bad, hipStream_t stream);
+hipError_t launch_prior_keep(const avm_window_batch& b, const avm_prior_out& po, hipStream_t stream);
+
 }  // namespace avm

@@ -2,20 +2,19 @@
 // device-resident tables"): FeatureManager::addFeatureCheckParallax's append by feature id (feature_manager.cpp:45-72), the buffer half of
 // Estimator::processIMU (estimator.cpp:92-98), the solve's filtered view of the whole list (estimator.cpp:715) and setDepth's copy back
 // (feature_manager.cpp:141-159); and FeatureSelector::select()'s bookkeeping around the selection on the tracker's image
-// (feature_selector.cpp:98-120, 156-196, 208-219; select_image.hpp).  Integer bookkeeping and copies only: no floating-point operation in this file.
+// (feature_selector.cpp:98-120, 156-196, 208-219; select_image.hpp); and the prior a window keeps when its marginalization dropped nothing
+// (estimator.cpp:926-927; avm_prior_keep_batch).  Integer bookkeeping and copies only: no floating-point operation in this file.
 // One 256-thread workgroup per window in the kernels that walk a list; every call has a check kernel of the same shape that runs first,
 // on its own, and writes nothing but the verdict (kernels.hpp), so that a refused batch leaves every table of every window as it was.
 #include "devmath.hpp"
 #include "kernels.hpp"
 #include "select_image.hpp"
+#include "track_prims.hpp"  // TRK_NT, block_compact, find_id, report
 
 namespace avm {
 namespace {
 
-constexpr int TRK_NT = 256;
-constexpr int TRK_WAVES = TRK_NT / 64;
 constexpr int TRK_SLOTS = (AVM_MAX_OBS_WIDE + TRK_NT - 1) / TRK_NT;  // 17 observation slots per thread
-constexpr int TRK_MAX_CHUNKS = AVM_MAX_IMAGE_PTS / 64;               // 16 (the rows of a window: 6)
 static_assert(AVM_MAX_IMAGE_PTS % 64 == 0 && AVM_MAX_FEAT_WIDE <= AVM_MAX_IMAGE_PTS, "chunk totals are sized by the image");
 
 // inclusive prefix sum over the wavefront, every lane active: the shift ladder of wave_sum_shr with each lane keeping its partial sum
@@ -48,42 +47,6 @@ AVM_DEV void block_scan_excl(const int* in, int* out, int n, int* tot) {
   __syncthreads();
 }
 
-// The items i < n with pred(i), ranked in index order: emit(i, rank) for each, the count returned to every thread.  Ballot / popcount per
-// 64-item chunk, the chunk totals through `tot` (TRK_MAX_CHUNKS ints of LDS).  pred is evaluated twice; ends with a workgroup barrier.
-template <class Pred, class Emit>
-AVM_DEV int block_compact(int n, int* tot, Pred pred, Emit emit) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int c = wave; c * 64 < n; c += TRK_WAVES) {
-    const int i = c * 64 + lane;
-    const unsigned long long m = __ballot(i < n && pred(i));
-    if (lane == 0) tot[c] = __popcll(m);
-  }
-  __syncthreads();
-  int total = 0;
-  for (int c = 0; c * 64 < n; c++) total += tot[c];
-  for (int c = wave; c * 64 < n; c += TRK_WAVES) {
-    const int i = c * 64 + lane;
-    const bool f = i < n && pred(i);
-    const unsigned long long m = __ballot(f);
-    int base = 0;
-    for (int k = 0; k < c; k++) base += tot[k];
-    if (f) emit(i, base + __popcll(m & ((1ull << lane) - 1ull)));
-  }
-  __syncthreads();
-  return total;
-}
-
-// position of `id` in the ascending ids[0 .. n), or -1 (memory-safe on any input)
-AVM_DEV int find_id(const int* ids, int n, int id) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (ids[mid] < id) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < n && ids[lo] == id) ? lo : -1;
-}
-
 // the row e < n_rows with begin[e] <= d < begin[e + 1] (begin strictly ascending from 0: every row has an observation)
 AVM_DEV int row_of_slot(const int* begin, int n_rows, int d) {
   int lo = 0, hi = n_rows;
@@ -104,8 +67,6 @@ AVM_DEV void sources_read_barrier() {
   __builtin_amdgcn_s_waitcnt(0x0F70);
   __syncthreads();
 }
-
-AVM_DEV void report(int* first_bad, int w, int rule) { atomicMin(first_bad, w * 8 + rule); }
 
 // ---- avm_add_image_batch ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TRK_NT) void add_image_check_kernel(avm_window_batch B, const int32_t* feat_id, avm_image_batch I, int* first_bad) {
@@ -326,6 +287,34 @@ __global__ __launch_bounds__(TRK_NT) void store_depths_kernel(avm_window_batch F
   const int nv = V.n_feat[w];
   for (int k = threadIdx.x; k < nv; k += TRK_NT)
     F.inv_depth[(size_t)w * F.max_feat + view_row[(size_t)w * V.max_feat + k]] = V.inv_depth[(size_t)w * V.max_feat + k];
+}
+
+// ---- avm_prior_keep_batch ---------------------------------------------------------------------------------------------------------------
+// estimator.cpp:926-927: a window whose marginalization reported n < 0 keeps the prior it was solved with (B's prior tables: CHK_PRIOR passed)
+__global__ __launch_bounds__(64) void prior_keep_check_kernel(avm_window_batch B, avm_prior_out P, int* first_bad) {
+  const int w = blockIdx.x * 64 + threadIdx.x;
+  if (w >= B.n_windows || P.n[w] >= 0) return;
+  const int n = B.prior_n[w], nb = B.prior_nblk[w];
+  if (nb < 0 || nb > B.max_pblk) report(first_bad, w, KEEP_BAD_NBLK);
+  else if (n > P.max_prior || nb > P.max_pblk) report(first_bad, w, KEEP_CAP);
+}
+
+__global__ __launch_bounds__(TRK_NT) void prior_keep_kernel(avm_window_batch B, avm_prior_out P) {
+  const int w = blockIdx.x, tid = threadIdx.x;
+  if (P.n[w] >= 0) return;  // (uniform; thread 0 writes P.n behind the barrier, after every thread has read it)
+  const int n = B.prior_n[w], nb = B.prior_nblk[w];
+  const size_t bs = B.max_prior, ps = P.max_prior;
+  const double* J = B.prior_J + (size_t)w * bs * bs;
+  double* Jo = P.J + (size_t)w * ps * ps;
+  for (int k = tid; k < n * n; k += TRK_NT) Jo[(size_t)(k / n) * ps + k % n] = J[(size_t)(k / n) * bs + k % n];
+  for (int k = tid; k < n; k += TRK_NT) P.r[(size_t)w * ps + k] = B.prior_r[(size_t)w * bs + k];
+  for (int k = tid; k < nb; k += TRK_NT) {
+    P.blk_kind[(size_t)w * P.max_pblk + k] = B.prior_blk_kind[(size_t)w * B.max_pblk + k];
+    P.blk_frame[(size_t)w * P.max_pblk + k] = B.prior_blk_frame[(size_t)w * B.max_pblk + k];
+  }
+  for (int k = tid; k < nb * 9; k += TRK_NT) P.x0[(size_t)w * P.max_pblk * 9 + k] = B.prior_x0[(size_t)w * B.max_pblk * 9 + k];
+  __syncthreads();
+  if (tid == 0) P.n[w] = n, P.nblk[w] = nb;
 }
 
 // ---- avm_fsel_select_image_batch -----------------------------------------------------------------------------------------------------
@@ -560,6 +549,16 @@ hipError_t launch_store_depths_check(const avm_window_batch& full, const avm_win
 
 hipError_t launch_store_depths(const avm_window_batch& full, const avm_window_batch& view, const int32_t* view_row, hipStream_t stream) {
   hipLaunchKernelGGL(store_depths_kernel, dim3(full.n_windows), dim3(TRK_NT), 0, stream, full, view, view_row);
+  return hipGetLastError();
+}
+
+hipError_t launch_prior_keep_check(const avm_window_batch& b, const avm_prior_out& po, int* first_bad, hipStream_t stream) {
+  hipLaunchKernelGGL(prior_keep_check_kernel, dim3((b.n_windows + 63) / 64), dim3(64), 0, stream, b, po, first_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_prior_keep(const avm_window_batch& b, const avm_prior_out& po, hipStream_t stream) {
+  hipLaunchKernelGGL(prior_keep_kernel, dim3(b.n_windows), dim3(TRK_NT), 0, stream, b, po);
   return hipGetLastError();
 }
 

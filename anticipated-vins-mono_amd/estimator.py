@@ -50,7 +50,10 @@ class Estimator:
             self.ctx.check(rc, "avm_window_solve_batch_flags")
         self.last_summary = summ
         if prior is not None and (marginalization_flags is not None or self.options.marginalization_flag == abi.MARGIN_SECOND_NEW):
-            self._keep_old_prior_where_nothing_was_dropped(prior, windows)
+            if windows.on_device and prior.on_device:
+                self.keep_prior(windows, prior)      # (one kernel: no table crosses to the host)
+            else:
+                self._keep_old_prior_where_nothing_was_dropped(prior, windows)
         self.last_marginalization_info = prior
         return summ
 
@@ -127,6 +130,63 @@ class Estimator:
             pa["J"][i, :mp, :mp] = wa["prior_J"][i, :mp, :mp]
             pa["r"][i, :mp] = wa["prior_r"][i, :mp]
             pa["x0"][i, :mb] = wa["prior_x0"][i, :mb]
+
+    def keep_prior(self, windows: buffers.WindowArrays, prior: buffers.PriorOutArrays):
+        """estimator.cpp:926-927 on the slots: every window that reported n < 0 gets the used part of the prior it was solved with (the
+        batch's prior_* tables), in place.  Afterwards `prior` can always be chained: TrackTables.swap_prior(prior) is the hand-over."""
+        assert prior.on_device == windows.on_device
+        s, po = windows.struct(), prior.struct()
+        self.ctx.check(self.ctx._L.avm_prior_keep_batch(self.ctx.h, windows.mem, C.byref(s), C.byref(po)), "avm_prior_keep_batch")
+
+    def headers_step(self, windows: buffers.WindowArrays, stamp, marginalization_flags=None, new_stamp=None):
+        """The frame stamps Headers[i].stamp of B streams, stamp [B, 11] where the windows live, in place: slideWindow's moves for the
+        flags (estimator.cpp:1015,1021,1064) - call it behind the roll -, then Headers[10] = new_stamp (:126) - on the next image."""
+        B = windows.n_windows
+        assert tuple(stamp.shape) == (B, abi.NFRAMES)
+        flags = None if marginalization_flags is None else self._flags_like(windows, marginalization_flags)
+        new = None if new_stamp is None else self._like(windows, new_stamp, np.float64)
+        assert new is None or tuple(new.shape) == (B,)
+        rc = self.ctx._L.avm_headers_step_batch(self.ctx.h, windows.mem, B, abi.dptr(stamp), abi.iptr(flags), abi.dptr(new))
+        self.ctx.check(rc, "avm_headers_step_batch")
+
+    # the reference's name
+    def setReloFrame(self, windows: buffers.WindowArrays, stamp, msg: buffers.ReloMsgArrays, state: buffers.ReloState):
+        """Estimator::setReloFrame (estimator.cpp:1109-1127) for every stream with a message: the message goes into `state`; a frame
+        0 .. WINDOW_SIZE - 1 whose stamp equals frame_stamp (the last one) makes the relocalization pending, relo_pose = its pose."""
+        assert msg.on_device == windows.on_device == state.on_device and tuple(stamp.shape) == (windows.n_windows, abi.NFRAMES)
+        s, sm, ss = windows.struct(), msg.struct(), state.struct()
+        rc = self.ctx._L.avm_set_relo_frame_batch(self.ctx.h, windows.mem, C.byref(s), abi.dptr(stamp), C.byref(sm), C.byref(ss))
+        self.ctx.check(rc, "avm_set_relo_frame_batch")
+
+    def resolve_relo(self, tables: buffers.TrackTables, state: buffers.ReloState) -> int:
+        """The match loop of optimization() (estimator.cpp:765-790) on tables.view (behind solve_view()): with a relocalization pending
+        in some window, tables.view gets relo_n / relo_frame / relo_feat / relo_xy and relo_pose (state's own array: the solve returns the
+        loop frame's pose into it), and optimization() takes the extended kernel; with none they are removed.  Returns the number of
+        windows with a relocalization pending."""
+        v = tables.view
+        B, mf = v.n_windows, v.dims["max_feat"]
+        out = getattr(tables, "_relo_out", None)
+        if out is None:
+            out = tables._relo_out = {"relo_n": self._out_like(v, (B,), np.int32), "relo_frame": self._out_like(v, (B,), np.int32),
+                                      "relo_feat": self._out_like(v, (B, mf), np.int32), "relo_xy": self._out_like(v, (B, mf, 2), np.float64)}
+        n_active = C.c_int32(0)
+        s, ss = v.struct(), state.struct()
+        rc = self.ctx._L.avm_relo_resolve_batch(self.ctx.h, v.mem, C.byref(s), abi.iptr(tables.feat_id), int(tables.full.dims["max_feat"]),
+                                                abi.iptr(tables.view_row), C.byref(ss), abi.iptr(out["relo_n"]), abi.iptr(out["relo_frame"]),
+                                                abi.iptr(out["relo_feat"]), abi.dptr(out["relo_xy"]), C.byref(n_active))
+        self.ctx.check(rc, "avm_relo_resolve_batch")
+        for k in ("relo_n", "relo_frame", "relo_feat", "relo_xy", "relo_pose"):
+            v.a.pop(k, None)
+        if n_active.value > 0:
+            v.a.update(out)
+            v.a["relo_pose"] = state.a["relo_pose"]
+        return int(n_active.value)
+
+    def relo_finish(self, windows: buffers.WindowArrays, state: buffers.ReloState):
+        """The outputs of double2vector() (estimator.cpp:588-604) behind optimization(): drift_correct_yaw / _t and relo_relative_t / _q /
+        _yaw of every window with a relocalization pending, whose relocalization_info then returns to 0."""
+        s, ss = windows.struct(), state.struct()
+        self.ctx.check(self.ctx._L.avm_relo_finish_batch(self.ctx.h, windows.mem, C.byref(s), C.byref(ss)), "avm_relo_finish_batch")
 
     # the reference's name
     def visualInitialAlign(self, align: buffers.AlignArrays, windows: buffers.WindowArrays = None, out: buffers.AlignOutArrays = None):

@@ -77,9 +77,10 @@ def lib():
         L.avm_visual_initial_align_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.AlignBatch), C.POINTER(abi.WindowBatch),
                                                      C.POINTER(abi.AlignOut)]
         L.avm_debug_align_layout.argtypes = [C.POINTER(C.c_int)]
-        for name, argtypes in list(abi.PROTOTYPES.items()) + list(abi.TRACK_PROTOTYPES.items()) + list(abi.SELECT_PROTOTYPES.items()):
+        for name, argtypes in list(abi.PROTOTYPES.items()) + list(abi.TRACK_PROTOTYPES.items()) + list(abi.SELECT_PROTOTYPES.items()) + list(abi.RELO_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.avm_debug_track_struct_sizes.argtypes = [C.POINTER(C.c_int)]
+        L.avm_debug_relo_struct_sizes.argtypes = [C.POINTER(C.c_int)]
         L.avm_comm_unique_id.argtypes = [vp, C.c_void_p]
         L.avm_comm_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_void_p]
         L.avm_gather_states.argtypes = [vp, abi.c_dp, abi.c_dp, C.c_size_t]
@@ -106,6 +107,7 @@ EXPORTS = [
     "avm_window_solve_batch_flags", "avm_slide_window_flags", "avm_keyframe_decision_batch", "avm_failure_detection_batch",
     "avm_add_image_batch", "avm_imu_push_batch", "avm_solve_view_batch", "avm_solve_view_store_depths", "avm_slide_window_tracks",
     "avm_fsel_select_image_batch",
+    "avm_headers_step_batch", "avm_set_relo_frame_batch", "avm_relo_resolve_batch", "avm_relo_finish_batch", "avm_prior_keep_batch",
 ]
 
 

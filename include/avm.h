@@ -195,7 +195,8 @@ typedef struct avm_window_batch {
   double* td;                    /* [B] in/out */
   /* relocalization (estimator.cpp:760-792, 588-604): these five arrays present <=> relocalization_info.  The loop over
    * f_manager.feature / match_points (ids ascending) is resolved by the host into feature INDICES of this batch
-   * (ascending, only features with start_frame <= relo_frame_local_index).  relo_n[w] == 0 (no feature matched): no factor
+   * (ascending, only features with start_frame <= relo_frame_local_index) - or, for device-resident tables, by
+   * avm_relo_resolve_batch below.  relo_n[w] == 0 (no feature matched): no factor
    * references relo_Pose and the solve leaves it alone, but it still comes back through double2vector's gauge fix
    * (relo_t / relo_r of :590-596), as in the reference; a window without relocalization simply ignores its relo_pose. */
   const int32_t* relo_n;         /* [B] number of matched features */
@@ -598,6 +599,96 @@ typedef struct avm_select_state {  /* the members of FeatureSelector that outliv
 int avm_fsel_select_image_batch(avm_ctx* ctx, avm_mem mem, const avm_image_batch* image, const double* prob /* [B][image->max_pts] */,
                                 const int32_t* initialized /* [B], nullable */, int32_t init_thresh, int32_t prune_lost,
                                 avm_select_state* state, avm_fsel_batch* problem, avm_fsel_out* out, avm_image_batch* image_out);
+
+/* ---- relocalization and the prior hand-over in the stream loop: what a batch of streams left to the host besides the initialisation ----
+ * Everything below is in `mem` space and all or nothing, like the feature manager's calls: a check kernel runs first, and on
+ * AVM_ERR_INVALID / AVM_ERR_CAPACITY the message names the first offending window and nothing has been written.  n_windows == 0: AVM_OK.
+ * avm_last_kernel_ms keys: "headers_step", "set_relo", "relo_resolve", "relo_finish", "prior_keep".
+ *
+ * The frame stamps, Headers[i].stamp.toSec(), are a table BESIDE the batch like feat_id: stamp [B][11].  Step one, if
+ * marginalization_flags is given: slideWindow's moves per window - AVM_MARGIN_OLD: Headers[i] = Headers[i + 1] for i < 10, then
+ * Headers[10] = Headers[9] (estimator.cpp:1015,1021); AVM_MARGIN_SECOND_NEW: Headers[9] = Headers[10] (:1064); any other value is
+ * AVM_ERR_INVALID.  Step two, if new_stamp is given: Headers[10] = new_stamp (:126).  A caller calls it behind the roll with the flags and
+ * on the next image's arrival with new_stamp. */
+int avm_headers_step_batch(avm_ctx* ctx, avm_mem mem, int32_t n_windows, double* stamp /* [B][11] in/out */,
+                           const int32_t* marginalization_flags /* [B], nullable */, const double* new_stamp /* [B], nullable */);
+
+typedef struct avm_relo_msg_batch {   /* the message of estimator_node.cpp:274-297, one row per stream */
+  int32_t n_windows, max_match;       /* max_match <= AVM_MAX_IMAGE_PTS */
+  const int32_t* has_msg;             /* [B] 0: no message for this stream, its row is not read */
+  const double*  frame_stamp;         /* [B] */
+  const int32_t* n_match;             /* [B] */
+  const int32_t* match_id;            /* [B][max_match] (int)match_points[k].z(), strictly ascending */
+  const double*  match_xy;            /* [B][max_match][2] */
+  const double*  prev_relo_t;         /* [B][3] */
+  const double*  prev_relo_q;         /* [B][4] x y z w */
+} avm_relo_msg_batch;
+
+typedef struct avm_relo_state {       /* the Estimator members that outlive the call; in/out, `mem` space */
+  int32_t max_match;                  /* <= AVM_MAX_IMAGE_PTS */
+  int32_t* relocalization_info;       /* [B] */
+  int32_t* relo_frame;                /* [B] relo_frame_local_index */
+  double*  relo_stamp;                /* [B] */
+  int32_t* n_match;                   /* [B]               match_points.size() */
+  int32_t* match_id;                  /* [B][max_match] */
+  double*  match_xy;                  /* [B][max_match][2] */
+  double*  prev_relo_t;               /* [B][3] */
+  double*  prev_relo_q;               /* [B][4] x y z w */
+  double*  relo_pose;                 /* [B][7]; the caller initialises rows to a finite pose (0 0 0 0 0 0 1) */
+  double*  drift_correct_yaw;         /* [B]    outputs of :597-603, written by avm_relo_finish_batch only */
+  double*  drift_correct_t;           /* [B][3] */
+  double*  relo_relative_t;           /* [B][3] */
+  double*  relo_relative_q;           /* [B][4] x y z w */
+  double*  relo_relative_yaw;         /* [B] */
+} avm_relo_state;
+
+/* Estimator::setReloFrame (estimator.cpp:1109-1127) per window with has_msg != 0: frame_stamp, the first n_match matches and prev_relo_*
+ * are copied into the state whether or not a frame matches (:1111-1116; match slots beyond n_match keep what they held); then for
+ * i = 0 .. WINDOW_SIZE - 1 in order, stamp[w][i] == frame_stamp sets relo_frame = i, relocalization_info = 1 and relo_pose = pose[w][i] -
+ * frame 10 is not searched and the last match wins, as the loop without a break does.  Windows without a message are untouched.
+ * DEVIATION: the reference copies para_Pose[i], which at that point still holds what the PREVIOUS optimization's Ceres run left - before
+ * the gauge fix and before the roll.  The tables have Ps / Rs only, so relo_pose starts from the current pose of frame i.  It is the start
+ * value of a free variable of the solve; only with zero matched features does it reach the outputs unchanged.
+ * AVM_ERR_INVALID: n_match outside [0, max_match]; ids not strictly ascending; msg->n_windows != windows->n_windows.
+ * AVM_ERR_CAPACITY: state->max_match < msg->max_match; max_match > AVM_MAX_IMAGE_PTS. */
+int avm_set_relo_frame_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* windows /* pose is read */, const double* stamp /* [B][11] */,
+                             const avm_relo_msg_batch* msg, avm_relo_state* state);
+
+/* The match loop of optimization() (estimator.cpp:765-790) on the solve's view.  For a window with relocalization_info != 0: the view rows
+ * k in order with feat_start[k] <= relo_frame, their id feat_id[view_row[k]]; for every such id that also occurs in match_id[0 .. n_match),
+ * in ascending order, the next slot gets relo_feat = k and relo_xy = match_xy of that match.  relo_n is the count, relo_frame the
+ * state's; slots at and beyond relo_n keep what they held.  A window with relocalization_info == 0 gets relo_n = 0 and relo_frame = 0.
+ * *n_active (a host int, nullable) is the number of windows with relocalization_info != 0: the caller passes the four arrays and
+ * state->relo_pose to the solve as the five optional members of avm_window_batch - and so takes the extended kernel - only when it is > 0.
+ * DEVIATIONS: both id sequences must ascend (the reference's two-pointer loop presumes it; a tracker's ids do).  The reference advances
+ * retrive_feature_index without a bound and reads past match_points when a list id exceeds every match id; here the matches simply end.
+ * AVM_ERR_INVALID: view_row not strictly increasing inside [0, full_max_feat); on a window with relocalization_info != 0: relo_frame
+ * outside [0, WINDOW_SIZE), n_match outside [0, state->max_match], the view rows' ids or the match ids not strictly ascending.
+ * AVM_ERR_CAPACITY: view->max_feat > AVM_MAX_FEAT; state->max_match > AVM_MAX_IMAGE_PTS. */
+int avm_relo_resolve_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* view, const int32_t* feat_id /* [B][full_max_feat] */,
+                           int32_t full_max_feat, const int32_t* view_row /* [B][view->max_feat] */, const avm_relo_state* state,
+                           int32_t* relo_n /* [B] */, int32_t* relo_frame /* [B] */, int32_t* relo_feat /* [B][view->max_feat] */,
+                           double* relo_xy /* [B][view->max_feat][2] */, int32_t* n_active /* host int, nullable */);
+
+/* The outputs of double2vector() (estimator.cpp:588-604) for every window with relocalization_info != 0.  With relo_t | relo_r =
+ * state->relo_pose as the solve returned it (after the gauge fix; the quaternion normalised as on :593), Ps | Rs = pose[w][relo_frame]
+ * (the quaternion normalised as on :551) and prev_relo_r = prev_relo_q.toRotationMatrix():
+ *   drift_correct_yaw = yaw(prev_relo_r) - yaw(relo_r)   in degrees
+ *   drift_correct_t   = prev_relo_t - Rz(drift_correct_yaw) relo_t
+ *   relo_relative_t   = relo_r^T (Ps - relo_t)
+ *   relo_relative_q   = the quaternion of relo_r^T Rs
+ *   relo_relative_yaw = normalizeAngle(yaw(Rs) - yaw(relo_r))
+ * with R2ypr / ypr2R / normalizeAngle of utility.h:66-108,130-139; then relocalization_info = 0.  The other windows keep all five outputs.
+ * Non-finite input gives non-finite output for that window only.  AVM_ERR_INVALID: relo_frame outside [0, WINDOW_SIZE) on such a window. */
+int avm_relo_finish_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* windows /* pose AFTER the solve */, avm_relo_state* state);
+
+/* The prior hand-over (estimator.cpp:926-927).  The solve reports prior->n[w] < 0 for a window whose prior it left alone (MARGIN_NONE, or
+ * MARGIN_SECOND_NEW with nothing to drop).  For every such window the slot becomes the prior the window was solved with, windows->prior_*:
+ * n, nblk, the first nblk rows of blk_kind / blk_frame / x0, the leading n x n of J and n of r, each table with its own stride.  Windows
+ * with n >= 0 and everything outside the used parts are untouched.  Afterwards `prior` is always chainable: with equal strides the caller
+ * exchanges its seven pointers with the batch's prior_*, and that exchange is the whole hand-over.
+ * AVM_ERR_INVALID: the window's own prior tables are inconsistent.  AVM_ERR_CAPACITY: a kept prior does not fit prior->max_prior / max_pblk. */
+int avm_prior_keep_batch(avm_ctx* ctx, avm_mem mem, const avm_window_batch* windows, avm_prior_out* prior);
 
 /* ---- Estimator::visualInitialAlign (estimator.cpp:355-431) with VisualIMUAlignment (initial/initial_aligment.cpp): the step that
  * moves solver_flag from INITIAL to NON_LINEAR.  It starts from the up-to-scale camera trajectory of initialStructure (relativePose,
