@@ -330,6 +330,13 @@ RELO_PROTOTYPES = {
     "avm_prior_keep_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(PriorOut)],
 }
 
+# The solve of a batch of which some streams relocalize (include/avm.h): the _flags call with relo_active behind the flags.  A dict of its
+# own, like the others.
+SPLIT_PROTOTYPES = {
+    "avm_window_solve_batch_relo": [C.c_void_p, C.POINTER(Options), C.c_int, C.POINTER(WindowBatch), c_ip, c_ip, C.POINTER(PriorOut),
+                                    C.POINTER(SolveSummary)],
+}
+
 
 def default_options() -> Options:
     """Values the reference runs with (estimator.cpp:794-806, euroc_config.yaml:54-63) + Ceres defaults.

@@ -28,6 +28,8 @@ struct avm_ctx {
   int last_marg_windows = 0;  // batch size of the last marginalization (its per-window "the one-wavefront kernel finished it" flags: pool "pe_done")
   bool last_solve_tp = false;  // which form of the solve kernel the last avm_window_solve_batch took (avm_debug_last_solve_form)
   bool last_marg_tp = false;   // ... and which form of the marginalization kernel (avm_debug_last_marg_form)
+  // avm_debug_last_split: windows the last solve took as plain / as extended, the plain ones' form (0 latency, 1 throughput, -1 none), 1: the list builds ran
+  int64_t last_split[4] = {0, 0, -1, 0};
   int scratch_slots = 0;  // slots allocated (n_slots, or 2 n_slots once a batch has taken the throughput form of the solve)
   double *pre_delta = nullptr, *pre_jac = nullptr, *pre_cov = nullptr, *pre_sqrt = nullptr, *pre_sum = nullptr;
   size_t pre_cap = 0;  // windows

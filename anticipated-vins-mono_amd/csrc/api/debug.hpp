@@ -16,6 +16,13 @@ int avm_debug_copy_profile(avm_ctx* c, long long* host_out) {
 int avm_debug_last_solve_form(const avm_ctx* c) { return c ? (c->last_solve_tp ? 1 : 0) : -1; }
 // ... 1 when its marginalization ran the throughput form (marginalize_tp_kernel: two 256-thread workgroups per CU)
 int avm_debug_last_marg_form(const avm_ctx* c) { return c ? (c->last_marg_tp ? 1 : 0) : -1; }
+// ... how it split the batch (avm_window_solve_batch_relo): out[0] = windows solved as plain ones, out[1] = windows that took the extended kernel,
+// out[2] = the plain ones' form (0 latency, 1 throughput, -1 there were none), out[3] = 1 when the list builds of the kernels ran
+int avm_debug_last_split(const avm_ctx* c, int64_t* out) {
+  if (!c || !out) return AVM_ERR_INVALID;
+  for (int k = 0; k < 4; k++) out[k] = c->last_split[k];
+  return AVM_OK;
+}
 // ... and which form the last avm_fsel_select_batch STARTED in: 3 = one workgroup per frame with lazy evaluation (fsel_solo_kernel), 2 / 1 = the
 // frame kernel's teams, 0 = one launch per greedy round
 int avm_debug_last_fsel_form(const avm_ctx* c) { return c ? c->last_fsel_mode : -1; }
@@ -24,6 +31,12 @@ int avm_debug_last_fsel_form(const avm_ctx* c) { return c ? c->last_fsel_mode : 
 int avm_debug_solve_tp_occupancy(int* out) {
   out[0] = window_solve_tp_occupancy(), out[1] = window_solve_tp_lds_bytes();
   return 2;
+}
+
+// ... and of its build over a window list (window_solve_tp_list_kernel): out[0] = workgroups per CU
+int avm_debug_solve_tp_list_occupancy(int* out) {
+  out[0] = window_solve_tp_list_occupancy();
+  return 1;
 }
 
 // test hook (not in avm.h): the compile-time tables of the throughput solve's sparse factorization (solve/chol_regs_tables.hpp; exported by solve/chol_regs.hpp); out: >= 512 ints

@@ -66,6 +66,30 @@ int run_solve(avm_ctx* c, SolveArgs& sa, bool extended, const SolveForms& forms)
   return AVM_OK;
 }
 
+// avm_window_solve_batch_relo's solve when a batch has windows of both kinds: the plain list in its form (forms.tp), then the extended
+// list, one after the other on the ctx stream - they share the scratch slots.  lists: [2 B] device, the plain windows from 0 and the
+// extended ones from B (solve_partition_kernel's layout); n_ext of them extended.  lists == null: every window through the extended list
+// build in batch order (estimate_extrinsic / estimate_td: relo_active then only decides which windows have a relocalization frame).
+int run_solve_split(avm_ctx* c, SolveArgs& sa, const SolveForms& forms, const int32_t* lists, int n_ext, const int32_t* relo_active) {
+  if (c->prof) HIPCHK(c, hipMemsetAsync(c->prof, 0, sizeof(long long) * PROF_SLOTS * 2 * c->n_slots, c->stream));
+  const int B = sa.b.n_windows;
+  SolveListArgs la;
+  static_cast<SolveArgs&>(la) = sa;
+  la.relo_active = relo_active;
+  if (lists) {
+    la.win_list = lists, la.n_list = B - n_ext;
+    la.n_slots = forms.tp ? 2 * c->n_slots : c->n_slots;
+    HIPCHK(c, forms.tp ? launch_window_solve_tp_list(la, c->stream) : launch_window_solve_list(la, c->stream));
+  }
+  la.win_list = lists ? lists + B : nullptr, la.n_list = lists ? n_ext : B;
+  la.n_slots = c->n_slots;
+  HIPCHK(c, launch_window_solve_x_list(la, c->stream));
+  sa.n_slots = forms.marg_tp ? 2 * c->n_slots : c->n_slots;
+  c->last_solve_tp = lists && forms.tp;
+  c->last_marg_tp = false;
+  return AVM_OK;
+}
+
 // Marginalization and the square root of the new prior, into prior_out (host mode: into the ctx's block, and the copy back enqueued).
 // *marg_err: the device flag the kernel raises when a window's kept set does not fit (prior_out->max_prior / max_pblk, or the 76 rows /
 // 16 blocks the eigen-solver holds): the call then fails with AVM_ERR_CAPACITY instead of returning a truncated prior.
@@ -118,9 +142,19 @@ int avm_window_solve_batch(avm_ctx* c, const avm_options* opt, avm_mem mem, cons
 
 int avm_window_solve_batch_flags(avm_ctx* c, const avm_options* opt, avm_mem mem, const avm_window_batch* batch, const int32_t* flags,
                                  avm_prior_out* prior_out, avm_solve_summary* summary) {
+  return avm_window_solve_batch_relo(c, opt, mem, batch, flags, nullptr, prior_out, summary);
+}
+
+// relo_active == null: the call avm_window_solve_batch_flags always was.  With it, the batch is split (include/avm.h has the contract):
+// the windows without a pending relocalization take the kernel form the batch would get without the relocalization arrays, the others
+// the extended kernel, both through the list builds of the kernels; the marginalization runs once on the whole batch.
+int avm_window_solve_batch_relo(avm_ctx* c, const avm_options* opt, avm_mem mem, const avm_window_batch* batch, const int32_t* flags,
+                                const int32_t* relo_active, avm_prior_out* prior_out, avm_solve_summary* summary) {
   if (!enter(c)) return AVM_ERR_INVALID;
   int rc = check_window_batch(c, opt, batch);
   if (rc != AVM_OK) return rc;
+  if (relo_active && (!batch->relo_n || !batch->relo_frame))
+    return fail(c, AVM_ERR_INVALID, "relo_active is given but relo_n / relo_frame / relo_feat / relo_xy / relo_pose of the batch is NULL");
   // (with per-window flags the forms and the buffers are chosen as for a marginalizing batch: which values occur is known after the check)
   bool marg = flags || opt->marginalization_flag != AVM_MARGIN_NONE;
   if (marg && (rc = check_prior_out(c, prior_out)) != AVM_OK) return rc;
@@ -132,13 +166,61 @@ int avm_window_solve_batch_flags(avm_ctx* c, const avm_options* opt, avm_mem mem
   unsigned flags_seen = 0;
   FlagCheck check;
   const FlagRule fr{flags, (1u << AVM_MARGIN_OLD) | (1u << AVM_MARGIN_SECOND_NEW) | (1u << AVM_MARGIN_NONE)};
-  rc = mem == AVM_MEM_HOST ? validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &tp_misfit, fr, SOLVE_FLAG_RULES, &flags_seen)
-                           : validate_windows_begin(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &check, fr);
+  // relo_active: the two lists of windows.  Host memory: built here and staged; device memory: by a kernel that runs in the table check's
+  // pass, the number of extended windows travels back as the verdict's fourth word (no wait of its own).  With estimate_extrinsic /
+  // estimate_td every window is an extended one: no lists, relo_active goes to the kernel as it is.
+  const bool est_x = opt->estimate_extrinsic != 0 || opt->estimate_td != 0;
+  const bool split = relo_active != nullptr && !est_x;
+  const int B = batch->n_windows;
+  const int32_t *d_lists = nullptr, *d_active = relo_active;
+  int n_ext = 0;
+  std::vector<int32_t> h_lists;  // (alive until the call's synchronize)
+  if (mem == AVM_MEM_HOST) {
+    rc = validate_windows(c, mem, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &tp_misfit, fr, SOLVE_FLAG_RULES, &flags_seen);
+    if (rc == AVM_OK && split) {
+      h_lists.resize(2 * (size_t)B);
+      int n_plain = 0;
+      for (int w = 0; w < B; w++) {
+        if (relo_active[w]) h_lists[(size_t)B + n_ext++] = w;
+        else h_lists[n_plain++] = w;
+      }
+      const void* dl;
+      if ((rc = stage_array(c, "w_lists", h_lists.data(), sizeof(int32_t) * h_lists.size(), &dl)) == AVM_OK) d_lists = static_cast<const int32_t*>(dl);
+    }
+    if (rc == AVM_OK && relo_active) {
+      const void* da;
+      if ((rc = stage_array(c, "w_relo_active", relo_active, sizeof(int32_t) * B, &da)) == AVM_OK) d_active = static_cast<const int32_t*>(da);
+    }
+  } else if (split) {
+    int32_t* lists = static_cast<int32_t*>(pool_get(c, "w_lists", sizeof(int32_t) * 2 * (size_t)B));
+    if (!lists) return fail(c, AVM_ERR_HIP, "hipMalloc failed (window lists)");
+    d_lists = lists;
+    if ((rc = null_window_tables(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR)) != AVM_OK) return rc;
+    rc = flag_begin(
+        c, 4,
+        [&](int* flag) {
+          const hipError_t e = launch_validate_windows(*batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, flag, c->stream, fr);
+          return e != hipSuccess ? e : launch_solve_partition(B, relo_active, lists, flag + 3, c->stream);
+        },
+        &check);
+  } else {
+    rc = validate_windows_begin(c, batch, CHK_TRACKS | CHK_IMU | CHK_PRIOR, &check, fr);
+  }
   if (rc != AVM_OK) return rc;
 
   // choose forms (the slots for the throughput forms are sized before the priors' verdict is in: a batch that then takes the latency forms uses half of them)
-  const bool extended = opt->estimate_extrinsic != 0 || opt->estimate_td != 0 || batch->relo_n != nullptr;
-  SolveForms forms = choose_forms(batch->n_windows, c->n_slots, extended, marg, 0);
+  // (split: the plain windows' forms from the WHOLE batch as if it had no relocalization arrays; the marginalization takes the throughput form
+  //  when either view of the batch gives it)
+  const bool extended = est_x || batch->relo_n != nullptr;
+  auto forms_of = [&](int misfit) {
+    SolveForms f = choose_forms(B, c->n_slots, extended && !split, marg, misfit);
+    if (split) {
+      const SolveForms fx = choose_forms(B, c->n_slots, true, marg, misfit);
+      f.big_x = fx.big_x, f.marg_tp = f.marg_tp || fx.marg_tp;
+    }
+    return f;
+  };
+  SolveForms forms = forms_of(0);
   if ((rc = ensure_window_buffers(c, batch->n_windows, batch->max_samp, forms.tp || forms.big_x)) != AVM_OK) {
     if (check.dev) (void)hipStreamSynchronize(c->stream);
     return rc;
@@ -163,12 +245,23 @@ int avm_window_solve_batch_flags(avm_ctx* c, const avm_options* opt, avm_mem mem
   HIPCHK(c, mark(c, M_SOLVE));
   if (check.dev && (rc = flag_end(c, check, "window", SOLVE_FLAG_RULES, &tp_misfit)) != AVM_OK) return rc;
   if (check.dev && flags) flags_seen = (unsigned)check.host[2];
-  forms = choose_forms(batch->n_windows, c->n_slots, extended, marg, tp_misfit);
+  if (check.dev && split) n_ext = check.host[3];
+  forms = forms_of(tp_misfit);
+  if (split && n_ext == B) forms.tp = false;  // (no plain window: the extended kernel has the latency form only)
 
-  // solve
+  // solve (a split batch whose windows are all of one kind: the launches without a list)
   SolveArgs sa = solve_args(c, opt, d, d_sum);
-  if ((rc = run_solve(c, sa, extended, forms)) != AVM_OK) return rc;
+  const bool lists_run = relo_active && (est_x || (n_ext > 0 && n_ext < B));
+  if (lists_run)
+    rc = run_solve_split(c, sa, forms, est_x ? nullptr : d_lists, n_ext, d_active);
+  else
+    rc = run_solve(c, sa, split ? n_ext == B : extended, forms);
+  if (rc != AVM_OK) return rc;
   HIPCHK(c, mark(c, M_SOLVE_END));
+  {
+    const int64_t nx = relo_active ? (est_x ? B : n_ext) : (extended ? B : 0);
+    c->last_split[0] = B - nx, c->last_split[1] = nx, c->last_split[2] = nx == B ? -1 : (forms.tp ? 1 : 0), c->last_split[3] = lists_run ? 1 : 0;
+  }
 
   // marginalize and take the square root.  Per-window flags that are all AVM_MARGIN_NONE: no launch, every window reports n = -1
   int* marg_err = nullptr;

@@ -92,6 +92,21 @@ struct SolveArgs {
   long long time_cap_ticks;  // avm_options::max_solver_time_s in ticks of the device wall clock (wall_clock64); 0 = no cap
   const int32_t* marg_flags;  // [B] device, or null: every window takes opt.marginalization_flag (read by the -DAVM_MARG_MIXED marginalization kernels only)
 };
+// The argument block of the -DAVM_WIN_LIST builds of the solve kernel (window_solve_list.o, _x_list.o, _tp_list.o): SolveArgs with
+// the window list appended.  (A block of its own and not three more members of SolveArgs: the kernel-argument size of every existing
+// kernel is part of its code object's .note, and those code objects stay byte for byte what they were.)
+struct SolveListArgs : SolveArgs {
+  const int32_t* win_list;     // [n_list] device: the windows this launch solves, ascending; null: windows 0 .. n_list - 1
+  int n_list;
+  const int32_t* relo_active;  // [B] device, or null: a window has a relocalization frame only where this is != 0 (extended build)
+};
+// avm_window_solve_batch_relo's split of a batch: list[0 .. B) = the windows with relo_active == 0, list[B .. 2 B) = the others, both
+// ascending; counts[0] = the number of the others (the first list holds the rest).  One workgroup; solve_split.hip
+hipError_t launch_solve_partition(int n_windows, const int32_t* relo_active, int32_t* list, int* counts, hipStream_t stream);
+hipError_t launch_window_solve_list(const SolveListArgs& a, hipStream_t stream);     // window_solve_list.o: the latency build over a list
+hipError_t launch_window_solve_x_list(const SolveListArgs& a, hipStream_t stream);   // window_solve_x_list.o: the extended build
+hipError_t launch_window_solve_tp_list(const SolveListArgs& a, hipStream_t stream);  // window_solve_tp_list.o: the throughput build
+int window_solve_tp_list_occupancy();
 
 struct EvalArgs {
   avm_window_batch b;

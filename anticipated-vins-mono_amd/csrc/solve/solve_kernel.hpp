@@ -1,17 +1,26 @@
 // solve/solve_kernel.hpp - the solve kernel: window load, frame deal, TrustRegionMinimizer, gauge fix, summary
 // Part of window_solve.hip, which includes it inside namespace avm; no translation unit of its own.
 
+// -DAVM_WIN_LIST: the same kernel over a list of windows, A.win_list[0 .. A.n_list) (avm_window_solve_batch_relo: the plain and the
+// relocalizing windows of one batch take different builds).  Scratch slot, iscratch and prof stay the workgroup's; every table is the window's.
+#ifdef AVM_WIN_LIST
+#define AVM_SOLVE_NAME(k) k##_list_kernel
+#define AVM_SOLVE_ARGS SolveListArgs
+#else
+#define AVM_SOLVE_NAME(k) k##_kernel
+#define AVM_SOLVE_ARGS SolveArgs
+#endif
 #ifdef AVM_X
-#define AVM_SOLVE_KERNEL window_solve_x_kernel
+#define AVM_SOLVE_KERNEL AVM_SOLVE_NAME(window_solve_x)
 #define AVM_SOLVE_OCC
 #elif defined(AVM_TP)
-#define AVM_SOLVE_KERNEL window_solve_tp_kernel
+#define AVM_SOLVE_KERNEL AVM_SOLVE_NAME(window_solve_tp)
 #define AVM_SOLVE_OCC __attribute__((amdgpu_waves_per_eu(2, 2)))  // two four-wavefront workgroups per CU: 256 registers each
 #else
-#define AVM_SOLVE_KERNEL window_solve_kernel
+#define AVM_SOLVE_KERNEL AVM_SOLVE_NAME(window_solve)
 #define AVM_SOLVE_OCC
 #endif
-__global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A) {
+__global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_ARGS A) {
   lds_base_check();
   red_init();
   AVM_PRIO_LIGHT();
@@ -21,7 +30,12 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
   const avm_options& o = lds_opt();
   const avm_window_batch& B = A.b;
 
+#ifdef AVM_WIN_LIST
+  for (int li = blockIdx.x; li < A.n_list; li += gridDim.x) {
+    const int w = A.win_list ? A.win_list[li] : li;  // (the same for every thread of the workgroup)
+#else
   for (int w = blockIdx.x; w < B.n_windows; w += gridDim.x) {
+#endif
     WinCtx cl;
     cl.sc = as_global(A.scratch + (size_t)blockIdx.x * Scratch::TOTAL);
     cl.osf = as_global(A.iscratch + (size_t)blockIdx.x * ISCRATCH);
@@ -49,6 +63,9 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(SolveArgs A
     cl.aux = (cl.est_td && B.obs_vel_td) ? as_global(B.obs_vel_td + (size_t)w * B.max_obs * 4) : nullptr;
     if (!cl.aux) cl.est_td = 0;  // (the host refuses estimate_td without the per-observation data)
     cl.has_relo = B.relo_n && B.relo_feat && B.relo_xy && B.relo_pose;
+#ifdef AVM_WIN_LIST
+    if (A.relo_active && A.relo_active[w] == 0) cl.has_relo = 0;  // (none of the window's relo_* rows is read, relo_pose is not written)
+#endif
     cl.relo_n = cl.has_relo ? min(max(B.relo_n[w], 0), cl.nf) : 0;
     cl.relo_xy = cl.relo_n > 0 ? as_global(B.relo_xy + (size_t)w * B.max_feat * 2) : nullptr;
 #endif

@@ -30,6 +30,8 @@
 //   window_solve_tp.o   -DAVM_TP, throughput build: 256 threads and <= 80 KB of LDS, two windows per CU; solve and marginalization
 //   window_solve_mm.o, window_solve_tp_mm.o   -DAVM_MARG_MIXED [-DAVM_TP]: the marginalization kernel of the latency / throughput build once
 //                       more, with the marginalization flag per window (solve/marg_kernel.hpp); no solve kernel
+//   window_solve_list.o, window_solve_x_list.o, window_solve_tp_list.o   -DAVM_WIN_LIST [-DAVM_X | -DAVM_TP]: the solve kernel of each of the three
+//                       builds once more over a list of windows (solve/solve_kernel.hpp); nothing else
 // This file is the table of contents: every function and kernel is in a part under solve/, included below in DEFINITION ORDER, which
 // is the order the compiler emits the functions in - moving an include moves code.  A part that all three builds share carries their
 // differences inside its functions under #ifdef AVM_X / AVM_TP; a part that only some builds have sits behind a conditional include
@@ -76,7 +78,7 @@ namespace {
 #include "solve/solve_kernel.hpp"     // the kernel: load, frame deal, TrustRegionMinimizer, gauge fix
 #endif
 
-#ifndef AVM_X  // marginalization: latency and throughput builds
+#if !defined(AVM_X) && !defined(AVM_WIN_LIST)  // marginalization: latency and throughput builds
 #include "solve/marg_layout.hpp"        // what the marginalization computes, its map of LDS (namespace mg), mg_col
 #include "solve/marg_imu0.hpp"          // marg_imu0_raw, marg_prior_wave (phase A beside the frame tasks), marg_imu0_gram (phase D)
 #include "solve/marg_feature_sums.hpp"  // marg_feature_sums: phase B, the per-feature sums
@@ -87,7 +89,9 @@ namespace {
 #include "solve/marg_kernel.hpp"        // the marginalization kernel: one function, phases A to G and the output
 #endif
 
-#if defined(AVM_MARG_MIXED)  // each build's launchers and test exports
+#if defined(AVM_WIN_LIST)  // each build's launchers and test exports
+#include "solve/launch_list.hpp"
+#elif defined(AVM_MARG_MIXED)
 #include "solve/launch_mm.hpp"
 #elif defined(AVM_TP)
 #include "solve/launch_tp.hpp"

@@ -24,13 +24,16 @@ class Estimator:
 
     # the reference's name
     def optimization(self, windows: buffers.WindowArrays, want_summary: bool = True, prior_out: buffers.PriorOutArrays = None,
-                     summary_out=None, marginalization_flags=None):
+                     summary_out=None, marginalization_flags=None, relo_active=None):
         """Solve all windows in place.  `prior_out` lets a caller that solves batch after batch hand the same
         output slots back in (the reference allocates a new MarginalizationInfo per call; the slots are plain data);
         `summary_out` (buffers.summary_alloc) likewise for the per-window summaries: every record is rewritten by a call.
         `marginalization_flags`: [B] int32 where the windows live (numpy / device tensor), one MARGIN_OLD / MARGIN_SECOND_NEW /
         MARGIN_NONE per window instead of options.marginalization_flag (keyframe_decision() gives them); every window that reports
-        n < 0 - MARGIN_NONE, or MARGIN_SECOND_NEW with nothing to drop - then keeps the prior it was solved with."""
+        n < 0 - MARGIN_NONE, or MARGIN_SECOND_NEW with nothing to drop - then keeps the prior it was solved with.
+        `relo_active`: [B] int32 where the windows live, != 0 for the windows with a relocalization pending
+        (avm_window_solve_batch_relo: the others are solved as if the batch had no relocalization arrays and their relo_pose rows stay
+        as they are); True: the table resolve_relo(split=True) remembered on the windows.  None: the calls as they always were."""
         L = self.ctx._L
         B = windows.n_windows
         s = windows.struct()
@@ -41,7 +44,12 @@ class Estimator:
             prior = prior_out or buffers.PriorOutArrays.alloc(B, windows.dims["max_prior"], windows.dims["max_pblk"], dev)
         po = prior.struct() if prior is not None else None
         args = (C.byref(po) if po is not None else None, buffers.summary_ptr(summ) if summ is not None else None)
-        if marginalization_flags is None:
+        if relo_active is not None:
+            active = self._flags_like(windows, windows._relo_active if relo_active is True else relo_active)
+            flags = None if marginalization_flags is None else self._flags_like(windows, marginalization_flags)
+            rc = L.avm_window_solve_batch_relo(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), abi.iptr(flags), abi.iptr(active), *args)
+            self.ctx.check(rc, "avm_window_solve_batch_relo")
+        elif marginalization_flags is None:
             rc = L.avm_window_solve_batch(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), *args)
             self.ctx.check(rc, "avm_window_solve_batch")
         else:
@@ -158,11 +166,13 @@ class Estimator:
         rc = self.ctx._L.avm_set_relo_frame_batch(self.ctx.h, windows.mem, C.byref(s), abi.dptr(stamp), C.byref(sm), C.byref(ss))
         self.ctx.check(rc, "avm_set_relo_frame_batch")
 
-    def resolve_relo(self, tables: buffers.TrackTables, state: buffers.ReloState) -> int:
+    def resolve_relo(self, tables: buffers.TrackTables, state: buffers.ReloState, split: bool = False) -> int:
         """The match loop of optimization() (estimator.cpp:765-790) on tables.view (behind solve_view()): with a relocalization pending
         in some window, tables.view gets relo_n / relo_frame / relo_feat / relo_xy and relo_pose (state's own array: the solve returns the
         loop frame's pose into it), and optimization() takes the extended kernel; with none they are removed.  Returns the number of
-        windows with a relocalization pending."""
+        windows with a relocalization pending.
+        split=True: the arrays are attached whether or not a window is active, and tables.view remembers state's relocalization_info
+        as the table optimization(relo_active=True) passes: only the windows it marks take the extended kernel."""
         v = tables.view
         B, mf = v.n_windows, v.dims["max_feat"]
         out = getattr(tables, "_relo_out", None)
@@ -177,7 +187,8 @@ class Estimator:
         self.ctx.check(rc, "avm_relo_resolve_batch")
         for k in ("relo_n", "relo_frame", "relo_feat", "relo_xy", "relo_pose"):
             v.a.pop(k, None)
-        if n_active.value > 0:
+        v._relo_active = state.a["relocalization_info"] if split else None
+        if split or n_active.value > 0:
             v.a.update(out)
             v.a["relo_pose"] = state.a["relo_pose"]
         return int(n_active.value)

@@ -69,15 +69,17 @@ def lib():
         L.avm_debug_last_solve_form.argtypes = [vp]
         L.avm_debug_last_marg_form.argtypes = [vp]
         L.avm_debug_last_fsel_form.argtypes = [vp]
+        L.avm_debug_last_split.argtypes = [vp, C.POINTER(C.c_int64)]
         L.avm_debug_counters.argtypes = [vp, C.POINTER(C.c_int64)]
         L.avm_debug_preint_cache.argtypes = [vp, C.POINTER(C.c_int64)]
         L.avm_debug_fsel_evaluations.argtypes = [vp, C.POINTER(C.c_int64)]
         L.avm_debug_solve_tp_occupancy.argtypes = [C.POINTER(C.c_int)]
+        L.avm_debug_solve_tp_list_occupancy.argtypes = [C.POINTER(C.c_int)]
         L.avm_slide_window.argtypes = [vp, C.c_int, C.POINTER(abi.WindowBatch), C.c_int32, C.c_int32, C.c_double]
         L.avm_visual_initial_align_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.AlignBatch), C.POINTER(abi.WindowBatch),
                                                      C.POINTER(abi.AlignOut)]
         L.avm_debug_align_layout.argtypes = [C.POINTER(C.c_int)]
-        for name, argtypes in list(abi.PROTOTYPES.items()) + list(abi.TRACK_PROTOTYPES.items()) + list(abi.SELECT_PROTOTYPES.items()) + list(abi.RELO_PROTOTYPES.items()):
+        for name, argtypes in list(abi.PROTOTYPES.items()) + list(abi.TRACK_PROTOTYPES.items()) + list(abi.SELECT_PROTOTYPES.items()) + list(abi.RELO_PROTOTYPES.items()) + list(abi.SPLIT_PROTOTYPES.items()):
             getattr(L, name).argtypes = argtypes
         L.avm_debug_track_struct_sizes.argtypes = [C.POINTER(C.c_int)]
         L.avm_debug_relo_struct_sizes.argtypes = [C.POINTER(C.c_int)]
@@ -108,6 +110,7 @@ EXPORTS = [
     "avm_add_image_batch", "avm_imu_push_batch", "avm_solve_view_batch", "avm_solve_view_store_depths", "avm_slide_window_tracks",
     "avm_fsel_select_image_batch",
     "avm_headers_step_batch", "avm_set_relo_frame_batch", "avm_relo_resolve_batch", "avm_relo_finish_batch", "avm_prior_keep_batch",
+    "avm_window_solve_batch_relo",
 ]
 
 
@@ -173,6 +176,13 @@ class Context:
         """Which form of the marginalization kernel the last optimization() took: 'throughput' (two 256-thread workgroups per CU; it
         follows the solve's form unless a prior keeps a speed-bias block beyond frame 1, AVM_MARG_TP=0 switches it off) or 'latency'."""
         return "throughput" if self._L.avm_debug_last_marg_form(self.h) == 1 else "latency"
+
+    def last_split(self) -> tuple:
+        """How the last optimization() split its batch (avm_window_solve_batch_relo): (windows solved as plain ones, windows that took the
+        extended kernel, the plain ones' form: 0 latency / 1 throughput / -1 there were none, 1 when the list builds of the kernels ran)."""
+        out = (C.c_int64 * 4)()
+        self.check(self._L.avm_debug_last_split(self.h, out), "avm_debug_last_split")
+        return tuple(int(v) for v in out)
 
     def last_fsel_form(self) -> str:
         """Which form the last select_batch() started in: 'solo' (one workgroup per frame with lazy evaluation: batches of 33 frames and

@@ -370,6 +370,30 @@ int avm_window_solve_batch_flags(avm_ctx* ctx, const avm_options* opt, avm_mem m
                                  const int32_t* marginalization_flags /* [B], in `mem` space; NULL = opt's */,
                                  avm_prior_out* prior_out, avm_solve_summary* summary);
 
+/* The same call for a batch of streams of which SOME have a relocalization pending: every window takes the kernel form of its own
+ * problem, instead of the relocalization arrays sending the whole batch to the extended kernel.
+ * relo_active: [B] in `mem` space, or NULL.  NULL is avm_window_solve_batch_flags, call for call.  Otherwise:
+ *  - relo_active[w] != 0: window w has a relocalization pending - the test avm_relo_resolve_batch applies to
+ *    state->relocalization_info, and that array can be passed as it is.  relo_n, relo_frame, relo_feat, relo_xy and relo_pose of the
+ *    batch must then be present (AVM_ERR_INVALID otherwise, whatever the values of relo_active).  The window is solved exactly (bit for
+ *    bit) as avm_window_solve_batch_flags solves it in this batch with the arrays; relo_n[w] == 0 keeps its meaning: the loop frame
+ *    takes part in the gauge fix without a factor.
+ *  - relo_active[w] == 0: none of the window's relo_* rows is read (they may hold anything) and its relo_pose row is NOT written.
+ *    With opt->estimate_extrinsic == opt->estimate_td == 0 the window is solved by the kernel form it would get in this same batch
+ *    without the relocalization arrays - chosen from n_windows of the WHOLE batch, not from the number of such windows - so its result
+ *    is, to the bit, what it would have been had no stream of the batch been relocalizing.  A prior that does not fit the throughput
+ *    form sends the batch's plain windows to the latency form, as it does without the arrays (the rule stays per batch).
+ *  - With opt->estimate_extrinsic or opt->estimate_td set every window takes the extended kernel as before; relo_active then only
+ *    decides which windows have a relocalization frame (the first two points hold unchanged).
+ *  - The marginalization runs once, on the whole batch, and reads no relocalization data.  It takes its throughput form when the plain
+ *    windows' solve does or when n_windows exceeds the number of compute units (unless a prior does not fit it, or AVM_MARG_TP=0).
+ *  - marginalization_flags, summary, opt->max_solver_time_s and prior_out behave as in avm_window_solve_batch_flags;
+ *    avm_last_kernel_ms("window_solve") covers both launches of the solve. */
+int avm_window_solve_batch_relo(avm_ctx* ctx, const avm_options* opt, avm_mem mem, const avm_window_batch* batch,
+                                const int32_t* marginalization_flags /* [B] or NULL, as avm_window_solve_batch_flags */,
+                                const int32_t* relo_active /* [B], in `mem` space, or NULL */,
+                                avm_prior_out* prior_out, avm_solve_summary* summary);
+
 /* the single-call form, exactly one Estimator::optimization() (estimator.h:47): the same arguments with
  * batch->n_windows == 1 (AVM_ERR_INVALID otherwise).  One window occupies one compute unit; see DESIGN.md for its latency. */
 int avm_window_solve(avm_ctx* ctx, const avm_options* opt, avm_mem mem, const avm_window_batch* window,

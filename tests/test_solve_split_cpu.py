@@ -1,0 +1,60 @@
+"""CPU tier of the split solve (avm_window_solve_batch_relo): the header, the exports and the ctypes prototype, and the Python statement
+of the split that tests/test_solve_split.py takes its counts from.
+
+  partition_statement   the two ascending lists of window indices the partition kernel (csrc/solve_split.hip) writes: the windows
+                        without a pending relocalization, and the others
+"""
+import ctypes as C
+import importlib
+
+import numpy as np
+
+from helpers import abi
+from test_mixed_batch_cpu import NEW_ENTRY_POINTS, _header, _header_arg_count
+
+SPLIT_ENTRY_POINTS = ("avm_window_solve_batch_relo",)
+
+
+def partition_statement(active):
+    """active: [B] integers, != 0 = a relocalization is pending.  Returns (plain, extended), each ascending."""
+    plain, extended = [], []
+    for w, a in enumerate(np.asarray(active).tolist()):
+        (extended if a != 0 else plain).append(w)
+    return plain, extended
+
+
+def test_partition_statement():
+    assert partition_statement([]) == ([], [])
+    assert partition_statement([0]) == ([0], []) and partition_statement([1]) == ([], [0])
+    assert partition_statement([0, 1, 0, 1, 1]) == ([0, 2], [1, 3, 4])
+    assert partition_statement([5, 0, -1, 0]) == ([1, 3], [0, 2])           # any value but 0 is "pending", as avm_relo_resolve_batch reads it
+    assert partition_statement(np.zeros(70, np.int32)) == (list(range(70)), [])
+    assert partition_statement(np.ones(70, np.int32)) == ([], list(range(70)))
+    a = np.zeros(130, np.int32)
+    a[[0, 63, 64, 65, 129]] = 1                                             # either side of a 64-window ballot
+    plain, ext = partition_statement(a)
+    assert ext == [0, 63, 64, 65, 129] and plain == [w for w in range(130) if w not in ext]
+    assert sorted(plain + ext) == list(range(130))
+
+
+def test_header_declares_the_entry_point_and_keeps_the_abi():
+    h = _header()
+    assert "#define AVM_ABI_VERSION 6 " in h and abi.AVM_ABI_VERSION == 6
+    assert _header_arg_count("avm_window_solve_batch_relo") == _header_arg_count("avm_window_solve_batch_flags") + 1
+    assert set(abi.PROTOTYPES) == set(NEW_ENTRY_POINTS)                    # the older dicts keep their keys
+
+
+def test_prototype_matches_the_header_and_the_library_exports_both_symbols():
+    assert set(abi.SPLIT_PROTOTYPES) == set(SPLIT_ENTRY_POINTS)
+    for name, argtypes in abi.SPLIT_PROTOTYPES.items():
+        assert len(argtypes) == _header_arg_count(name), name
+    flags, relo = abi.PROTOTYPES["avm_window_solve_batch_flags"], abi.SPLIT_PROTOTYPES["avm_window_solve_batch_relo"]
+    assert relo[:5] == flags[:5] and relo[5] is abi.c_ip and relo[6:] == flags[5:]     # relo_active sits behind the flags
+    lib_m = importlib.import_module("anticipated-vins-mono_amd.lib")
+    assert set(SPLIT_ENTRY_POINTS) <= set(lib_m.EXPORTS)
+    L = lib_m.lib()                                                         # (loads without a GPU)
+    assert L.avm_window_solve_batch_relo.argtypes == relo
+    assert L.avm_debug_last_split.argtypes == [C.c_void_p, C.POINTER(C.c_int64)]
+    out = (C.c_int64 * 4)(9, 9, 9, 9)
+    assert L.avm_debug_last_split(None, out) == abi.AVM_ERR_INVALID and list(out) == [9, 9, 9, 9]
+    assert L.avm_window_solve_batch_relo(None, None, 0, None, None, None, None, None) == abi.AVM_ERR_INVALID
