@@ -391,6 +391,27 @@ class AlignOutArrays(_Arrays):
         return self._fill(abi.AlignOut())
 
 
+class SfmArrays(_Arrays):
+    """What Estimator::initialStructure hands GlobalSFM::construct and its PnP loop, one row per stream (synth.make_sfm; the reference
+    statement tests/golden/gen_global_sfm.py reads these tables): relativePose's result - l [B], relative_R [B, 9] row-major,
+    relative_T [B, 3] -, all_image_frame - n_frames [B], key_index [B, 11] - and the image of every frame - frame_n_pts [B, max_frames],
+    frame_pt_id [B, max_frames, max_pts] strictly ascending, frame_pt_xy [..., 2].  dims: n_windows, max_frames, max_pts and the BA's
+    ba_max_num_iterations / ba_max_solver_time_s.  A table container only (copy / to_device / to_host / slice): the C ABI has no entry
+    point that takes it yet, so there is no struct()."""
+
+    F64 = ["relative_R", "relative_T", "frame_pt_xy"]
+    I32 = ["l", "n_frames", "key_index", "frame_n_pts", "frame_pt_id"]
+
+    @property
+    def n_windows(self) -> int:
+        return self.dims["n_windows"]
+
+    def slice(self, lo: int, hi: int) -> "SfmArrays":
+        d = dict(self.dims)
+        d["n_windows"] = hi - lo
+        return SfmArrays(d, {k: v[lo:hi] for k, v in self.a.items()})
+
+
 def summary_alloc(n_windows: int, device=None):
     """[B] avm_solve_summary records (numpy structured array, or a raw byte tensor on device)."""
     if device is None:

@@ -595,3 +595,92 @@ def make_align(n_windows, n_frames, key_index=None, scale=2.5, first_id=0, max_f
         return align, None
     d = dict(n_windows=B, max_feat=max(n_feat, 1), max_obs=max(n_feat, 1) * abi.NFRAMES, max_samp=wms, max_prior=1, max_pblk=1)
     return align, WindowArrays(d, win)
+
+
+SEED_SFM = 0x5F3D0000  # make_sfm's own stream (the tracks and images; the trajectory and IMU are make_align's)
+
+
+def make_sfm(n_windows, tracks, n_frames=11, key_index=None, l=0, noise_px=0.5, first_id=0, scale=2.5, max_frames=None, max_feat=None,
+             max_pts=None, extra_ids=3):
+    """Inputs of the deterministic half of Estimator::initialStructure for B streams: GlobalSFM::construct and the PnP of every frame.
+
+    The trajectory, all_image_frame's raw IMU and the window's IMU tables are make_align's (same arguments, same seeds); its SfM poses
+    frame_R / frame_T are taken as the TRUE camera trajectory (in c0, up to `scale`), from which this function draws
+      tracks   a list of (start_frame, length, count) over the 11 key frames, stored in f_manager's order (start_frame non-decreasing):
+               a 3-D point 2 .. 12 m (divided by `scale`) in front of the start frame's camera, observed with noise_px / 460 of noise
+               in each of its frames; feat_id[b, e] = 7 + 3 e,
+      images   for every non-key frame the points whose track spans it, observed the same way, under their ids in ascending order,
+               followed by `extra_ids` ids no track has (key frames get frame_n_pts = 0: they are never read),
+      relativePose's result   l, relative_R = R_l^T R_10 and relative_T = R_l^T (p_10 - p_l) normalized to 1 (what the five-point solver
+               returns), perturbed by 0.05 degrees and 0.5 % of direction noise.
+    Returns (SfmArrays, WindowArrays `full`, feat_id [B, max_feat], AlignArrays, truth) with truth = {"R": camera orientations in c0
+    [B, n_frames, 3, 3], "p": camera positions [B, n_frames, 3]}."""
+    from .buffers import SfmArrays
+
+    B, F = n_windows, n_frames
+    key = np.arange(abi.NFRAMES, dtype=np.int32) if key_index is None else np.asarray(key_index, np.int32)
+    tracks = sorted((int(s), int(n), int(c)) for s, n, c in tracks)
+    n_feat = sum(c for _, _, c in tracks)
+    MFE = max_feat or n_feat
+    assert n_feat <= MFE and all(n >= 1 and s >= 0 and s + n <= abi.NFRAMES for s, n, _ in tracks)
+    al, win = make_align(B, F, key_index=key, scale=scale, first_id=first_id, max_frames=max_frames, n_feat=MFE)
+    MF = al.dims["max_frames"]
+    MP = max_pts or (n_feat + extra_ids)
+    w = win.a
+    for k in ("n_feat", "feat_start", "feat_nobs", "feat_obs_begin", "obs_xy"):
+        w[k][:] = 0
+    w["inv_depth"][:] = -1.0
+    feat_id = np.zeros((B, MFE), np.int32)
+    s = {"l": np.full(B, l, np.int32), "relative_R": np.zeros((B, 9)), "relative_T": np.zeros((B, 3)), "n_frames": np.full(B, F, np.int32),
+         "key_index": np.tile(key, (B, 1)).astype(np.int32), "frame_n_pts": np.zeros((B, MF), np.int32),
+         "frame_pt_id": np.zeros((B, MF, MP), np.int32), "frame_pt_xy": np.zeros((B, MF, MP, 2))}
+    truth = {"R": np.zeros((B, F, 3, 3)), "p": np.zeros((B, F, 3))}
+    sig = noise_px / 460.0
+    for b in range(B):
+        rng = np.random.Generator(np.random.Philox(key=SEED_SFM + first_id + b))
+        Rc = [al.a["frame_R"][b, k].reshape(3, 3) @ RIC for k in range(F)]
+        pc = [al.a["frame_T"][b, k].copy() for k in range(F)]
+        truth["R"][b], truth["p"][b] = np.array(Rc), np.array(pc)
+        see = lambda X, k: Rc[k].T @ (X - pc[k])
+        e = o = 0
+        pts = []
+        for s0, L, cnt in tracks:
+            for _ in range(cnt):
+                for _ in range(200):
+                    xy = np.array([rng.uniform(-0.7, 0.7), rng.uniform(-0.45, 0.45)])
+                    X = Rc[key[s0]] @ (np.array([xy[0], xy[1], 1.0]) * rng.uniform(2.0, 12.0) / scale) + pc[key[s0]]
+                    cams = [see(X, key[f]) for f in range(s0, s0 + L)]
+                    if min(c[2] for c in cams) >= 0.5 / scale and max(abs(c[0] / c[2]) for c in cams) < 1.2:
+                        break
+                w["feat_start"][b, e], w["feat_nobs"][b, e], w["feat_obs_begin"][b, e] = s0, L, o
+                w["obs_xy"][b, o : o + L] = np.array([c[:2] / c[2] for c in cams]) + rng.normal(0, sig, (L, 2))
+                feat_id[b, e] = 7 + 3 * e
+                pts.append((X, key[s0], key[s0 + L - 1]))
+                o += L
+                e += 1
+        w["n_feat"][b] = e
+        iskey = np.zeros(F, bool)
+        iskey[key] = True
+        for k in range(F):
+            if iskey[k]:
+                continue
+            n = 0
+            for j, (X, k0, k1) in enumerate(pts):
+                c = see(X, k)
+                if k0 < k < k1 and c[2] >= 0.5 / scale:
+                    s["frame_pt_id"][b, k, n] = feat_id[b, j]
+                    s["frame_pt_xy"][b, k, n] = c[:2] / c[2] + rng.normal(0, sig, 2)
+                    n += 1
+            for x in range(extra_ids):
+                s["frame_pt_id"][b, k, n] = 7 + 3 * MFE + 5 * x + 1
+                s["frame_pt_xy"][b, k, n] = rng.uniform(-0.5, 0.5, 2)
+                n += 1
+            s["frame_n_pts"][b, k] = n
+        kl, kn = key[l], key[abi.NFRAMES - 1]
+        dR = _expm_so3(rng.normal(0, np.deg2rad(0.05), 3))
+        t = Rc[kl].T @ (pc[kn] - pc[kl])
+        t = t / np.linalg.norm(t) + rng.normal(0, 0.005, 3)
+        s["relative_R"][b] = (Rc[kl].T @ Rc[kn] @ dR).reshape(9)
+        s["relative_T"][b] = t / np.linalg.norm(t)
+    dims = dict(n_windows=B, max_frames=MF, max_pts=MP, ba_max_num_iterations=50, ba_max_solver_time_s=0.0)
+    return SfmArrays(dims, s), win, feat_id, al, truth
