@@ -144,6 +144,52 @@ int avmt_solve_dd(const avm_options* opt, const avm_window_batch* batch, int w, 
   return R.sum.num_iterations;
 }
 
+// The pre-integration of the ten intervals of window w in the wide scalar type: PreIntegration::push_back over the raw samples and
+// imu_sqrt_info, as load_window runs them per interval (oracle/window_io.hpp) - from the batch's imu_* tables and the options' noise
+// densities alone, so a batch without features (or without any other table) is fine.  The sample loop is load_window's, repeated here
+// and not shared with it: the FP64 build of that header decides its fused multiply-adds by how load_window is inlined, a helper called
+// from both moved the last bits of the FP64 oracle's covariances and, through them, every stream test that amplifies them.
+// Every output is rounded once to FP64 (the `hi` array) and, where the `lo` array is given, followed by lo = (double)(x - hi): the pair
+// carries the binary128 value to 32 digits (tests/test_preint_truth.py against tests/golden/preint_mp.npz).  Per interval: delta [10]
+// in the ABI's order p | qx qy qz qw | v, jacobian [225], covariance [225], sum_dt [1], sqrt_info [225].  Any pointer may be NULL.
+int avmt_imu_preintegrate(const avm_options* opt, const avm_window_batch* batch, int w, double* delta_hi, double* delta_lo,
+                          double* jacobian_hi, double* jacobian_lo, double* covariance_hi, double* covariance_lo, double* sum_dt_hi,
+                          double* sum_dt_lo, double* sqrt_info_hi, double* sqrt_info_lo) {
+  const avm_window_batch& B = *batch;
+  auto put = [](avmo_real v, double* hi, double* lo, size_t at) {
+    const double h = (double)v;
+    if (hi) hi[at] = h;
+    if (lo) lo[at] = (double)(v - (avmo_real)h);
+  };
+  ImuNoise nz{opt->acc_n, opt->gyr_n, opt->acc_w, opt->gyr_w};
+  for (int j = 0; j < AVM_WINDOW_SIZE; j++) {
+    const size_t iv = (size_t)w * AVM_WINDOW_SIZE + j;
+    const auto* acc = B.imu_acc + iv * (B.max_samp + 1) * 3;
+    const auto* gyr = B.imu_gyr + iv * (B.max_samp + 1) * 3;
+    const auto* dt = B.imu_dt + iv * B.max_samp;
+    const auto* lba = B.imu_lin_ba + iv * 3;
+    const auto* lbg = B.imu_lin_bg + iv * 3;
+    PreIntegration p(V3(acc[0], acc[1], acc[2]), V3(gyr[0], gyr[1], gyr[2]), V3(lba[0], lba[1], lba[2]), V3(lbg[0], lbg[1], lbg[2]), nz);
+    const int ns = B.imu_n[iv];
+    for (int s = 0; s < ns; s++)
+      p.push_back(dt[s], V3(acc[3 * (s + 1)], acc[3 * (s + 1) + 1], acc[3 * (s + 1) + 2]),
+                  V3(gyr[3 * (s + 1)], gyr[3 * (s + 1) + 1], gyr[3 * (s + 1) + 2]));
+    const avmo_real d[10] = {p.delta_p.x, p.delta_p.y, p.delta_p.z, p.delta_q.x, p.delta_q.y, p.delta_q.z, p.delta_q.w,
+                             p.delta_v.x, p.delta_v.y, p.delta_v.z};
+    for (int k = 0; k < 10; k++) put(d[k], delta_hi, delta_lo, (size_t)j * 10 + k);
+    put(p.sum_dt, sum_dt_hi, sum_dt_lo, (size_t)j);
+    for (int k = 0; k < 225; k++) {
+      put(p.jacobian.a[k], jacobian_hi, jacobian_lo, (size_t)j * 225 + k);
+      put(p.covariance.a[k], covariance_hi, covariance_lo, (size_t)j * 225 + k);
+    }
+    if (sqrt_info_hi || sqrt_info_lo) {
+      const Mat U = imu_sqrt_info(p);
+      for (int k = 0; k < 225; k++) put(U.a[k], sqrt_info_hi, sqrt_info_lo, (size_t)j * 225 + k);
+    }
+  }
+  return 0;
+}
+
 // FeatureSelector::select of frame p of the batch in the wide scalar type (oracle/fsel.hpp: calcInfoFromRobotMotion,
 // calcInfoFromFeatures, the lazy greedy of selectInformativeFeatures with sortedlogDetUB's std::map, Utility::logdet by Cholesky -
 // feature_selector.cpp:239-728): the ids the reference's algorithm selects when no logdet comparison is decided by rounding.

@@ -66,6 +66,41 @@ def preintegrate(opt, win):
     return d, j, cv, sd, sq
 
 
+_TRUTH = None
+
+
+def truth_lib():
+    """libavm_truth.so: the oracle with binary128 as its scalar type (oracle/avm_truth.cpp)."""
+    global _TRUTH
+    if _TRUTH is None:
+        path = os.path.join(_HERE, "libavm_truth.so")
+        if not os.path.exists(path):
+            subprocess.check_call(["make", "-C", _HERE, "-s", "libavm_truth.so"])
+        _TRUTH = C.CDLL(path)
+    return _TRUTH
+
+
+def truth_preintegrate(opt, win, sqrt_info=True):
+    """avmt_imu_preintegrate on every window of host WindowArrays: the pre-integration in binary128 from the imu_* tables and the
+    options' noise.  Returns (hi, lo): two dicts of delta [B,10,10], jacobian, covariance [B,10,15,15], sum_dt [B,10] and
+    sqrt_info [B,10,15,15]; hi is the value rounded once to FP64, hi + lo the value to 32 digits."""
+    import numpy as np
+    abi = importlib.import_module("anticipated-vins-mono_amd.abi")
+    B = win.n_windows
+    shapes = dict(delta=(B, 10, 10), jacobian=(B, 10, 15, 15), covariance=(B, 10, 15, 15), sum_dt=(B, 10), sqrt_info=(B, 10, 15, 15))
+    hi, lo = {k: np.zeros(s) for k, s in shapes.items()}, {k: np.zeros(s) for k, s in shapes.items()}
+    s = win.struct()
+    L = truth_lib()
+    for w in range(B):
+        ptrs = []
+        for k in shapes:
+            skip = k == "sqrt_info" and not sqrt_info
+            ptrs += [None if skip else abi.dptr(hi[k][w]), None if skip else abi.dptr(lo[k][w])]
+        rc = L.avmt_imu_preintegrate(C.byref(opt), C.byref(s), w, *ptrs)
+        assert rc == 0
+    return hi, lo
+
+
 def eval_factors(opt, win, apply_loss=False):
     import numpy as np
     abi = importlib.import_module("anticipated-vins-mono_amd.abi")

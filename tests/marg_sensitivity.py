@@ -85,22 +85,10 @@ def install_prior(win, p):
 # The extended-precision arbiter (oracle/avm_truth.cpp: the oracle's marginalization with __float128 as its scalar type,
 # following marginalization_factor.cpp:232-291 literally from the same FP64 inputs).  "How far is X from the value the
 # reference's algorithm defines" replaces "how far is X from the oracle, in units of the oracle's own scatter".
-_TRUTH = None
-
-
 def truth_lib():
-    global _TRUTH
-    if _TRUTH is None:
-        import ctypes as C
-        import os
-        import subprocess
+    import oracle_py
 
-        here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
-        path = os.path.join(here, "libavm_truth.so")
-        if not os.path.exists(path):
-            subprocess.check_call(["make", "-C", here, "-s", "libavm_truth.so"])
-        _TRUTH = C.CDLL(path)
-    return _TRUTH
+    return oracle_py.truth_lib()
 
 
 def truth_marginalize(w, opt):

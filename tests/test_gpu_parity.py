@@ -48,11 +48,14 @@ def test_ragged_imu_sample_counts(estimator, oracle):
     w.a["imu_n"][1, 7] = 1
     w.a["imu_n"][1, 8] = 0
     d, J, P, sd = estimator.preintegrate(w)
-    od, oJ, oP, osd, _ = oracle.preintegrate(estimator.options, w)
+    sq = estimator.sqrt_info(2)
+    od, oJ, oP, osd, osq = oracle.preintegrate(estimator.options, w)
     assert rel(d, od) < 1e-12 and rel(J, oJ) < 1e-12 and rel(sd, osd) < 1e-15
     ok = np.ones((2, 10), bool)
     ok[1, 8] = False  # zero samples: covariance is all zero (singular), nothing to compare
     assert rel(P[ok], oP[ok]) < 1e-12
+    two = w.a["imu_n"] >= 2  # one sample: a covariance of rank 12, no sqrt_info is defined (tests/test_preint_truth.py)
+    assert two.sum() == 18 and rel(sq[two], osq[two]) < 1e-12
 
 
 def test_factor_evaluation_matches_oracle_and_golden(estimator, oracle):

@@ -81,8 +81,11 @@ def test_preintegration_with_wide_tables_matches_oracle(ctx, oracle):
     E = _est(ctx)
     w = synth.make_windows(3, tracks="sparse", n_feat=300, max_feat=abi.MAX_FEAT_WIDE)
     d, J, P, sd = E.preintegrate(w)
-    od, oJ, oP, osd, _ = oracle.preintegrate(E.options, w)
-    for a, b in ((d, od), (J, oJ), (P, oP), (sd, osd)):
+    sq = E.sqrt_info(3)
+    od, oJ, oP, osd, osq = oracle.preintegrate(E.options, w)
+    two = w.a["imu_n"] >= 2
+    assert two.all()
+    for a, b in ((d, od), (J, oJ), (P, oP), (sd, osd), (sq[two], osq[two])):
         assert rel(a, b) < 1e-12
 
 
