@@ -15,6 +15,7 @@
 
 #include "window_io.hpp"  // (-> solver.hpp -> factors.hpp -> linalg.hpp, all in the wide scalar type from here on)
 #include "fsel_io.hpp"    // (-> fsel.hpp)
+#include "triangulate.hpp"
 
 #undef double
 
@@ -187,6 +188,88 @@ int avmt_imu_preintegrate(const avm_options* opt, const avm_window_batch* batch,
       for (int k = 0; k < 225; k++) put(U.a[k], sqrt_info_hi, sqrt_info_lo, (size_t)j * 225 + k);
     }
   }
+  return 0;
+}
+
+// ---- the small per-feature / per-window / per-factor operations around the solve (tests/test_window_ops_truth.py) ----------------------
+// Each is the oracle's own function (triangulate.hpp, factors.hpp) on the same FP64 tables, converted exactly; each output is rounded
+// once to FP64 (`hi`) and, where a `lo` array is given, followed by lo = (double)(x - hi).  Any output pointer may be NULL.
+namespace {
+struct HiLo {
+  static void put(avmo_real v, double* hi, double* lo, size_t at) {
+    const double h = (double)v;
+    if (hi) hi[at] = h;
+    if (lo) lo[at] = (double)(v - (avmo_real)h);
+  }
+};
+}  // namespace
+
+// FeatureManager::triangulate of feature e of window w (triangulate_feature; its Hestenes sweep converges to binary128's roundoff,
+// AVMO_SVD_TOL of quad_prelude.hpp): ratio = v[2] / v[3] as it comes out of the SVD, depth = the same after `< 0.1 -> init_depth`,
+// sigma [4] the singular values of the (2 nobs) x 4 system in descending order, V [4][4] its right singular vectors (column k belongs
+// to sigma[k]; the last column is v, up to the sign the sweep happened to give it).  Whatever inv_depth holds for the feature is not read.
+int avmt_triangulate(const avm_window_batch* batch, int w, int e, double init_depth, double* ratio_hi, double* ratio_lo, double* depth_hi,
+                     double* depth_lo, double* sigma_hi, double* sigma_lo, double* V_hi, double* V_lo) {
+  const avm_window_batch& B = *batch;
+  if (w < 0 || w >= B.n_windows || e < 0 || e >= B.max_feat) return -1;
+  const size_t k = (size_t)w * B.max_feat + e;
+  const int start = B.feat_start[k], nobs = B.feat_nobs[k];
+  if (start < 0 || nobs < 1 || start + nobs > AVM_NFRAMES) return -1;
+  avmo_real pose[AVM_NFRAMES][7], ex[7];
+  for (int f = 0; f < AVM_NFRAMES; f++)
+    for (int c = 0; c < 7; c++) pose[f][c] = B.pose[((size_t)w * AVM_NFRAMES + f) * 7 + c];
+  for (int c = 0; c < 7; c++) ex[c] = B.ex_pose[(size_t)w * 7 + c];
+  std::vector<avmo_real> obs((size_t)2 * nobs);
+  const auto* src = B.obs_xy + ((size_t)w * B.max_obs + B.feat_obs_begin[k]) * 2;
+  for (int c = 0; c < 2 * nobs; c++) obs[c] = src[c];
+  TriDetail D;
+  tri_detail() = &D;
+  const avmo_real depth = triangulate_feature(pose, ex, start, nobs, obs.data(), (avmo_real)init_depth);
+  tri_detail() = nullptr;
+  HiLo::put(D.ratio, ratio_hi, ratio_lo, 0);
+  HiLo::put(depth, depth_hi, depth_lo, 0);
+  for (int c = 0; c < 4; c++) HiLo::put(D.sig[c], sigma_hi, sigma_lo, c);
+  for (int c = 0; c < 16; c++) HiLo::put(D.V[c], V_hi, V_lo, c);
+  return 0;
+}
+
+// Estimator::processIMU's dead-reckoning of the newest frame (propagate_newest_frame) on interval 9 of window w, from pose [10] and
+// speedbias [10] of the batch and gravity g: pose_out [7] (p | qx qy qz qw), sb_out [9] (v, and the biases as they went in).
+int avmt_imu_propagate(const avm_window_batch* batch, int w, const double* g, double* pose_hi, double* pose_lo, double* sb_hi, double* sb_lo) {
+  const avm_window_batch& B = *batch;
+  if (w < 0 || w >= B.n_windows) return -1;
+  const size_t iv = (size_t)w * AVM_WINDOW_SIZE + (AVM_WINDOW_SIZE - 1);
+  const int n = B.imu_n[iv];
+  if (n < 0 || n > B.max_samp) return -1;
+  avmo_real pose[7], sb[9];
+  for (int c = 0; c < 7; c++) pose[c] = B.pose[((size_t)w * AVM_NFRAMES + AVM_WINDOW_SIZE) * 7 + c];
+  for (int c = 0; c < 9; c++) sb[c] = B.speedbias[((size_t)w * AVM_NFRAMES + AVM_WINDOW_SIZE) * 9 + c];
+  std::vector<avmo_real> dt(n), acc((size_t)3 * (n + 1)), gyr((size_t)3 * (n + 1));
+  for (int s = 0; s < n; s++) dt[s] = B.imu_dt[iv * B.max_samp + s];
+  for (int c = 0; c < 3 * (n + 1); c++) acc[c] = B.imu_acc[iv * (B.max_samp + 1) * 3 + c], gyr[c] = B.imu_gyr[iv * (B.max_samp + 1) * 3 + c];
+  propagate_newest_frame(pose, sb, n, dt.data(), acc.data(), gyr.data(), V3(g[0], g[1], g[2]));
+  for (int c = 0; c < 7; c++) HiLo::put(pose[c], pose_hi, pose_lo, c);
+  for (int c = 0; c < 9; c++) HiLo::put(sb[c], sb_hi, sb_lo, c);
+  return 0;
+}
+
+// ProjectionTdFactor::Evaluate of factor i of the batch (projection_td_factor_evaluate): residual [2], jac [2][20].
+int avmt_projection_td_eval(const avm_td_factor_batch* f, int i, double* residual_hi, double* residual_lo, double* jac_hi, double* jac_lo) {
+  if (i < 0 || i >= f->n) return -1;
+  auto two = [&](const double* p, avmo_real out[2]) { out[0] = p[2 * i], out[1] = p[2 * i + 1]; };
+  auto seven = [&](const double* p, avmo_real out[7]) {
+    for (int c = 0; c < 7; c++) out[c] = p[7 * (size_t)i + c];
+  };
+  avmo_real pts_i[2], pts_j[2], vel_i[2], vel_j[2], pose_i[7], pose_j[7], ex[7], r[2], J[40];
+  two(f->pts_i, pts_i), two(f->pts_j, pts_j), two(f->vel_i, vel_i), two(f->vel_j, vel_j);
+  seven(f->pose_i, pose_i), seven(f->pose_j, pose_j), seven(f->ex_pose, ex);
+  const bool want_jac = jac_hi || jac_lo;
+  projection_td_factor_evaluate(pts_i, pts_j, vel_i, vel_j, f->td_i[i], f->td_j[i], f->row_i[i], f->row_j[i], f->tr, f->row,
+                                (avmo_real)(f->focal_length / 1.5) /* sqrt_info is an FP64 constant (estimator.cpp:17) */, pose_i, pose_j, ex, f->inv_depth[i], f->td[i], r,
+                                want_jac ? J : nullptr);
+  for (int c = 0; c < 2; c++) HiLo::put(r[c], residual_hi, residual_lo, c);
+  if (want_jac)
+    for (int c = 0; c < 40; c++) HiLo::put(J[c], jac_hi, jac_lo, c);
   return 0;
 }
 

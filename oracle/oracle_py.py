@@ -101,6 +101,67 @@ def truth_preintegrate(opt, win, sqrt_info=True):
     return hi, lo
 
 
+def _hilo(shapes):
+    import numpy as np
+    return {k: np.zeros(s) for k, s in shapes.items()}, {k: np.zeros(s) for k, s in shapes.items()}
+
+
+def truth_triangulate(win, init_depth=5.0, features=None):
+    """avmt_triangulate on host WindowArrays: FeatureManager::triangulate in binary128 for every (window, feature) pair of `features`
+    (default: every row e < n_feat; rows with fewer than two observations included - their ratio is whatever a rank-2 system gives).
+    Returns (hi, lo): dicts of ratio [B, max_feat] (v[2] / v[3] before the 0.1 rule), depth [B, max_feat] (after it), sigma
+    [B, max_feat, 4] (descending) and V [B, max_feat, 4, 4] (column k belongs to sigma[k]); NaN where nothing was asked for."""
+    import numpy as np
+    abi = importlib.import_module("anticipated-vins-mono_amd.abi")
+    B, mf = win.n_windows, win.dims["max_feat"]
+    hi, lo = _hilo(dict(ratio=(B, mf), depth=(B, mf), sigma=(B, mf, 4), V=(B, mf, 4, 4)))
+    for d in (hi, lo):
+        for v in d.values():
+            v[:] = np.nan
+    if features is None:
+        features = [(w, e) for w in range(B) for e in range(int(win.a["n_feat"][w]))]
+    s = win.struct()
+    L = truth_lib()
+    L.avmt_triangulate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double] + [abi.c_dp] * 8
+    for w, e in features:
+        ptrs = []
+        for k in ("ratio", "depth", "sigma", "V"):
+            ptrs += [abi.dptr(hi[k][w, e:e + 1]), abi.dptr(lo[k][w, e:e + 1])]
+        rc = L.avmt_triangulate(C.byref(s), int(w), int(e), float(init_depth), *ptrs)
+        assert rc == 0, (w, e)
+    return hi, lo
+
+
+def truth_imu_propagate(win, g):
+    """avmt_imu_propagate on every window of host WindowArrays (nothing is changed in place).  Returns (hi, lo): dicts of pose [B, 7]
+    and speedbias [B, 9] of frame 10 after the dead-reckoning."""
+    import numpy as np
+    abi = importlib.import_module("anticipated-vins-mono_amd.abi")
+    B = win.n_windows
+    hi, lo = _hilo(dict(pose=(B, 7), speedbias=(B, 9)))
+    gg = np.ascontiguousarray(g, float)
+    s = win.struct()
+    L = truth_lib()
+    for w in range(B):
+        rc = L.avmt_imu_propagate(C.byref(s), w, abi.dptr(gg), abi.dptr(hi["pose"][w]), abi.dptr(lo["pose"][w]), abi.dptr(hi["speedbias"][w]),
+                                  abi.dptr(lo["speedbias"][w]))
+        assert rc == 0, w
+    return hi, lo
+
+
+def truth_projection_td_eval(arrays, tr, row, focal_length=460.0):
+    """avmt_projection_td_eval on every factor of `arrays` (abi.td_factor_batch).  Returns (hi, lo): dicts of residual [n, 2], jac [n, 2, 20]."""
+    abi = importlib.import_module("anticipated-vins-mono_amd.abi")
+    f = abi.td_factor_batch(arrays, tr, row, focal_length)
+    hi, lo = _hilo(dict(residual=(f.n, 2), jac=(f.n, 2, 20)))
+    L = truth_lib()
+    for i in range(f.n):
+        rc = L.avmt_projection_td_eval(C.byref(f), i, abi.dptr(hi["residual"][i]), abi.dptr(lo["residual"][i]), abi.dptr(hi["jac"][i]),
+                                       abi.dptr(lo["jac"][i]))
+        assert rc == 0, i
+    return hi, lo
+
+
 def eval_factors(opt, win, apply_loss=False):
     import numpy as np
     abi = importlib.import_module("anticipated-vins-mono_amd.abi")

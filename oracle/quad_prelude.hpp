@@ -49,6 +49,9 @@ inline avmo_real min(double a, avmo_real b) { return b < a ? b : (avmo_real)a; }
 #define AVMO_EIG_EPS scalbnq((avmo_real)1, -112)
 // (the scalar type's limits: see oracle/linalg.hpp.  The unit roundoff that Eigen's slerp compares with stays FP64's: the
 //  branch `|d| >= 1 - eps` is part of the algorithm, the inputs are FP64 quaternions)
+// (the Hestenes sweep of triangulate.hpp stops at the scalar's own roundoff, not at FP64's 2.3e-16)
+#define AVMO_SVD_TOL AVMO_EIG_EPS
+#define AVMO_TRI_DETAIL 1
 #define AVMO_NUM_MAX FLT128_MAX
 #define AVMO_NUM_MIN FLT128_MIN
 #define AVMO_NUM_EPSILON ((avmo_real)2.220446049250313e-16)

@@ -9,7 +9,26 @@
 #pragma once
 #include "linalg.hpp"
 
+// The convergence test of the sweep, relative to the two columns' norms: FP64's roundoff here.  The extended-precision build
+// (quad_prelude.hpp) sets its own scalar's, so that its singular vectors are orthogonal to ITS working precision.
+#ifndef AVMO_SVD_TOL
+#define AVMO_SVD_TOL 2.3e-16
+#endif
+
 namespace avmo {
+
+// The arbiter's build (AVMO_TRI_DETAIL, quad_prelude.hpp) also hands out what the depth was taken from: the ratio before the 0.1 rule,
+// all four singular values in descending order and the right singular vectors, V[i * 4 + k] = component i of the vector of sig[k].
+// It is compiled in there only - an argument more on these functions changes how the FP64 build inlines them, and with that its bits.
+#ifdef AVMO_TRI_DETAIL
+struct TriDetail {
+  double ratio, sig[4], V[16];
+};
+inline TriDetail*& tri_detail() {
+  static thread_local TriDetail* p = nullptr;
+  return p;
+}
+#endif
 
 // right singular vector of the smallest singular value of the n x 4 matrix A (row-major), n >= 4
 inline void smallest_right_singular_vector(std::vector<double> A, int n, double v[4]) {
@@ -23,7 +42,7 @@ inline void smallest_right_singular_vector(std::vector<double> A, int n, double 
           const double x = A[i * 4 + p], y = A[i * 4 + q];
           app += x * x, aqq += y * y, apq += x * y;
         }
-        if (std::fabs(apq) <= 1e-300 || std::fabs(apq) <= 2.3e-16 * std::sqrt(app * aqq)) continue;
+        if (std::fabs(apq) <= 1e-300 || std::fabs(apq) <= AVMO_SVD_TOL * std::sqrt(app * aqq)) continue;
         rotated = true;
         const double tau = (aqq - app) / (2.0 * apq);
         const double t = (tau >= 0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
@@ -47,6 +66,25 @@ inline void smallest_right_singular_vector(std::vector<double> A, int n, double 
     if (s < bn) bn = s, best = j;
   }
   for (int i = 0; i < 4; i++) v[i] = V[i][best];
+#ifdef AVMO_TRI_DETAIL
+  if (TriDetail* D = tri_detail()) {
+    double nn[4];
+    int ord[4] = {0, 1, 2, 3};
+    for (int j = 0; j < 4; j++) {
+      nn[j] = 0;
+      for (int i = 0; i < n; i++) nn[j] += A[i * 4 + j] * A[i * 4 + j];
+    }
+    nn[best] = -1;  // (the vector handed out as v is the last one, whatever a tie would say)
+    for (int a = 0; a < 4; a++)
+      for (int b = a + 1; b < 4; b++)
+        if (nn[ord[b]] > nn[ord[a]]) std::swap(ord[a], ord[b]);
+    nn[best] = bn;
+    for (int k = 0; k < 4; k++) {
+      D->sig[k] = std::sqrt(nn[ord[k]]);
+      for (int i = 0; i < 4; i++) D->V[i * 4 + k] = V[i][ord[k]];
+    }
+  }
+#endif
 }
 
 // depth of one feature: poses[f] = (p, q) of the body frames, (tic, qic) the camera extrinsic, obs[k] the normalized
@@ -81,6 +119,9 @@ inline double triangulate_feature(const double (*pose)[7], const double* ex, int
   double v[4];
   smallest_right_singular_vector(A, 2 * nobs, v);
   double depth = v[2] / v[3];
+#ifdef AVMO_TRI_DETAIL
+  if (tri_detail()) tri_detail()->ratio = depth;
+#endif
   if (!(depth >= 0.1)) depth = init_depth;  // `estimated_depth < 0.1` -> INIT_DEPTH (a NaN ratio also falls back)
   return depth;
 }
