@@ -14,7 +14,6 @@ MAX_ITER_TRACE = 16
 MAX_FEAT, MAX_FEAT_WIDE = 150, 384
 MAX_OBS, MAX_OBS_WIDE = MAX_FEAT * NFRAMES, MAX_FEAT_WIDE * NFRAMES
 
-AVM_OK = 0
 AVM_MEM_HOST, AVM_MEM_DEVICE = 0, 1
 # avm_status (include/avm.h)
 AVM_OK, AVM_ERR_INVALID, AVM_ERR_UNSUPPORTED, AVM_ERR_NO_DEVICE, AVM_ERR_HIP, AVM_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
@@ -128,19 +127,7 @@ class SolveSummary(C.Structure):
     ]
 
 
-SUMMARY_DTYPE = np.dtype(
-    [
-        ("termination", np.int32),
-        ("num_iterations", np.int32),
-        ("num_successful", np.int32),
-        ("accept_mask", np.int32),
-        ("initial_cost", np.float64),
-        ("final_cost", np.float64),
-        ("cost_trace", np.float64, (MAX_ITER_TRACE,)),
-        ("radius_trace", np.float64, (MAX_ITER_TRACE,)),
-    ],
-    align=True,
-)
+SUMMARY_DTYPE = np.dtype(SolveSummary)
 
 
 class TdFactorBatch(C.Structure):
@@ -151,8 +138,6 @@ class TdFactorBatch(C.Structure):
 
 def td_factor_batch(arrays: dict, tr: float, row: float, focal_length: float = 460.0):
     """Build an avm_td_factor_batch from host numpy arrays (kept alive on the returned struct)."""
-    import numpy as np
-
     keep = {k: np.ascontiguousarray(np.asarray(v, float)) for k, v in arrays.items()}
     s = TdFactorBatch()
     s.n = keep["inv_depth"].shape[0]
@@ -176,19 +161,28 @@ class FselHorizonIn(C.Structure):
 
 
 def horizon_in(horizon, k_pos, k_quat, k_ba, k1_pos, k1_vel, k1_quat, acc, gyr, nr_imu, delta_imu):
-    """Build an avm_fsel_horizon_in from host numpy arrays (kept alive on the returned struct)."""
-    import numpy as np
-
-    f64 = lambda a, n: np.ascontiguousarray(np.asarray(a, float).reshape(-1, n))
-    arrs = dict(k_pos=f64(k_pos, 3), k_quat=f64(k_quat, 4), k_ba=f64(k_ba, 3), k1_pos=f64(k1_pos, 3), k1_vel=f64(k1_vel, 3),
-                k1_quat=f64(k1_quat, 4), acc=f64(acc, 3), gyr=f64(gyr, 3), delta_imu=np.ascontiguousarray(np.asarray(delta_imu, float).reshape(-1)))
-    nr = np.ascontiguousarray(np.asarray(nr_imu, np.int32).reshape(-1))
+    """Build an avm_fsel_horizon_in from host arrays or from torch tensors, all eleven of one kind (a mix raises).  The converted
+    arrays are kept alive on the returned struct as `_keep`; its `mem` is AVM_MEM_HOST for arrays, AVM_MEM_DEVICE for tensors."""
+    given = dict(k_pos=k_pos, k_quat=k_quat, k_ba=k_ba, k1_pos=k1_pos, k1_vel=k1_vel, k1_quat=k1_quat, acc=acc, gyr=gyr, nr_imu=nr_imu,
+                 delta_imu=delta_imu)
+    tensors = [k for k, a in given.items() if hasattr(a, "data_ptr")]
+    if tensors and len(tensors) != len(given):
+        raise ValueError("horizon_in: host arrays and tensors mixed (tensors: %s)" % ", ".join(tensors))
+    if tensors:
+        import torch
+    cols = dict(k_pos=3, k_quat=4, k_ba=3, k1_pos=3, k1_vel=3, k1_quat=4, acc=3, gyr=3)   # nr_imu and delta_imu are [P]
+    keep = {}
+    for k, a in given.items():
+        shape = (-1, cols[k]) if k in cols else (-1,)
+        if tensors:
+            keep[k] = a.to(torch.int32 if k == "nr_imu" else torch.float64).reshape(shape).contiguous()
+        else:
+            keep[k] = np.ascontiguousarray(np.asarray(a, np.int32 if k == "nr_imu" else float).reshape(shape))
     s = FselHorizonIn()
-    s.n_problems, s.horizon = arrs["k_pos"].shape[0], int(horizon)
-    for k, v in arrs.items():
-        setattr(s, k, dptr(v))
-    s.nr_imu = iptr(nr)
-    s._keep = (arrs, nr)
+    s.n_problems, s.horizon = keep["k_pos"].shape[0], int(horizon)
+    for k, v in keep.items():
+        setattr(s, k, iptr(v) if k == "nr_imu" else dptr(v))
+    s._keep, s.mem = keep, AVM_MEM_DEVICE if tensors else AVM_MEM_HOST
     return s
 
 
@@ -264,17 +258,6 @@ class Config(C.Structure):
     ]
 
 
-# The entry points of a batch of streams (include/avm.h; lib.py sets these argtypes): per-window marginalization flags through the solve and
-# the roll, the keyframe decision, the failure detection.  ctx is a void pointer, avm_mem an int.
-PROTOTYPES = {
-    "avm_window_solve_batch_flags": [C.c_void_p, C.POINTER(Options), C.c_int, C.POINTER(WindowBatch), c_ip, C.POINTER(PriorOut),
-                                     C.POINTER(SolveSummary)],
-    "avm_slide_window_flags": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.c_int32, C.c_double, C.c_int32],
-    "avm_keyframe_decision_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.c_double, c_ip, c_ip, c_dp],
-    "avm_failure_detection_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_dp, c_ip],
-}
-
-
 MAX_IMAGE_PTS = 1024  # AVM_MAX_IMAGE_PTS
 
 
@@ -283,27 +266,9 @@ class ImageBatch(C.Structure):
     _fields_ = [("n_windows", C.c_int32), ("max_pts", C.c_int32), ("n_pts", c_ip), ("feature_id", c_ip), ("xy", c_dp), ("vel_td", c_dp)]
 
 
-# The feature manager on device-resident tables (include/avm.h): the image's append by feature id, the IMU buffer, the solve's view of
-# the whole list and setDepth, the roll with ids.  A dict of its own: PROTOTYPES keeps its keys.  lib.py applies both the same way.
-TRACK_PROTOTYPES = {
-    "avm_add_image_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.POINTER(ImageBatch), C.c_double, c_ip, c_ip, c_dp],
-    "avm_imu_push_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.c_int32, c_dp, c_dp, c_dp],
-    "avm_solve_view_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(WindowBatch), c_ip],
-    "avm_solve_view_store_depths": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(WindowBatch), c_ip],
-    "avm_slide_window_tracks": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, c_ip, C.c_int32, C.c_double, C.c_int32],
-}
-
-
 class SelectState(C.Structure):
     """avm_select_state (include/avm.h): the members of FeatureSelector that outlive a call, one row per stream."""
     _fields_ = [("max_tracked", C.c_int32), ("last_feature_id", c_ip), ("n_tracked", c_ip), ("tracked_id", c_ip), ("first_image", c_ip)]
-
-
-# FeatureSelector::select() on device-resident images (include/avm.h).  A dict of its own again; lib.py applies it like the other two.
-SELECT_PROTOTYPES = {
-    "avm_fsel_select_image_batch": [C.c_void_p, C.c_int, C.POINTER(ImageBatch), c_dp, c_ip, C.c_int32, C.c_int32, C.POINTER(SelectState),
-                                    C.POINTER(FselBatch), C.POINTER(FselOut), C.POINTER(ImageBatch)],
-}
 
 
 class ReloMsgBatch(C.Structure):
@@ -320,21 +285,97 @@ class ReloState(C.Structure):
                 ("relo_relative_yaw", c_dp)]
 
 
-# Relocalization and the prior hand-over in the stream loop (include/avm.h).  A dict of its own once more; lib.py applies it like the others.
-RELO_PROTOTYPES = {
-    "avm_headers_step_batch": [C.c_void_p, C.c_int, C.c_int32, c_dp, c_ip, c_dp],
-    "avm_set_relo_frame_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_dp, C.POINTER(ReloMsgBatch), C.POINTER(ReloState)],
-    "avm_relo_resolve_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), c_ip, C.c_int32, c_ip, C.POINTER(ReloState), c_ip, c_ip, c_ip, c_dp,
-                               C.POINTER(C.c_int32)],
-    "avm_relo_finish_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(ReloState)],
-    "avm_prior_keep_batch": [C.c_void_p, C.c_int, C.POINTER(WindowBatch), C.POINTER(PriorOut)],
-}
+def pointer_members(struct):
+    """(names of the double* members, names of the int32_t* members) of a struct type, in declaration order."""
+    return [k for k, t in struct._fields_ if t is c_dp], [k for k, t in struct._fields_ if t is c_ip]
 
-# The solve of a batch of which some streams relocalize (include/avm.h): the _flags call with relo_active behind the flags.  A dict of its
-# own, like the others.
-SPLIT_PROTOTYPES = {
-    "avm_window_solve_batch_relo": [C.c_void_p, C.POINTER(Options), C.c_int, C.POINTER(WindowBatch), c_ip, c_ip, C.POINTER(PriorOut),
-                                    C.POINTER(SolveSummary)],
+
+# Every function the package binds: name -> (restype, argtypes); lib.py applies the table in one loop.  The 51 declarations of
+# include/avm.h under the header's own headings, then the avm_debug_* hooks (csrc/api/debug.hpp).  avm_ctx* is a void pointer,
+# avm_mem an int; restype None is ctypes' void.
+_vp, _int, _i32, _f64, _P = C.c_void_p, C.c_int, C.c_int32, C.c_double, C.POINTER
+_opt, _win, _prior, _summ, _fsel, _img, _rs = _P(Options), _P(WindowBatch), _P(PriorOut), _P(SolveSummary), _P(FselBatch), _P(ImageBatch), _P(ReloState)
+_ints, _i64s = _P(C.c_int), _P(C.c_int64)
+PROTOTYPES = {
+    # lifecycle
+    "avm_default_options": (_int, [_opt]),
+    "avm_create": (_int, [_P(Config), _P(_vp)]),
+    "avm_destroy": (None, [_vp]),
+    "avm_last_error": (C.c_char_p, [_vp]),
+    "avm_version": (C.c_char_p, []),
+    "avm_abi_version": (_int, []),
+    # HP-A: Estimator::optimization() for a batch of independent windows, and the steps around it
+    "avm_window_solve_batch": (_int, [_vp, _opt, _int, _win, _prior, _summ]),
+    "avm_window_solve_batch_flags": (_int, [_vp, _opt, _int, _win, c_ip, _prior, _summ]),
+    "avm_window_solve_batch_relo": (_int, [_vp, _opt, _int, _win, c_ip, c_ip, _prior, _summ]),
+    "avm_window_solve": (_int, [_vp, _opt, _int, _win, _prior, _summ]),
+    "avm_imu_preintegrate_batch": (_int, [_vp, _opt, _int, _win] + [c_dp] * 4),
+    "avm_triangulate_batch": (_int, [_vp, _int, _win, _f64]),
+    "avm_imu_propagate_batch": (_int, [_vp, _int, _win, c_dp]),
+    "avm_fsel_horizon_imu": (_int, [_vp, _int, _P(FselHorizonIn), c_dp, c_dp]),
+    "avm_projection_td_eval": (_int, [_vp, _int, _P(TdFactorBatch), c_dp, c_dp]),
+    "avm_fsel_build_cloud": (_int, [_vp, _int, _win, c_dp, c_dp, _i32, c_ip, c_dp, c_dp]),
+    "avm_slide_window": (_int, [_vp, _int, _win, _i32, _i32, _f64]),
+    "avm_slide_window_flags": (_int, [_vp, _int, _win, c_ip, _i32, _f64, _i32]),
+    "avm_keyframe_decision_batch": (_int, [_vp, _int, _win, _f64, c_ip, c_ip, c_dp]),
+    "avm_failure_detection_batch": (_int, [_vp, _int, _win, c_dp, c_ip]),
+    # the feature manager on device-resident tables
+    "avm_add_image_batch": (_int, [_vp, _int, _win, c_ip, _img, _f64, c_ip, c_ip, c_dp]),
+    "avm_imu_push_batch": (_int, [_vp, _int, _win, c_ip, _i32, c_dp, c_dp, c_dp]),
+    "avm_solve_view_batch": (_int, [_vp, _int, _win, _win, c_ip]),
+    "avm_solve_view_store_depths": (_int, [_vp, _int, _win, _win, c_ip]),
+    "avm_slide_window_tracks": (_int, [_vp, _int, _win, c_ip, c_ip, _i32, _f64, _i32]),
+    # the selector in the stream loop
+    "avm_fsel_select_image_batch": (_int, [_vp, _int, _img, c_dp, c_ip, _i32, _i32, _P(SelectState), _fsel, _P(FselOut), _img]),
+    # relocalization and the prior hand-over in the stream loop
+    "avm_headers_step_batch": (_int, [_vp, _int, _i32, c_dp, c_ip, c_dp]),
+    "avm_set_relo_frame_batch": (_int, [_vp, _int, _win, c_dp, _P(ReloMsgBatch), _rs]),
+    "avm_relo_resolve_batch": (_int, [_vp, _int, _win, c_ip, _i32, c_ip, _rs, c_ip, c_ip, c_ip, c_dp, _P(_i32)]),
+    "avm_relo_finish_batch": (_int, [_vp, _int, _win, _rs]),
+    "avm_prior_keep_batch": (_int, [_vp, _int, _win, _prior]),
+    # Estimator::visualInitialAlign
+    "avm_visual_initial_align_batch": (_int, [_vp, _opt, _int, _P(AlignBatch), _win, _P(AlignOut)]),
+    # host-side format adapters (no ctx), and the per-factor parity surface declared behind them
+    "avm_gt_load_csv": (_vp, [C.c_char_p]),
+    "avm_gt_from_rows": (_vp, [c_dp, _i32]),
+    "avm_gt_free": (None, [_vp]),
+    "avm_gt_size": (_int, [_vp]),
+    "avm_gt_seek": (_int, [_vp]),
+    "avm_fsel_horizon_ground_truth": (_int, [_vp, _i32, _f64, c_dp, c_dp, _f64, c_dp, c_dp]),
+    "avm_image_from_pointcloud": (_int, [_i32, _P(C.c_float), _P(_P(C.c_float)), _i32, c_ip, c_ip, c_dp]),
+    "avm_window_eval_factors": (_int, [_vp, _opt, _int, _win, _int] + [c_dp] * 6),
+    # HP-B: FeatureSelector::select() for a batch of independent frames
+    "avm_fsel_select_batch": (_int, [_vp, _int, _fsel, _P(FselOut)]),
+    "avm_fsel_select": (_int, [_vp, _int, _fsel, c_ip, c_ip, c_dp]),
+    "avm_fsel_fallback_stats": (_int, [_vp, _i64s]),
+    "avm_fsel_nn_depth": (_int, [_vp, _int, _fsel, c_dp]),
+    "avm_fsel_information": (_int, [_vp, _int, _fsel, c_dp, c_dp, c_ip]),
+    # multi-GPU: the library's own communicator
+    "avm_comm_unique_id": (_int, [_vp, _vp]),
+    "avm_comm_init": (_int, [_vp, _i32, _i32, _vp]),
+    "avm_gather_states": (_int, [_vp, c_dp, c_dp, C.c_size_t]),
+    "avm_comm_destroy": (_int, [_vp]),
+    # the ctx stream, and the timing of the last call on it
+    "avm_ctx_stream": (_int, [_vp, _P(_vp)]),
+    "avm_last_kernel_ms": (_int, [_vp, C.c_char_p, _P(C.c_float)]),
+    # test / bench hooks, not in avm.h
+    "avm_debug_copy_sqrt_info": (_int, [_vp, _int, c_dp]),
+    "avm_debug_last_solve_form": (_int, [_vp]),
+    "avm_debug_last_marg_form": (_int, [_vp]),
+    "avm_debug_last_fsel_form": (_int, [_vp]),
+    "avm_debug_last_split": (_int, [_vp, _i64s]),
+    "avm_debug_counters": (_int, [_vp, _i64s]),
+    "avm_debug_preint_cache": (_int, [_vp, _i64s]),
+    "avm_debug_fsel_evaluations": (_int, [_vp, _i64s]),
+    "avm_debug_solve_tp_occupancy": (_int, [_ints]),
+    "avm_debug_solve_tp_list_occupancy": (_int, [_ints]),
+    "avm_debug_solve_pattern": (_int, [_int, _ints]),
+    "avm_debug_solve_tp_pattern": (_int, [_ints]),
+    "avm_debug_table_limits": (_int, [_ints]),
+    "avm_debug_struct_sizes": (_int, [_ints]),
+    "avm_debug_track_struct_sizes": (_int, [_ints]),
+    "avm_debug_relo_struct_sizes": (_int, [_ints]),
+    "avm_debug_align_layout": (_int, [_ints]),
 }
 
 

@@ -10,21 +10,55 @@ import numpy as np
 
 from . import abi
 
-_WINDOW_F64 = [
-    "pose", "speedbias", "ex_pose", "inv_depth", "obs_xy", "imu_dt", "imu_acc", "imu_gyr",
-    "imu_lin_ba", "imu_lin_bg", "prior_J", "prior_r", "prior_x0",
-    "obs_vel_td", "td", "relo_xy", "relo_pose", "last_pose0",   # optional members (absent key -> NULL)
-]
-_WINDOW_I32 = [
-    "n_feat", "feat_start", "feat_nobs", "feat_obs_begin", "imu_n", "prior_n", "prior_nblk",
-    "prior_blk_kind", "prior_blk_frame",
-    "relo_n", "relo_frame", "relo_feat", "failure_occur",       # optional members
-]
+
+def _device(where):
+    """None when `where` - a *Arrays object, or one array - is host memory (numpy), else the torch device it lives on."""
+    first = next(iter(where.a.values())) if hasattr(where, "a") else where
+    return None if isinstance(first, np.ndarray) else first.device
+
+
+def _torch_dtype(dtype):
+    import torch
+
+    return None if dtype is None else torch.int32 if dtype == np.int32 else torch.float64
+
+
+def like(arrays, x, dtype, shape=None):
+    """x contiguous, of `dtype` (np.int32 / np.float64; None: its own), in the memory space of `arrays`: a numpy array beside host
+    arrays, a tensor on their device beside device ones.  shape: asserted when given."""
+    dev = _device(arrays)
+    if dev is None:
+        out = np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x, dtype)
+    else:
+        import torch
+
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype))
+        out = t.to(device=dev, dtype=_torch_dtype(dtype)).contiguous()
+    assert shape is None or tuple(out.shape) == tuple(shape), (tuple(out.shape), tuple(shape))
+    return out
+
+
+def zeros_like_space(arrays, shape, dtype):
+    """zeros of `shape` and `dtype` (np.int32 / np.float64) in the memory space of `arrays`"""
+    dev = _device(arrays)
+    if dev is None:
+        return np.zeros(shape, dtype)
+    import torch
+
+    return torch.zeros(shape, dtype=_torch_dtype(dtype), device=dev)
 
 
 class _Arrays:
+    """A subclass names its struct type as STRUCT; F64 / I32, the keys of `a` that become its double* / int32_t* members (an absent
+    key or a None value: NULL), follow from it.  PER_STREAM: the [B] array that gives n_windows where dims has none."""
+    STRUCT = None
+    PER_STREAM = None
     F64: list = []
     I32: list = []
+
+    def __init_subclass__(cls):
+        if "STRUCT" in cls.__dict__:
+            cls.F64, cls.I32 = abi.pointer_members(cls.STRUCT)
 
     def __init__(self, dims: dict, arrays: dict):
         self.dims = dict(dims)
@@ -32,12 +66,23 @@ class _Arrays:
 
     @property
     def on_device(self) -> bool:
-        first = next(iter(self.a.values()))
-        return not isinstance(first, np.ndarray)
+        return _device(self) is not None
 
     @property
     def mem(self) -> int:
         return abi.AVM_MEM_DEVICE if self.on_device else abi.AVM_MEM_HOST
+
+    @property
+    def n_windows(self) -> int:
+        return self.dims["n_windows"] if "n_windows" in self.dims else self.a[self.PER_STREAM].shape[0]
+
+    def struct(self):
+        return self._fill(self.STRUCT())
+
+    def slice(self, lo: int, hi: int):
+        d = dict(self.dims)
+        d["n_windows"] = hi - lo
+        return type(self)(d, {k: v[lo:hi] for k, v in self.a.items()})
 
     def copy(self):
         if self.on_device:
@@ -70,19 +115,7 @@ class _Arrays:
 class WindowArrays(_Arrays):
     """avm_window_batch: the inputs/outputs of Estimator::optimization() for B windows."""
 
-    F64, I32 = _WINDOW_F64, _WINDOW_I32
-
-    def struct(self) -> abi.WindowBatch:
-        return self._fill(abi.WindowBatch())
-
-    @property
-    def n_windows(self) -> int:
-        return self.dims["n_windows"]
-
-    def slice(self, lo: int, hi: int) -> "WindowArrays":
-        d = dict(self.dims)
-        d["n_windows"] = hi - lo
-        return WindowArrays(d, {k: v[lo:hi] for k, v in self.a.items()})
+    STRUCT = abi.WindowBatch
 
 
 TRACK_KEYS = ("n_feat", "feat_start", "feat_nobs", "feat_obs_begin", "obs_xy", "inv_depth", "obs_vel_td")   # what avm_solve_view_batch writes
@@ -93,14 +126,7 @@ class ImageArrays(_Arrays):
     strictly ascending, xy [B, max_pts, 2] and, with the time offset, vel_td [B, max_pts, 4] (velocity.x, velocity.y, cur_td, uv.y).
     Optionally `prob` [B, max_pts], the fPROB channel: not a member of the struct, the array FeatureSelector.select_stream takes beside it."""
 
-    F64, I32 = ["xy", "vel_td"], ["n_pts", "feature_id"]
-
-    def struct(self) -> abi.ImageBatch:
-        return self._fill(abi.ImageBatch())
-
-    @property
-    def n_windows(self) -> int:
-        return self.dims["n_windows"]
+    STRUCT = abi.ImageBatch
 
     @staticmethod
     def from_maps(images, max_pts: int, with_td: bool = False, prob=None) -> "ImageArrays":
@@ -131,7 +157,7 @@ class SelectorState(_Arrays):
     n_tracked [B] and tracked_id [B, max_tracked] (trackedFeatures_, append order), first_image [B] (firstImage_).  alloc() gives the
     state of freshly constructed selectors; copy / to_device / to_host as every *Arrays."""
 
-    I32 = ["last_feature_id", "n_tracked", "tracked_id", "first_image"]
+    STRUCT, PER_STREAM = abi.SelectState, "n_tracked"
 
     @staticmethod
     def alloc(n_windows: int, max_tracked: int, device=None) -> "SelectorState":
@@ -140,26 +166,12 @@ class SelectorState(_Arrays):
         s = SelectorState({"max_tracked": max_tracked}, a)
         return s.to_device(device) if device else s
 
-    def struct(self) -> abi.SelectState:
-        return self._fill(abi.SelectState())
-
-    @property
-    def n_windows(self) -> int:
-        return self.a["n_tracked"].shape[0]
-
 
 class ReloMsgArrays(_Arrays):
     """avm_relo_msg_batch: the loop-closure message of estimator_node.cpp:274-297, one row per stream - has_msg [B], frame_stamp [B],
     n_match [B], match_id [B, max_match] strictly ascending, match_xy [B, max_match, 2], prev_relo_t [B, 3], prev_relo_q [B, 4] (x y z w)."""
 
-    F64, I32 = ["frame_stamp", "match_xy", "prev_relo_t", "prev_relo_q"], ["has_msg", "n_match", "match_id"]
-
-    def struct(self) -> abi.ReloMsgBatch:
-        return self._fill(abi.ReloMsgBatch())
-
-    @property
-    def n_windows(self) -> int:
-        return self.dims["n_windows"]
+    STRUCT = abi.ReloMsgBatch
 
     @staticmethod
     def from_messages(messages, max_match: int) -> "ReloMsgArrays":
@@ -185,9 +197,7 @@ class ReloState(_Arrays):
     """avm_relo_state: the Estimator members of the relocalization that outlive a call, one row per stream.  alloc() gives the state of
     freshly constructed estimators: no relocalization pending, relo_pose rows (0, 0, 0, 0, 0, 0, 1)."""
 
-    F64 = ["relo_stamp", "match_xy", "prev_relo_t", "prev_relo_q", "relo_pose", "drift_correct_yaw", "drift_correct_t", "relo_relative_t",
-           "relo_relative_q", "relo_relative_yaw"]
-    I32 = ["relocalization_info", "relo_frame", "n_match", "match_id"]
+    STRUCT, PER_STREAM = abi.ReloState, "n_match"
 
     @staticmethod
     def alloc(n_windows: int, max_match: int, device=None) -> "ReloState":
@@ -199,13 +209,6 @@ class ReloState(_Arrays):
              "relo_relative_q": np.tile(unit, (B, 1)), "relo_relative_yaw": np.zeros(B)}
         s = ReloState({"max_match": max_match}, a)
         return s.to_device(device) if device else s
-
-    def struct(self) -> abi.ReloState:
-        return self._fill(abi.ReloState())
-
-    @property
-    def n_windows(self) -> int:
-        return self.a["n_match"].shape[0]
 
 
 PRIOR_KEYS = ("n", "nblk", "blk_kind", "blk_frame", "J", "r", "x0")   # avm_prior_out's arrays; the batch's are prior_<key>
@@ -229,17 +232,9 @@ class TrackTables:
         a = {k: v for k, v in full.a.items() if k not in TRACK_KEYS and not k.startswith("relo_")}
         for k in TRACK_KEYS:
             if k in full.a:
-                a[k] = view_tracks[k] if view_tracks else self._zeros_like(full.a[k], shapes[k])
+                a[k] = view_tracks[k] if view_tracks else zeros_like_space(full, shapes[k], np.int32 if k in WindowArrays.I32 else np.float64)
         self.view = WindowArrays(dims, a)
-        self.view_row = view_row if view_row is not None else self._zeros_like(full.a["n_feat"], (B, max_feat))
-
-    @staticmethod
-    def _zeros_like(x, shape):
-        if isinstance(x, np.ndarray):
-            return np.zeros(shape, x.dtype)
-        import torch
-
-        return torch.zeros(shape, dtype=x.dtype, device=x.device)
+        self.view_row = view_row if view_row is not None else zeros_like_space(full, (B, max_feat), np.int32)
 
     @property
     def on_device(self) -> bool:
@@ -266,17 +261,15 @@ class TrackTables:
         return self._rebuilt((lambda v: v.clone()) if self.on_device else (lambda v: v.copy()), self.full.copy())
 
     def to_device(self, device="cuda:0") -> "TrackTables":
-        import torch
-
-        return self._rebuilt(lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(device) if isinstance(v, np.ndarray) else v.to(device),
-                             self.full.to_device(device))
+        full = self.full.to_device(device)
+        return self._rebuilt(lambda v: like(full, v, None), full)
 
     def to_host(self) -> "TrackTables":
         return self._rebuilt(lambda v: v.copy() if isinstance(v, np.ndarray) else v.cpu().numpy(), self.full.to_host())
 
 
 class PriorOutArrays(_Arrays):
-    F64, I32 = ["J", "r", "x0"], ["n", "nblk", "blk_kind", "blk_frame"]
+    STRUCT = abi.PriorOut
 
     @staticmethod
     def alloc(n_windows: int, max_prior: int = 96, max_pblk: int = 16, device=None) -> "PriorOutArrays":
@@ -297,15 +290,11 @@ class PriorOutArrays(_Arrays):
             a = {k: np.zeros(sh, np.int32 if dt == "i4" else np.float64) for k, (sh, dt) in shapes.items()}
         return PriorOutArrays({"max_prior": max_prior, "max_pblk": max_pblk}, a)
 
-    def struct(self) -> abi.PriorOut:
-        return self._fill(abi.PriorOut())
-
 
 class FselArrays(_Arrays):
     """avm_fsel_batch: the inputs of FeatureSelector::select() for P frames."""
 
-    F64 = ["hor_pos", "hor_quat", "delta_imu", "cand_xy", "cand_prob", "used_xy", "cloud_xy", "cloud_depth"]
-    I32 = ["nr_imu", "n_cand", "cand_id", "n_used", "used_id", "n_cloud"]
+    STRUCT = abi.FselBatch
 
     def __init__(self, dims, arrays, scalars=None):
         super().__init__(dims, arrays)
@@ -322,7 +311,7 @@ class FselArrays(_Arrays):
         return c
 
     def struct(self) -> abi.FselBatch:
-        s = self._fill(abi.FselBatch())
+        s = super().struct()
         for k, v in self.scalars.items():
             if k in ("q_ic", "t_ic"):
                 arr = getattr(s, k)
@@ -338,7 +327,7 @@ class FselArrays(_Arrays):
 
 
 class FselOutArrays(_Arrays):
-    F64, I32 = ["fvalues", "min_gap"], ["n_selected", "selected_ids"]
+    STRUCT = abi.FselOut
 
     @staticmethod
     def alloc(n_problems: int, max_features: int, device=None, want_min_gap: bool = False) -> "FselOutArrays":
@@ -352,31 +341,15 @@ class FselOutArrays(_Arrays):
         o = FselOutArrays({}, a)
         return o.to_device(device) if device else o
 
-    def struct(self) -> abi.FselOut:
-        return self._fill(abi.FselOut())
-
 
 class AlignArrays(_Arrays):
     """avm_align_batch: all_image_frame (SfM poses and raw IMU) of B windows, the inputs of Estimator::visualInitialAlign()."""
 
-    F64 = ["frame_R", "frame_T", "tic", "imu_dt", "imu_acc", "imu_gyr", "imu_lin_ba", "imu_lin_bg"]
-    I32 = ["n_frames", "imu_n", "key_index"]
-
-    def struct(self) -> abi.AlignBatch:
-        return self._fill(abi.AlignBatch())
-
-    @property
-    def n_windows(self) -> int:
-        return self.dims["n_windows"]
-
-    def slice(self, lo: int, hi: int) -> "AlignArrays":
-        d = dict(self.dims)
-        d["n_windows"] = hi - lo
-        return AlignArrays(d, {k: v[lo:hi] for k, v in self.a.items()})
+    STRUCT = abi.AlignBatch
 
 
 class AlignOutArrays(_Arrays):
-    F64, I32 = ["delta_bg", "g_c0", "x", "g_world", "deltas"], ["ok"]
+    STRUCT = abi.AlignOut
 
     @staticmethod
     def alloc(n_windows: int, max_frames: int, device=None, want_deltas: bool = True) -> "AlignOutArrays":
@@ -386,9 +359,6 @@ class AlignOutArrays(_Arrays):
             a["deltas"] = np.zeros((n_windows, max_frames - 1, 10))
         o = AlignOutArrays({}, a)
         return o.to_device(device) if device else o
-
-    def struct(self) -> abi.AlignOut:
-        return self._fill(abi.AlignOut())
 
 
 class SfmArrays(_Arrays):
@@ -401,15 +371,6 @@ class SfmArrays(_Arrays):
 
     F64 = ["relative_R", "relative_T", "frame_pt_xy"]
     I32 = ["l", "n_frames", "key_index", "frame_n_pts", "frame_pt_id"]
-
-    @property
-    def n_windows(self) -> int:
-        return self.dims["n_windows"]
-
-    def slice(self, lo: int, hi: int) -> "SfmArrays":
-        d = dict(self.dims)
-        d["n_windows"] = hi - lo
-        return SfmArrays(d, {k: v[lo:hi] for k, v in self.a.items()})
 
 
 def summary_alloc(n_windows: int, device=None):

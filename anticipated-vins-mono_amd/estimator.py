@@ -34,28 +34,24 @@ class Estimator:
         `relo_active`: [B] int32 where the windows live, != 0 for the windows with a relocalization pending
         (avm_window_solve_batch_relo: the others are solved as if the batch had no relocalization arrays and their relo_pose rows stay
         as they are); True: the table resolve_relo(split=True) remembered on the windows.  None: the calls as they always were."""
-        L = self.ctx._L
         B = windows.n_windows
         s = windows.struct()
-        dev = "cuda:%d" % self.ctx.device if windows.on_device else None
+        dev = self.ctx.device_str if windows.on_device else None
         summ = (summary_out if summary_out is not None else buffers.summary_alloc(B, dev)) if want_summary else None
         prior = None
         if marginalization_flags is not None or self.options.marginalization_flag != abi.MARGIN_NONE:
             prior = prior_out or buffers.PriorOutArrays.alloc(B, windows.dims["max_prior"], windows.dims["max_pblk"], dev)
         po = prior.struct() if prior is not None else None
-        args = (C.byref(po) if po is not None else None, buffers.summary_ptr(summ) if summ is not None else None)
+        head = (C.byref(self.options), windows.mem, C.byref(s))
+        tail = (C.byref(po) if po is not None else None, buffers.summary_ptr(summ) if summ is not None else None)
+        flags = None if marginalization_flags is None else self._flags(windows, marginalization_flags)
         if relo_active is not None:
-            active = self._flags_like(windows, windows._relo_active if relo_active is True else relo_active)
-            flags = None if marginalization_flags is None else self._flags_like(windows, marginalization_flags)
-            rc = L.avm_window_solve_batch_relo(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), abi.iptr(flags), abi.iptr(active), *args)
-            self.ctx.check(rc, "avm_window_solve_batch_relo")
-        elif marginalization_flags is None:
-            rc = L.avm_window_solve_batch(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), *args)
-            self.ctx.check(rc, "avm_window_solve_batch")
+            active = self._flags(windows, windows._relo_active if relo_active is True else relo_active)
+            self.ctx.call("avm_window_solve_batch_relo", *head, abi.iptr(flags), abi.iptr(active), *tail)
+        elif flags is None:
+            self.ctx.call("avm_window_solve_batch", *head, *tail)
         else:
-            flags = self._flags_like(windows, marginalization_flags)
-            rc = L.avm_window_solve_batch_flags(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), abi.iptr(flags), *args)
-            self.ctx.check(rc, "avm_window_solve_batch_flags")
+            self.ctx.call("avm_window_solve_batch_flags", *head, abi.iptr(flags), *tail)
         self.last_summary = summ
         if prior is not None and (marginalization_flags is not None or self.options.marginalization_flag == abi.MARGIN_SECOND_NEW):
             if windows.on_device and prior.on_device:
@@ -65,56 +61,34 @@ class Estimator:
         self.last_marginalization_info = prior
         return summ
 
-    def _flags_like(self, windows, flags):
+    @staticmethod
+    def _flags(windows, flags):
         """[B] int32 flags in the memory space of `windows`: a host array for host windows, a device tensor for device ones."""
-        if windows.on_device:
-            import torch
+        return buffers.like(windows, flags, np.int32, (windows.n_windows,))
 
-            if isinstance(flags, torch.Tensor):
-                t = flags.to(device="cuda:%d" % self.ctx.device, dtype=torch.int32).contiguous()
-            else:
-                t = torch.from_numpy(np.ascontiguousarray(flags, np.int32)).to("cuda:%d" % self.ctx.device)
-            assert t.shape == (windows.n_windows,)
-            return t
-        a = np.ascontiguousarray(flags.cpu().numpy() if hasattr(flags, "cpu") else flags, np.int32)
-        assert a.shape == (windows.n_windows,)
-        return a
-
-    def _out_like(self, windows, shape, dtype):
-        if windows.on_device:
-            import torch
-
-            return torch.zeros(shape, dtype=torch.int32 if dtype == np.int32 else torch.float64, device="cuda:%d" % self.ctx.device)
-        return np.zeros(shape, dtype)
+    @staticmethod
+    def _decision_out(windows):
+        """the outputs of the keyframe decision where the windows live: marginalization_flags [B], last_track_num [B], parallax [B, 2]"""
+        B = windows.n_windows
+        return tuple(buffers.zeros_like_space(windows, sh, dt) for sh, dt in (((B,), np.int32), ((B,), np.int32), ((B, 2), np.float64)))
 
     def keyframe_decision(self, windows: buffers.WindowArrays, min_parallax: float):
         """FeatureManager::addFeatureCheckParallax's verdict (feature_manager.cpp:74-96) for every window, on tables that already hold
         the new image's observations: returns (marginalization_flags [B] int32, last_track_num [B] int32, parallax [B, 2] = sum, num),
         arrays where the windows live.  MARGIN_OLD = keyframe.  min_parallax: MIN_PARALLAX (configured pixels / FOCAL_LENGTH)."""
-        B = windows.n_windows
-        flags, ltn, par = self._out_like(windows, (B,), np.int32), self._out_like(windows, (B,), np.int32), self._out_like(windows, (B, 2), np.float64)
+        flags, ltn, par = self._decision_out(windows)
         s = windows.struct()
-        rc = self.ctx._L.avm_keyframe_decision_batch(self.ctx.h, windows.mem, C.byref(s), float(min_parallax), abi.iptr(flags), abi.iptr(ltn),
-                                                     abi.dptr(par))
-        self.ctx.check(rc, "avm_keyframe_decision_batch")
+        self.ctx.call("avm_keyframe_decision_batch", windows.mem, C.byref(s), float(min_parallax), abi.iptr(flags), abi.iptr(ltn), abi.dptr(par))
         return flags, ltn, par
 
     def failureDetection(self, windows: buffers.WindowArrays, last_P):
         """Estimator::failureDetection (estimator.cpp:612-658) for every window: [B] int32, 0 or the number of the first rule that fired
         (1: |Ba[10]| > 2.5, 2: |Bg[10]| > 1, 3: |P[10] - last_P| > 5, 4: |dP.z| > 1).  last_P: [B, 3] where the windows live."""
         B = windows.n_windows
-        if windows.on_device:
-            import torch
-
-            lp = last_P if isinstance(last_P, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(last_P, np.float64))
-            lp = lp.to(device="cuda:%d" % self.ctx.device, dtype=torch.float64).contiguous()
-        else:
-            lp = np.ascontiguousarray(last_P, np.float64)
-        assert tuple(lp.shape) == (B, 3)
-        failed = self._out_like(windows, (B,), np.int32)
+        lp = buffers.like(windows, last_P, np.float64, (B, 3))
+        failed = buffers.zeros_like_space(windows, (B,), np.int32)
         s = windows.struct()
-        rc = self.ctx._L.avm_failure_detection_batch(self.ctx.h, windows.mem, C.byref(s), abi.dptr(lp), abi.iptr(failed))
-        self.ctx.check(rc, "avm_failure_detection_batch")
+        self.ctx.call("avm_failure_detection_batch", windows.mem, C.byref(s), abi.dptr(lp), abi.iptr(failed))
         return failed
 
     @staticmethod
@@ -144,18 +118,16 @@ class Estimator:
         batch's prior_* tables), in place.  Afterwards `prior` can always be chained: TrackTables.swap_prior(prior) is the hand-over."""
         assert prior.on_device == windows.on_device
         s, po = windows.struct(), prior.struct()
-        self.ctx.check(self.ctx._L.avm_prior_keep_batch(self.ctx.h, windows.mem, C.byref(s), C.byref(po)), "avm_prior_keep_batch")
+        self.ctx.call("avm_prior_keep_batch", windows.mem, C.byref(s), C.byref(po))
 
     def headers_step(self, windows: buffers.WindowArrays, stamp, marginalization_flags=None, new_stamp=None):
         """The frame stamps Headers[i].stamp of B streams, stamp [B, 11] where the windows live, in place: slideWindow's moves for the
         flags (estimator.cpp:1015,1021,1064) - call it behind the roll -, then Headers[10] = new_stamp (:126) - on the next image."""
         B = windows.n_windows
         assert tuple(stamp.shape) == (B, abi.NFRAMES)
-        flags = None if marginalization_flags is None else self._flags_like(windows, marginalization_flags)
-        new = None if new_stamp is None else self._like(windows, new_stamp, np.float64)
-        assert new is None or tuple(new.shape) == (B,)
-        rc = self.ctx._L.avm_headers_step_batch(self.ctx.h, windows.mem, B, abi.dptr(stamp), abi.iptr(flags), abi.dptr(new))
-        self.ctx.check(rc, "avm_headers_step_batch")
+        flags = None if marginalization_flags is None else self._flags(windows, marginalization_flags)
+        new = None if new_stamp is None else buffers.like(windows, new_stamp, np.float64, (B,))
+        self.ctx.call("avm_headers_step_batch", windows.mem, B, abi.dptr(stamp), abi.iptr(flags), abi.dptr(new))
 
     # the reference's name
     def setReloFrame(self, windows: buffers.WindowArrays, stamp, msg: buffers.ReloMsgArrays, state: buffers.ReloState):
@@ -163,8 +135,7 @@ class Estimator:
         0 .. WINDOW_SIZE - 1 whose stamp equals frame_stamp (the last one) makes the relocalization pending, relo_pose = its pose."""
         assert msg.on_device == windows.on_device == state.on_device and tuple(stamp.shape) == (windows.n_windows, abi.NFRAMES)
         s, sm, ss = windows.struct(), msg.struct(), state.struct()
-        rc = self.ctx._L.avm_set_relo_frame_batch(self.ctx.h, windows.mem, C.byref(s), abi.dptr(stamp), C.byref(sm), C.byref(ss))
-        self.ctx.check(rc, "avm_set_relo_frame_batch")
+        self.ctx.call("avm_set_relo_frame_batch", windows.mem, C.byref(s), abi.dptr(stamp), C.byref(sm), C.byref(ss))
 
     def resolve_relo(self, tables: buffers.TrackTables, state: buffers.ReloState, split: bool = False) -> int:
         """The match loop of optimization() (estimator.cpp:765-790) on tables.view (behind solve_view()): with a relocalization pending
@@ -177,14 +148,13 @@ class Estimator:
         B, mf = v.n_windows, v.dims["max_feat"]
         out = getattr(tables, "_relo_out", None)
         if out is None:
-            out = tables._relo_out = {"relo_n": self._out_like(v, (B,), np.int32), "relo_frame": self._out_like(v, (B,), np.int32),
-                                      "relo_feat": self._out_like(v, (B, mf), np.int32), "relo_xy": self._out_like(v, (B, mf, 2), np.float64)}
+            shapes = {"relo_n": ((B,), np.int32), "relo_frame": ((B,), np.int32), "relo_feat": ((B, mf), np.int32), "relo_xy": ((B, mf, 2), np.float64)}
+            out = tables._relo_out = {k: buffers.zeros_like_space(v, sh, dt) for k, (sh, dt) in shapes.items()}
         n_active = C.c_int32(0)
         s, ss = v.struct(), state.struct()
-        rc = self.ctx._L.avm_relo_resolve_batch(self.ctx.h, v.mem, C.byref(s), abi.iptr(tables.feat_id), int(tables.full.dims["max_feat"]),
-                                                abi.iptr(tables.view_row), C.byref(ss), abi.iptr(out["relo_n"]), abi.iptr(out["relo_frame"]),
-                                                abi.iptr(out["relo_feat"]), abi.dptr(out["relo_xy"]), C.byref(n_active))
-        self.ctx.check(rc, "avm_relo_resolve_batch")
+        self.ctx.call("avm_relo_resolve_batch", v.mem, C.byref(s), abi.iptr(tables.feat_id), int(tables.full.dims["max_feat"]),
+                      abi.iptr(tables.view_row), C.byref(ss), abi.iptr(out["relo_n"]), abi.iptr(out["relo_frame"]), abi.iptr(out["relo_feat"]),
+                      abi.dptr(out["relo_xy"]), C.byref(n_active))
         for k in ("relo_n", "relo_frame", "relo_feat", "relo_xy", "relo_pose"):
             v.a.pop(k, None)
         v._relo_active = state.a["relocalization_info"] if split else None
@@ -197,7 +167,7 @@ class Estimator:
         """The outputs of double2vector() (estimator.cpp:588-604) behind optimization(): drift_correct_yaw / _t and relo_relative_t / _q /
         _yaw of every window with a relocalization pending, whose relocalization_info then returns to 0."""
         s, ss = windows.struct(), state.struct()
-        self.ctx.check(self.ctx._L.avm_relo_finish_batch(self.ctx.h, windows.mem, C.byref(s), C.byref(ss)), "avm_relo_finish_batch")
+        self.ctx.call("avm_relo_finish_batch", windows.mem, C.byref(s), C.byref(ss))
 
     # the reference's name
     def visualInitialAlign(self, align: buffers.AlignArrays, windows: buffers.WindowArrays = None, out: buffers.AlignOutArrays = None):
@@ -205,13 +175,11 @@ class Estimator:
         (initial_aligment.cpp:199-207).  With windows: pose, velocities, gyro biases and inverse depths are set in place; a window
         whose `ok` is 0 keeps them, except for the bias increment.  Returns the AlignOutArrays (ok, delta_bg, g_c0, x, g_world,
         deltas).  Before the first optimization() call reset_linearization_biases(windows)."""
-        dev = "cuda:%d" % self.ctx.device if align.on_device else None
-        out = out or buffers.AlignOutArrays.alloc(align.n_windows, align.dims["max_frames"], dev)
+        out = out or buffers.AlignOutArrays.alloc(align.n_windows, align.dims["max_frames"], self.ctx.device_str if align.on_device else None)
         sa, so = align.struct(), out.struct()
         sw = windows.struct() if windows is not None else None
-        rc = self.ctx._L.avm_visual_initial_align_batch(self.ctx.h, C.byref(self.options), align.mem, C.byref(sa),
-                                                        C.byref(sw) if sw is not None else None, C.byref(so))
-        self.ctx.check(rc, "avm_visual_initial_align_batch")
+        self.ctx.call("avm_visual_initial_align_batch", C.byref(self.options), align.mem, C.byref(sa), C.byref(sw) if sw is not None else None,
+                      C.byref(so))
         return out
 
     @staticmethod
@@ -225,44 +193,32 @@ class Estimator:
         """FeatureManager::triangulate (feature_manager.cpp:202-257), the step before optimization() in solveOdometry():
         features whose inverse depth is <= 0 get 1 / depth from the multi-view linear triangulation, in place."""
         s = windows.struct()
-        rc = self.ctx._L.avm_triangulate_batch(self.ctx.h, windows.mem, C.byref(s), float(init_depth))
-        self.ctx.check(rc, "avm_triangulate_batch")
+        self.ctx.call("avm_triangulate_batch", windows.mem, C.byref(s), float(init_depth))
 
     def projection_td_eval(self, arrays: dict, tr: float, row: float, focal_length: float = 460.0):
         """ProjectionTdFactor::Evaluate (projection_td_factor.cpp:34-141) for n factors given as host arrays
         (abi.td_factor_batch): returns residual [n, 2] and Jacobian [n, 2, 20] (pose_i 6 | pose_j 6 | ex 6 | lambda | td)."""
         f = abi.td_factor_batch(arrays, tr, row, focal_length)
         r, J = np.zeros((f.n, 2)), np.zeros((f.n, 2, 20))
-        rc = self.ctx._L.avm_projection_td_eval(self.ctx.h, abi.AVM_MEM_HOST, C.byref(f), abi.dptr(r), abi.dptr(J))
-        self.ctx.check(rc, "avm_projection_td_eval")
+        self.ctx.call("avm_projection_td_eval", abi.AVM_MEM_HOST, C.byref(f), abi.dptr(r), abi.dptr(J))
         return r, J
 
     def imu_propagate(self, windows: buffers.WindowArrays):
         """Estimator::processIMU's dead-reckoning of the newest frame (estimator.cpp:100-107), in place."""
         s = windows.struct()
         g = (C.c_double * 3)(*[float(x) for x in self.options.g])
-        rc = self.ctx._L.avm_imu_propagate_batch(self.ctx.h, windows.mem, C.byref(s), g)
-        self.ctx.check(rc, "avm_imu_propagate_batch")
-
-    def _like(self, windows, x, dtype):
-        """x as a contiguous array of `dtype` in the memory space of `windows`"""
-        if windows.on_device:
-            import torch
-
-            td = torch.int32 if dtype == np.int32 else torch.float64
-            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype))
-            return t.to(device="cuda:%d" % self.ctx.device, dtype=td).contiguous()
-        return np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x, dtype)
+        self.ctx.call("avm_imu_propagate_batch", windows.mem, C.byref(s), g)
 
     def push_imu(self, windows: buffers.WindowArrays, n, dt, acc, gyr):
         """The buffer half of Estimator::processIMU (estimator.cpp:92-98) for the samples between two images: n [B] samples per window,
         dt [B, max_in], acc / gyr [B, max_in, 3], appended to interval WINDOW_SIZE - 1 in place.  imu_propagate() is the other half."""
-        n, dt, acc, gyr = self._like(windows, n, np.int32), self._like(windows, dt, np.float64), self._like(windows, acc, np.float64), self._like(windows, gyr, np.float64)
+        dt = buffers.like(windows, dt, np.float64)
         B, max_in = windows.n_windows, int(dt.shape[1])
-        assert tuple(n.shape) == (B,) and tuple(dt.shape) == (B, max_in) and tuple(acc.shape) == tuple(gyr.shape) == (B, max_in, 3)
+        assert tuple(dt.shape) == (B, max_in)
+        n = buffers.like(windows, n, np.int32, (B,))
+        acc, gyr = buffers.like(windows, acc, np.float64, (B, max_in, 3)), buffers.like(windows, gyr, np.float64, (B, max_in, 3))
         s = windows.struct()
-        rc = self.ctx._L.avm_imu_push_batch(self.ctx.h, windows.mem, C.byref(s), abi.iptr(n), max_in, abi.dptr(dt), abi.dptr(acc), abi.dptr(gyr))
-        self.ctx.check(rc, "avm_imu_push_batch")
+        self.ctx.call("avm_imu_push_batch", windows.mem, C.byref(s), abi.iptr(n), max_in, abi.dptr(dt), abi.dptr(acc), abi.dptr(gyr))
 
     # the reference's name
     def addFeatureCheckParallax(self, full: buffers.WindowArrays, feat_id, image: buffers.ImageArrays, min_parallax: float):
@@ -270,20 +226,18 @@ class Estimator:
         to the track of its id in feat_id [B, max_feat] or starts a new row, the observation table is rewritten dense in list order.
         Returns keyframe_decision()'s (marginalization_flags, last_track_num, parallax) on the result."""
         B = full.n_windows
-        assert image.n_windows == B and image.on_device == full.on_device and tuple(feat_id.shape) == (B, full.dims["max_feat"])
-        flags, ltn, par = self._out_like(full, (B,), np.int32), self._out_like(full, (B,), np.int32), self._out_like(full, (B, 2), np.float64)
+        assert image.on_device == full.on_device and tuple(feat_id.shape) == (B, full.dims["max_feat"])   # (n_windows: the library refuses it)
+        flags, ltn, par = self._decision_out(full)
         s, si = full.struct(), image.struct()
-        rc = self.ctx._L.avm_add_image_batch(self.ctx.h, full.mem, C.byref(s), abi.iptr(feat_id), C.byref(si), float(min_parallax), abi.iptr(flags),
-                                             abi.iptr(ltn), abi.dptr(par))
-        self.ctx.check(rc, "avm_add_image_batch")
+        self.ctx.call("avm_add_image_batch", full.mem, C.byref(s), abi.iptr(feat_id), C.byref(si), float(min_parallax), abi.iptr(flags),
+                      abi.iptr(ltn), abi.dptr(par))
         return flags, ltn, par
 
     def solve_view(self, tables: buffers.TrackTables) -> buffers.WindowArrays:
         """The rows of tables.full that pass used_num >= 2 && start_frame < WINDOW_SIZE - 2 (estimator.cpp:715), gathered into
         tables.view (and tables.view_row): what triangulate() and optimization() take.  Returns tables.view."""
         sf, sv = tables.full.struct(), tables.view.struct()
-        rc = self.ctx._L.avm_solve_view_batch(self.ctx.h, tables.full.mem, C.byref(sf), C.byref(sv), abi.iptr(tables.view_row))
-        self.ctx.check(rc, "avm_solve_view_batch")
+        self.ctx.call("avm_solve_view_batch", tables.full.mem, C.byref(sf), C.byref(sv), abi.iptr(tables.view_row))
         return tables.view
 
     # the reference's name
@@ -291,8 +245,7 @@ class Estimator:
         """FeatureManager::setDepth's copy (feature_manager.cpp:141-159): the inverse depths of tables.view back into the rows of
         tables.full they came from."""
         sf, sv = tables.full.struct(), tables.view.struct()
-        rc = self.ctx._L.avm_solve_view_store_depths(self.ctx.h, tables.full.mem, C.byref(sf), C.byref(sv), abi.iptr(tables.view_row))
-        self.ctx.check(rc, "avm_solve_view_store_depths")
+        self.ctx.call("avm_solve_view_store_depths", tables.full.mem, C.byref(sf), C.byref(sv), abi.iptr(tables.view_row))
 
     def slideWindow(self, windows: buffers.WindowArrays, marginalization_flag=None, shift_depth=True, init_depth=5.0, remove_failures=False,
                     feat_id=None):
@@ -303,21 +256,16 @@ class Estimator:
         the windows live): the ids of the rows, compacted with them; the rows of obs_vel_td then move with their observations."""
         flag = self.options.marginalization_flag if marginalization_flag is None else marginalization_flag
         s = windows.struct()
+        if feat_id is None and np.ndim(flag) == 0 and not remove_failures:
+            self.ctx.call("avm_slide_window", windows.mem, C.byref(s), int(flag), int(bool(shift_depth)), float(init_depth))
+            return
+        flags = self._flags(windows, np.full(windows.n_windows, int(flag), np.int32) if np.ndim(flag) == 0 else flag)
+        tail = (abi.iptr(flags), int(bool(shift_depth)), float(init_depth), int(bool(remove_failures)))
         if feat_id is not None:
             assert tuple(feat_id.shape) == (windows.n_windows, windows.dims["max_feat"])
-            flags = self._flags_like(windows, np.full(windows.n_windows, int(flag), np.int32) if np.ndim(flag) == 0 else flag)
-            rc = self.ctx._L.avm_slide_window_tracks(self.ctx.h, windows.mem, C.byref(s), abi.iptr(feat_id), abi.iptr(flags), int(bool(shift_depth)),
-                                                     float(init_depth), int(bool(remove_failures)))
-            self.ctx.check(rc, "avm_slide_window_tracks")
-            return
-        if np.ndim(flag) == 0 and not remove_failures:
-            rc = self.ctx._L.avm_slide_window(self.ctx.h, windows.mem, C.byref(s), int(flag), int(bool(shift_depth)), float(init_depth))
-            self.ctx.check(rc, "avm_slide_window")
-            return
-        flags = self._flags_like(windows, np.full(windows.n_windows, int(flag), np.int32) if np.ndim(flag) == 0 else flag)
-        rc = self.ctx._L.avm_slide_window_flags(self.ctx.h, windows.mem, C.byref(s), abi.iptr(flags), int(bool(shift_depth)), float(init_depth),
-                                                int(bool(remove_failures)))
-        self.ctx.check(rc, "avm_slide_window_flags")
+            self.ctx.call("avm_slide_window_tracks", windows.mem, C.byref(s), abi.iptr(feat_id), *tail)
+        else:
+            self.ctx.call("avm_slide_window_flags", windows.mem, C.byref(s), *tail)
 
     def preintegrate(self, windows: buffers.WindowArrays):
         """IntegrationBase for every interval: returns delta [B,10,10], jacobian, covariance [B,10,15,15], sum_dt [B,10]."""
@@ -325,14 +273,12 @@ class Estimator:
         B = windows.n_windows
         d, j, cv, sd = np.zeros((B, 10, 10)), np.zeros((B, 10, 15, 15)), np.zeros((B, 10, 15, 15)), np.zeros((B, 10))
         s = windows.struct()
-        rc = self.ctx._L.avm_imu_preintegrate_batch(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s),
-                                                    abi.dptr(d), abi.dptr(j), abi.dptr(cv), abi.dptr(sd))
-        self.ctx.check(rc, "avm_imu_preintegrate_batch")
+        self.ctx.call("avm_imu_preintegrate_batch", C.byref(self.options), windows.mem, C.byref(s), abi.dptr(d), abi.dptr(j), abi.dptr(cv), abi.dptr(sd))
         return d, j, cv, sd
 
     def sqrt_info(self, n_windows: int):
         out = np.zeros((n_windows, 10, 15, 15))
-        self.ctx.check(self.ctx._L.avm_debug_copy_sqrt_info(self.ctx.h, n_windows, abi.dptr(out)), "avm_debug_copy_sqrt_info")
+        self.ctx.call("avm_debug_copy_sqrt_info", n_windows, abi.dptr(out))
         return out
 
     def eval_factors(self, windows: buffers.WindowArrays, apply_loss: bool = False):
@@ -341,7 +287,6 @@ class Estimator:
         out = dict(proj_r=np.zeros((B, mo, 2)), proj_J=np.zeros((B, mo, 2, 13)), imu_r=np.zeros((B, 10, 15)),
                    imu_J=np.zeros((B, 10, 15, 30)), prior_res=np.zeros((B, mp)), cost=np.zeros(B))
         s = windows.struct()
-        rc = self.ctx._L.avm_window_eval_factors(self.ctx.h, C.byref(self.options), windows.mem, C.byref(s), int(apply_loss),
-                                                 *[abi.dptr(out[k]) for k in ("proj_r", "proj_J", "imu_r", "imu_J", "prior_res", "cost")])
-        self.ctx.check(rc, "avm_window_eval_factors")
+        self.ctx.call("avm_window_eval_factors", C.byref(self.options), windows.mem, C.byref(s), int(apply_loss),
+                      *[abi.dptr(out[k]) for k in ("proj_r", "proj_J", "imu_r", "imu_J", "prior_res", "cost")])
         return out

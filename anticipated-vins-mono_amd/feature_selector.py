@@ -26,41 +26,22 @@ class FeatureSelector:
         """Greedy selection for P independent frames. Returns (n_selected[P], ids[P, max_features], fvalues[, min_gap: how firmly every
         round was decided, avm_fsel_out::min_gap])."""
         P, mf = problems.n_problems, problems.dims["max_features"]
-        dev = "cuda:%d" % self.ctx.device if problems.on_device else None
-        out = buffers.FselOutArrays.alloc(P, mf, dev, want_min_gap=want_min_gap)
+        out = buffers.FselOutArrays.alloc(P, mf, self.ctx.device_str if problems.on_device else None, want_min_gap=want_min_gap)
         if not want_fvalues:
             out.a["fvalues"] = None
         s, o = problems.struct(), out.struct()
-        rc = self.ctx._L.avm_fsel_select_batch(self.ctx.h, problems.mem, C.byref(s), C.byref(o))
-        self.ctx.check(rc, "avm_fsel_select_batch")
+        self.ctx.call("avm_fsel_select_batch", problems.mem, C.byref(s), C.byref(o))
         return out
 
     def generateFutureHorizon(self, horizon, k_pos, k_quat, k_ba, k1_pos, k1_vel, k1_quat, acc, gyr, nr_imu, delta_imu):
         """FeatureSelector::generateFutureHorizon in IMU mode = HorizonGenerator::imu (horizon_generator.cpp:25-69) for P
         frames: returns hor_pos [P, H+1, 3], hor_quat [P, H+1, 4] (x y z w), the arrays avm_fsel_batch consumes.  Host arrays give
         host arrays; device tensors (all eleven inputs then) give device tensors, nothing crossing to the host."""
-        if hasattr(k_pos, "data_ptr"):
-            import torch
-
-            f64 = lambda a, n: a.to(torch.float64).reshape(-1, n).contiguous()
-            keep = dict(k_pos=f64(k_pos, 3), k_quat=f64(k_quat, 4), k_ba=f64(k_ba, 3), k1_pos=f64(k1_pos, 3), k1_vel=f64(k1_vel, 3),
-                        k1_quat=f64(k1_quat, 4), acc=f64(acc, 3), gyr=f64(gyr, 3), delta_imu=delta_imu.to(torch.float64).reshape(-1).contiguous())
-            nr = nr_imu.to(torch.int32).reshape(-1).contiguous()
-            s = abi.FselHorizonIn()
-            s.n_problems, s.horizon = keep["k_pos"].shape[0], int(horizon)
-            for k, v in keep.items():
-                setattr(s, k, abi.dptr(v))
-            s.nr_imu = abi.iptr(nr)
-            P, dev = s.n_problems, keep["k_pos"].device
-            hp, hq = torch.zeros((P, horizon + 1, 3), dtype=torch.float64, device=dev), torch.zeros((P, horizon + 1, 4), dtype=torch.float64, device=dev)
-            mem = abi.AVM_MEM_DEVICE
-        else:
-            s = abi.horizon_in(horizon, k_pos, k_quat, k_ba, k1_pos, k1_vel, k1_quat, acc, gyr, nr_imu, delta_imu)
-            P = s.n_problems
-            hp, hq = np.zeros((P, horizon + 1, 3)), np.zeros((P, horizon + 1, 4))
-            mem = abi.AVM_MEM_HOST
-        rc = self.ctx._L.avm_fsel_horizon_imu(self.ctx.h, mem, C.byref(s), abi.dptr(hp), abi.dptr(hq))
-        self.ctx.check(rc, "avm_fsel_horizon_imu")
+        s = abi.horizon_in(horizon, k_pos, k_quat, k_ba, k1_pos, k1_vel, k1_quat, acc, gyr, nr_imu, delta_imu)
+        where = s._keep["k_pos"]
+        hp = buffers.zeros_like_space(where, (s.n_problems, horizon + 1, 3), np.float64)
+        hq = buffers.zeros_like_space(where, (s.n_problems, horizon + 1, 4), np.float64)
+        self.ctx.call("avm_fsel_horizon_imu", s.mem, C.byref(s), abi.dptr(hp), abi.dptr(hq))
         return hp, hq
 
     def initKDTree(self, windows: buffers.WindowArrays, k1_pos, k1_quat, max_cloud: int = 150):
@@ -68,21 +49,12 @@ class FeatureSelector:
         n_cloud [B], cloud_xy [B, max_cloud, 2], cloud_depth [B, max_cloud], where the windows live (host arrays or device tensors;
         k1_pos / k1_quat are taken there too)."""
         B = windows.n_windows
-        if windows.on_device:
-            import torch
-
-            dev = windows.a["pose"].device
-            conv = lambda x: (x if hasattr(x, "data_ptr") else torch.from_numpy(np.ascontiguousarray(x, float))).to(device=dev, dtype=torch.float64).contiguous()
-            kp, kq = conv(k1_pos), conv(k1_quat)
-            n = torch.zeros(B, dtype=torch.int32, device=dev)
-            xy, dep = torch.zeros((B, max_cloud, 2), dtype=torch.float64, device=dev), torch.zeros((B, max_cloud), dtype=torch.float64, device=dev)
-        else:
-            kp, kq = np.ascontiguousarray(k1_pos, float), np.ascontiguousarray(k1_quat, float)
-            n, xy, dep = np.zeros(B, np.int32), np.zeros((B, max_cloud, 2)), np.zeros((B, max_cloud))
+        kp, kq = buffers.like(windows, k1_pos, np.float64), buffers.like(windows, k1_quat, np.float64)
+        n = buffers.zeros_like_space(windows, (B,), np.int32)
+        xy, dep = buffers.zeros_like_space(windows, (B, max_cloud, 2), np.float64), buffers.zeros_like_space(windows, (B, max_cloud), np.float64)
         s = windows.struct()
-        rc = self.ctx._L.avm_fsel_build_cloud(self.ctx.h, windows.mem, C.byref(s), abi.dptr(kp), abi.dptr(kq), int(max_cloud), abi.iptr(n),
-                                              abi.dptr(xy), abi.dptr(dep))
-        self.ctx.check(rc, "avm_fsel_build_cloud")
+        self.ctx.call("avm_fsel_build_cloud", windows.mem, C.byref(s), abi.dptr(kp), abi.dptr(kq), int(max_cloud), abi.iptr(n), abi.dptr(xy),
+                      abi.dptr(dep))
         return n, xy, dep
 
     def select_stream(self, image: buffers.ImageArrays, state: buffers.SelectorState, problem: buffers.FselArrays, initialized=None,
@@ -95,19 +67,17 @@ class FeatureSelector:
         selection's FselOutArrays and the ImageArrays addFeatureCheckParallax takes (allocated with the image's max_pts unless given)."""
         B, mp = image.n_windows, image.dims["max_pts"]
         assert problem.n_problems == B and state.n_windows == B and image.on_device == state.on_device == problem.on_device and "prob" in image.a
-        dev = "cuda:%d" % self.ctx.device if image.on_device else None
+        dev = self.ctx.device_str if image.on_device else None
         out = out or buffers.FselOutArrays.alloc(B, problem.dims["max_features"], dev, want_min_gap=want_min_gap)
         if image_out is None:
-            a = {"n_pts": np.zeros(B, np.int32), "feature_id": np.zeros((B, mp), np.int32), "xy": np.zeros((B, mp, 2))}
+            shapes = {"n_pts": ((B,), np.int32), "feature_id": ((B, mp), np.int32), "xy": ((B, mp, 2), np.float64)}
             if "vel_td" in image.a:
-                a["vel_td"] = np.zeros((B, mp, 4))
-            image_out = buffers.ImageArrays({"n_windows": B, "max_pts": mp}, a)
-            image_out = image_out.to_device(dev) if dev else image_out
+                shapes["vel_td"] = ((B, mp, 4), np.float64)
+            image_out = buffers.ImageArrays({"n_windows": B, "max_pts": mp}, {k: buffers.zeros_like_space(image, sh, dt) for k, (sh, dt) in shapes.items()})
         thresh = getattr(self, "initThresh_", 0) if init_thresh is None else init_thresh
         si, ss, sp, so, sio = image.struct(), state.struct(), problem.struct(), out.struct(), image_out.struct()
-        rc = self.ctx._L.avm_fsel_select_image_batch(self.ctx.h, image.mem, C.byref(si), abi.dptr(image.a["prob"]), abi.iptr(initialized),
-                                                     int(thresh), int(bool(prune_lost)), C.byref(ss), C.byref(sp), C.byref(so), C.byref(sio))
-        self.ctx.check(rc, "avm_fsel_select_image_batch")
+        self.ctx.call("avm_fsel_select_image_batch", image.mem, C.byref(si), abi.dptr(image.a["prob"]), abi.iptr(initialized), int(thresh),
+                      int(bool(prune_lost)), C.byref(ss), C.byref(sp), C.byref(so), C.byref(sio))
         return out, image_out
 
     def information(self, problems: buffers.FselArrays):
@@ -117,8 +87,7 @@ class FeatureSelector:
         N, T = 9 * (H + 1), 3 * H
         om, dl, va = np.zeros((P, N, N)), np.zeros((P, mc, T, T)), np.zeros((P, mc), np.int32)
         s = problems.struct()
-        rc = self.ctx._L.avm_fsel_information(self.ctx.h, problems.mem, C.byref(s), abi.dptr(om), abi.dptr(dl), abi.iptr(va))
-        self.ctx.check(rc, "avm_fsel_information")
+        self.ctx.call("avm_fsel_information", problems.mem, C.byref(s), abi.dptr(om), abi.dptr(dl), abi.iptr(va))
         return om, dl, va
 
     def nn_depth(self, problems: buffers.FselArrays):
@@ -126,7 +95,7 @@ class FeatureSelector:
         assert not problems.on_device
         out = np.zeros((problems.n_problems, problems.dims["max_cand"]))
         s = problems.struct()
-        self.ctx.check(self.ctx._L.avm_fsel_nn_depth(self.ctx.h, problems.mem, C.byref(s), abi.dptr(out)), "avm_fsel_nn_depth")
+        self.ctx.call("avm_fsel_nn_depth", problems.mem, C.byref(s), abi.dptr(out))
         return out
 
     def setParameters(self, enable=True, maxFeatures=150, initThresh=0):

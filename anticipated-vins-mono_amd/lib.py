@@ -41,77 +41,15 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(_LIB_PATH)
-        vp = C.c_void_p
-        L.avm_version.restype = C.c_char_p
-        L.avm_last_error.restype = C.c_char_p
-        L.avm_last_error.argtypes = [vp]
-        L.avm_default_options.argtypes = [C.POINTER(abi.Options)]
-        L.avm_create.argtypes = [C.POINTER(abi.Config), C.POINTER(vp)]
-        L.avm_destroy.argtypes = [vp]
-        L.avm_destroy.restype = None
-        L.avm_last_kernel_ms.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
-        L.avm_window_solve_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.WindowBatch),
-                                             C.POINTER(abi.PriorOut), C.POINTER(abi.SolveSummary)]
-        L.avm_window_solve.argtypes = L.avm_window_solve_batch.argtypes
-        L.avm_fsel_select.argtypes = [vp, C.c_int, C.POINTER(abi.FselBatch), abi.c_ip, abi.c_ip, abi.c_dp]
-        L.avm_fsel_fallback_stats.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.avm_imu_preintegrate_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.WindowBatch)] + [abi.c_dp] * 4
-        L.avm_window_eval_factors.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.WindowBatch), C.c_int] + [abi.c_dp] * 6
-        L.avm_triangulate_batch.argtypes = [vp, C.c_int, C.POINTER(abi.WindowBatch), C.c_double]
-        L.avm_imu_propagate_batch.argtypes = [vp, C.c_int, C.POINTER(abi.WindowBatch), C.POINTER(C.c_double)]
-        L.avm_fsel_select_batch.argtypes = [vp, C.c_int, C.POINTER(abi.FselBatch), C.POINTER(abi.FselOut)]
-        L.avm_fsel_information.argtypes = [vp, C.c_int, C.POINTER(abi.FselBatch), abi.c_dp, abi.c_dp, abi.c_ip]
-        L.avm_fsel_nn_depth.argtypes = [vp, C.c_int, C.POINTER(abi.FselBatch), abi.c_dp]
-        L.avm_fsel_horizon_imu.argtypes = [vp, C.c_int, C.POINTER(abi.FselHorizonIn), abi.c_dp, abi.c_dp]
-        L.avm_projection_td_eval.argtypes = [vp, C.c_int, C.POINTER(abi.TdFactorBatch), abi.c_dp, abi.c_dp]
-        L.avm_fsel_build_cloud.argtypes = [vp, C.c_int, C.POINTER(abi.WindowBatch), abi.c_dp, abi.c_dp, C.c_int32, abi.c_ip, abi.c_dp, abi.c_dp]
-        L.avm_debug_copy_sqrt_info.argtypes = [vp, C.c_int, abi.c_dp]
-        L.avm_debug_last_solve_form.argtypes = [vp]
-        L.avm_debug_last_marg_form.argtypes = [vp]
-        L.avm_debug_last_fsel_form.argtypes = [vp]
-        L.avm_debug_last_split.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.avm_debug_counters.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.avm_debug_preint_cache.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.avm_debug_fsel_evaluations.argtypes = [vp, C.POINTER(C.c_int64)]
-        L.avm_debug_solve_tp_occupancy.argtypes = [C.POINTER(C.c_int)]
-        L.avm_debug_solve_tp_list_occupancy.argtypes = [C.POINTER(C.c_int)]
-        L.avm_slide_window.argtypes = [vp, C.c_int, C.POINTER(abi.WindowBatch), C.c_int32, C.c_int32, C.c_double]
-        L.avm_visual_initial_align_batch.argtypes = [vp, C.POINTER(abi.Options), C.c_int, C.POINTER(abi.AlignBatch), C.POINTER(abi.WindowBatch),
-                                                     C.POINTER(abi.AlignOut)]
-        L.avm_debug_align_layout.argtypes = [C.POINTER(C.c_int)]
-        for name, argtypes in list(abi.PROTOTYPES.items()) + list(abi.TRACK_PROTOTYPES.items()) + list(abi.SELECT_PROTOTYPES.items()) + list(abi.RELO_PROTOTYPES.items()) + list(abi.SPLIT_PROTOTYPES.items()):
-            getattr(L, name).argtypes = argtypes
-        L.avm_debug_track_struct_sizes.argtypes = [C.POINTER(C.c_int)]
-        L.avm_debug_relo_struct_sizes.argtypes = [C.POINTER(C.c_int)]
-        L.avm_comm_unique_id.argtypes = [vp, C.c_void_p]
-        L.avm_comm_init.argtypes = [vp, C.c_int32, C.c_int32, C.c_void_p]
-        L.avm_gather_states.argtypes = [vp, abi.c_dp, abi.c_dp, C.c_size_t]
-        L.avm_comm_destroy.argtypes = [vp]
-        L.avm_gt_load_csv.restype = vp
-        L.avm_gt_load_csv.argtypes = [C.c_char_p]
-        L.avm_gt_from_rows.restype = vp
-        L.avm_gt_from_rows.argtypes = [abi.c_dp, C.c_int32]
-        L.avm_gt_free.argtypes = [vp]
-        L.avm_gt_size.argtypes = [vp]
-        L.avm_gt_seek.argtypes = [vp]
-        L.avm_fsel_horizon_ground_truth.argtypes = [vp, C.c_int32, C.c_double, abi.c_dp, abi.c_dp, C.c_double, abi.c_dp, abi.c_dp]
-        L.avm_image_from_pointcloud.argtypes = [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.POINTER(C.c_float)), C.c_int32, abi.c_ip, abi.c_ip, abi.c_dp]
+        for name, (restype, argtypes) in abi.PROTOTYPES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
-EXPORTS = [
-    "avm_default_options", "avm_create", "avm_destroy", "avm_last_error", "avm_version", "avm_abi_version",
-    "avm_window_solve_batch", "avm_window_solve", "avm_fsel_select", "avm_fsel_fallback_stats", "avm_imu_preintegrate_batch", "avm_window_eval_factors",
-    "avm_fsel_select_batch", "avm_fsel_information", "avm_fsel_nn_depth", "avm_last_kernel_ms", "avm_triangulate_batch", "avm_imu_propagate_batch", "avm_fsel_horizon_imu", "avm_projection_td_eval", "avm_fsel_build_cloud",
-    "avm_ctx_stream", "avm_comm_unique_id", "avm_comm_init", "avm_gather_states", "avm_comm_destroy", "avm_gt_load_csv", "avm_gt_from_rows", "avm_gt_free", "avm_gt_size", "avm_gt_seek", "avm_fsel_horizon_ground_truth", "avm_image_from_pointcloud", "avm_slide_window",
-    "avm_visual_initial_align_batch",
-    "avm_window_solve_batch_flags", "avm_slide_window_flags", "avm_keyframe_decision_batch", "avm_failure_detection_batch",
-    "avm_add_image_batch", "avm_imu_push_batch", "avm_solve_view_batch", "avm_solve_view_store_depths", "avm_slide_window_tracks",
-    "avm_fsel_select_image_batch",
-    "avm_headers_step_batch", "avm_set_relo_frame_batch", "avm_relo_resolve_batch", "avm_relo_finish_batch", "avm_prior_keep_batch",
-    "avm_window_solve_batch_relo",
-]
+# the functions include/avm.h declares: __graft_entry__.build() looks every one up
+EXPORTS = [name for name in abi.PROTOTYPES if not name.startswith("avm_debug_")]
 
 
 class Context:
@@ -144,28 +82,41 @@ class Context:
         if rc != abi.AVM_OK:
             raise AvmError(f"{what} failed: status {rc}: {self._L.avm_last_error(self.h).decode()}")
 
+    def call(self, name: str, *args):
+        """The entry point `name` on this ctx (the handle goes first); a status other than AVM_OK raises AvmError with the library's message."""
+        self.check(getattr(self._L, name)(self.h, *args), name)
+
+    @property
+    def device_str(self) -> str:
+        """the torch name of this ctx's device"""
+        return "cuda:%d" % self.device
+
+    def _int64s(self, name: str, n: int) -> list:
+        """the n counters the hook `name` writes"""
+        out = (C.c_int64 * n)()
+        self.call(name, out)
+        return [int(v) for v in out]
+
     # ---- multi-GPU: the library's own RCCL communicator (include/avm.h)
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)
-        self.check(self._L.avm_comm_unique_id(self.h, buf), "avm_comm_unique_id")
+        self.call("avm_comm_unique_id", buf)
         return buf.raw
 
     def comm_init(self, n_ranks: int, rank: int, uid: bytes):
         assert len(uid) == 128
-        self.check(self._L.avm_comm_init(self.h, int(n_ranks), int(rank), C.create_string_buffer(uid, 128)), "avm_comm_init")
+        self.call("avm_comm_init", int(n_ranks), int(rank), C.create_string_buffer(uid, 128))
 
     def gather_states(self, send, recv, count: int):
         """ncclAllGather of `count` doubles per rank (device tensors): recv[r * count : (r + 1) * count] = rank r's send."""
-        self.check(self._L.avm_gather_states(self.h, abi.dptr(send), abi.dptr(recv), int(count)), "avm_gather_states")
+        self.call("avm_gather_states", abi.dptr(send), abi.dptr(recv), int(count))
 
     def comm_destroy(self):
-        self.check(self._L.avm_comm_destroy(self.h), "avm_comm_destroy")
+        self.call("avm_comm_destroy")
 
     def fsel_fallback_stats(self) -> dict:
         """avm_fsel_fallback_stats: how often this ctx's selects fell back from the all-rounds-in-one-launch kernel."""
-        out = (C.c_int64 * 4)()
-        self.check(self._L.avm_fsel_fallback_stats(self.h, out), "avm_fsel_fallback_stats")
-        return {"reruns": int(out[0]), "failed_launches": int(out[1]), "mode": int(out[2]), "calls": int(out[3])}
+        return dict(zip(("reruns", "failed_launches", "mode", "calls"), self._int64s("avm_fsel_fallback_stats", 4)))
 
     def last_solve_form(self) -> str:
         """Which form of the solve kernel the last optimization() took: 'throughput' (two 256-thread workgroups per CU,
@@ -180,9 +131,7 @@ class Context:
     def last_split(self) -> tuple:
         """How the last optimization() split its batch (avm_window_solve_batch_relo): (windows solved as plain ones, windows that took the
         extended kernel, the plain ones' form: 0 latency / 1 throughput / -1 there were none, 1 when the list builds of the kernels ran)."""
-        out = (C.c_int64 * 4)()
-        self.check(self._L.avm_debug_last_split(self.h, out), "avm_debug_last_split")
-        return tuple(int(v) for v in out)
+        return tuple(self._int64s("avm_debug_last_split", 4))
 
     def last_fsel_form(self) -> str:
         """Which form the last select_batch() started in: 'solo' (one workgroup per frame with lazy evaluation: batches of 33 frames and
@@ -192,26 +141,22 @@ class Context:
     def last_fsel_evaluations(self) -> int:
         """Candidate evaluations the last select_batch() executed on the device: counted by the solo form's kernel (lazy evaluation);
         -1 for the forms that score every live candidate in every round (their count follows from the frame: bench.py)."""
-        out = C.c_int64(0)
-        self.check(self._L.avm_debug_fsel_evaluations(self.h, C.byref(out)), "avm_debug_fsel_evaluations")
-        return int(out.value)
+        return self._int64s("avm_debug_fsel_evaluations", 1)[0]
 
     def counters(self) -> dict:
         """Debug counters of this ctx: device / pinned (re)allocations so far, and how the last marginalization's square roots were taken."""
-        out = (C.c_int64 * 4)()
-        self.check(self._L.avm_debug_counters(self.h, out), "avm_debug_counters")
-        return {"allocations": int(out[0]), "prior_one_wavefront": int(out[1]), "prior_windows": int(out[2]),
-                "prior_pivoted_path": int(out[2] - out[1]), "solve_form": "throughput" if out[3] else "latency"}
+        allocs, one_wave, windows, tp = self._int64s("avm_debug_counters", 4)
+        return {"allocations": allocs, "prior_one_wavefront": one_wave, "prior_windows": windows, "prior_pivoted_path": windows - one_wave,
+                "solve_form": "throughput" if tp else "latency"}
 
     def preint_cache(self) -> dict:
         """The ctx's pre-integration cache: intervals the last pre-integration examined and how many of them it integrated (the ones
         whose IMU samples or linearization biases differ from what the stored results came from; all of them with AVM_PREINT_CACHE=0),
         and the windows whose cached intervals the last slide_window rolled (0: it left the cache alone)."""
-        out = (C.c_int64 * 3)()
-        self.check(self._L.avm_debug_preint_cache(self.h, out), "avm_debug_preint_cache")
-        return {"examined": int(out[0]), "recomputed": int(out[1]), "rolled_windows": int(out[2])}
+        return dict(zip(("examined", "recomputed", "rolled_windows"), self._int64s("avm_debug_preint_cache", 3)))
 
     def kernel_ms(self, which: str) -> float:
         ms = C.c_float(0)
-        self.check(self._L.avm_last_kernel_ms(self.h, which.encode(), C.byref(ms)), "avm_last_kernel_ms")
+        self.call("avm_last_kernel_ms", which.encode(), C.byref(ms))
         return ms.value
+

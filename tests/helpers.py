@@ -9,6 +9,31 @@ buffers = importlib.import_module(PKG + ".buffers")
 synth = importlib.import_module(PKG + ".synth")
 
 
+def header_text():
+    import os
+
+    return open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "avm.h")).read()
+
+
+def header_declarations():
+    """Every function include/avm.h declares: {name: (return type as written, number of arguments)}; `(void)` is 0 arguments."""
+    import re
+
+    code = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)             # (comments hold commas, semicolons and parentheses)
+    code = re.sub(r"^\s*#.*$", "", code, flags=re.M)
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w ]*?[\s\*]+)(avm_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;", code):
+        args = [x for x in args.split(",") if x.strip()]
+        out[name] = (" ".join(ret.replace("*", " * ").split()), 0 if [a.strip() for a in args] == ["void"] else len(args))
+    return out
+
+
+def header_arg_count(name):
+    decl = header_declarations()
+    assert name in decl, name + " is not declared in include/avm.h"
+    return decl[name][1]
+
+
 def rel(a, b):
     a, b = np.asarray(a, float), np.asarray(b, float)
     return float(np.abs(a - b).max() / max(1e-300, np.abs(b).max()))

@@ -7,15 +7,11 @@ The statements follow vins_estimator/src/feature_manager.cpp (addFeatureCheckPar
 :141-159, removeFailures :161-170, removeBackShiftDepth / removeBack / removeFront :275-352) and estimator.cpp (failureDetection
 :612-658) with Python lists and numpy float64 scalars: one rounding per operation, no fused multiply-add, sums in list order.
 """
-import os
-import re
-
 import numpy as np
 
 from helpers import abi, blank_windows
+from helpers import header_arg_count as _header_arg_count, header_text as _header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "avm.h")
 NEW_ENTRY_POINTS = ("avm_window_solve_batch_flags", "avm_slide_window_flags", "avm_keyframe_decision_batch", "avm_failure_detection_batch")
 WINDOW_SIZE = abi.WINDOW_SIZE
 
@@ -118,17 +114,6 @@ def roll_features_statement(feats, flag, shift_depth, remove_failures, pose, ex_
 
 
 # ---------------------------------------------------------------- header and prototypes
-def _header():
-    return open(HEADER).read()
-
-
-def _header_arg_count(name):
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)          # (comments hold commas and semicolons)
-    m = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, code, re.S)
-    assert m, name + " is not declared in include/avm.h"
-    return len([x for x in m.group(1).split(",") if x.strip()])
-
-
 def test_header_declares_the_entry_points_and_keeps_the_abi_version():
     for name in NEW_ENTRY_POINTS:
         assert _header_arg_count(name) > 0
@@ -137,12 +122,13 @@ def test_header_declares_the_entry_points_and_keeps_the_abi_version():
 
 
 def test_ctypes_prototypes_match_the_headers_argument_counts():
-    assert set(abi.PROTOTYPES) == set(NEW_ENTRY_POINTS)
-    for name, argtypes in abi.PROTOTYPES.items():
-        assert len(argtypes) == _header_arg_count(name), name
-    lib_src = open(os.path.join(ROOT, "anticipated-vins-mono_amd", "lib.py")).read()
+    import importlib
+
     for name in NEW_ENTRY_POINTS:
-        assert '"%s"' % name in lib_src                                  # lib.EXPORTS: build() looks every one up
+        assert len(abi.PROTOTYPES[name][1]) == _header_arg_count(name), name
+    exports = importlib.import_module("anticipated-vins-mono_amd.lib").EXPORTS
+    for name in NEW_ENTRY_POINTS:
+        assert name in exports                                           # lib.EXPORTS: build() looks every one up
 
 
 # ---------------------------------------------------------------- the statements against hand-computed cases

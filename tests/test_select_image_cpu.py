@@ -9,7 +9,7 @@ import importlib
 import numpy as np
 
 from helpers import abi
-from test_mixed_batch_cpu import _header, _header_arg_count
+from helpers import header_arg_count as _header_arg_count, header_text as _header
 
 fs_m = importlib.import_module("anticipated-vins-mono_amd.feature_selector")
 lib_m = importlib.import_module("anticipated-vins-mono_amd.lib")
@@ -50,15 +50,15 @@ def select_statement(state, image, prob, initialized, init_thresh, prune_lost, p
 # ---------------------------------------------------------------- header and prototype
 def test_header_declares_the_entry_point_and_the_prototype_matches():
     name = "avm_fsel_select_image_batch"
-    assert _header_arg_count(name) == 11 == len(abi.SELECT_PROTOTYPES[name])
-    assert set(abi.SELECT_PROTOTYPES) == {name} and name in lib_m.EXPORTS
+    assert _header_arg_count(name) == 11 == len(abi.PROTOTYPES[name][1])
+    assert name in lib_m.EXPORTS
     assert "#define AVM_ABI_VERSION 6 " in _header() and abi.AVM_ABI_VERSION == 6
     assert "typedef struct avm_select_state {" in _header()
     S = abi.SelectState
     assert [f[0] for f in S._fields_] == ["max_tracked", "last_feature_id", "n_tracked", "tracked_id", "first_image"]
     assert (C.sizeof(S), S.last_feature_id.offset, S.first_image.offset) == (40, 8, 32)
     L = lib_m.lib()                                          # (loads without a GPU)
-    assert L.avm_fsel_select_image_batch.argtypes == abi.SELECT_PROTOTYPES[name]
+    assert L.avm_fsel_select_image_batch.argtypes == abi.PROTOTYPES[name][1]
     for word in ("never issues a lost id again", "decided BEFORE the selection", "conservative on purpose"):
         assert word in _header(), word
 

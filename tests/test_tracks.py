@@ -465,6 +465,25 @@ def test_add_image_refusals(ctx, where):
     assert _host(g.a["n_feat"]).tolist() == [6, 6, 6] and _host(gfid)[0, :6].tolist() == [10, 4, 2, 8, 6, 5]
 
 
+def test_a_refused_call_raises_with_the_entry_points_name_and_the_ctx_stays_usable(ctx):
+    """The call path of the Python layer (Context.call) on a refusal: an image batch of three windows for tables of two."""
+    E = est_m.Estimator(ctx=ctx, options=abi.default_options())
+    w = blank_windows(2)
+    fid, before = np.zeros((2, w.dims["max_feat"]), np.int32), w.copy()
+    three = buffers.ImageArrays.from_maps([{1: (0.1, 0.1)}] * 3, 4)
+    assert three.n_windows != w.n_windows
+    with pytest.raises(lib_m.AvmError) as e:
+        E.addFeatureCheckParallax(w, fid, three, MIN_PARALLAX)
+    assert str(e.value).startswith("avm_add_image_batch failed: status %d: " % abi.AVM_ERR_INVALID)
+    assert "image->n_windows differs from windows->n_windows" in str(e.value)
+    assert all(np.array_equal(w.a[k], before.a[k]) for k in w.a) and not fid.any()
+    # ... and the same ctx takes the valid call
+    two = buffers.ImageArrays.from_maps([{1: (0.1, 0.1)}, {2: (0.2, 0.2), 5: (0.5, 0.5)}], 4)
+    flags, ltn, _ = E.addFeatureCheckParallax(w, fid, two, MIN_PARALLAX)
+    assert w.a["n_feat"].tolist() == [1, 2] and fid[0, :1].tolist() == [1] and fid[1, :2].tolist() == [2, 5]
+    assert flags.tolist() == [OLD, OLD] and ltn.tolist() == [0, 0]          # nothing tracked: a keyframe
+
+
 @WHERE
 def test_view_depths_and_imu_refusals(ctx, where):
     L = ctx._L
