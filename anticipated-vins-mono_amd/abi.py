@@ -379,6 +379,26 @@ PROTOTYPES = {
 }
 
 
+class SfmBatch(C.Structure):
+    """avm_sfm_batch (include/avm_init.h): relativePose's result, all_image_frame and every frame's image, one row per stream."""
+    _fields_ = [("n_windows", C.c_int32), ("max_frames", C.c_int32), ("max_pts", C.c_int32), ("ba_max_num_iterations", C.c_int32),
+                ("ba_max_solver_time_s", C.c_double),
+                ("l", c_ip), ("n_frames", c_ip), ("key_index", c_ip), ("frame_n_pts", c_ip), ("frame_pt_id", c_ip),
+                ("relative_R", c_dp), ("relative_T", c_dp), ("frame_pt_xy", c_dp)]
+
+
+class SfmOut(C.Structure):
+    """avm_sfm_out (include/avm_init.h)."""
+    _fields_ = [("ok", c_ip), ("frame_R", c_dp), ("frame_T", c_dp), ("q", c_dp), ("T", c_dp), ("point", c_dp), ("point_state", c_ip),
+                ("ba_counts", c_ip), ("ba_cost", c_dp), ("pnp_q", c_dp), ("pnp_t", c_dp)]
+
+
+# The declarations of include/avm_init.h, the initialisation phase: a table of its own, applied by lib.lib() like the one above
+PROTOTYPES_INIT = {
+    "avm_global_sfm_batch": (_int, [_vp, _int, _P(SfmBatch), _win, c_ip, _P(SfmOut)]),
+}
+
+
 def default_options() -> Options:
     """Values the reference runs with (estimator.cpp:794-806, euroc_config.yaml:54-63) + Ceres defaults.
 

@@ -28,6 +28,14 @@ const Rule ALIGN_RULES[8] = {{AVM_ERR_INVALID, "bad table"},
                              {AVM_ERR_INVALID, "imu_n outside [0, max_samp]"},
                              {AVM_ERR_INVALID, "key_index must be strictly increasing inside [0, n_frames)"}};
 
+static_assert(BAD_SFM_L == 1 && BAD_SFM_FRAMES == 2 && BAD_SFM_KEYS == 3 && BAD_SFM_NPTS == 4 && BAD_SFM_IDS == 5, "the rows below stand in the order of the rule numbers");
+const Rule SFM_RULES[8] = {{AVM_ERR_INVALID, "bad table"},
+                           {AVM_ERR_INVALID, "l outside [0, 9]"},
+                           {AVM_ERR_INVALID, "n_frames outside [11, max_frames]"},
+                           {AVM_ERR_INVALID, "key_index must be strictly increasing inside [0, n_frames)"},
+                           {AVM_ERR_INVALID, "frame_n_pts outside [0, max_pts]"},
+                           {AVM_ERR_INVALID, "frame_pt_id must be strictly increasing within a frame"}};
+
 int report_bad(avm_ctx* c, int first_bad, const char* unit, const Rule* rules) {
   const Rule& r = rules[first_bad % 8];
   c->err = std::string(unit) + " " + std::to_string(first_bad / 8) + ": " + (r.text ? r.text : "bad table");

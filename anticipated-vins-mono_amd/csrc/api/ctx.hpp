@@ -12,6 +12,7 @@ enum Mark {
   M_ALIGN_GYRO_BIAS, M_ALIGN_SOLVE, M_ALIGN_APPLY, M_ALIGN_END,                          // avm_visual_initial_align_batch
   M_SPLIT, M_SPLIT_END, M_MERGE, M_MERGE_END,                                            // avm_fsel_select_image_batch around the selection
   M_GATHER, M_GATHER_END,                                                                // avm_gather_states
+  M_SFM_CHAIN_BA, M_SFM_FRAME_PNP, M_SFM_END,                                            // avm_global_sfm_batch
   N_MARKS
 };
 

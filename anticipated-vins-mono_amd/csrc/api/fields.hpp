@@ -36,7 +36,7 @@ inline void set_ptr(void* s, const Field& f, const void* p) { std::memcpy(static
 // avm_relo_resolve_batch, U_RELO_FINISH: avm_relo_finish_batch; U_KEEP: avm_prior_keep_batch)
 enum : unsigned { U_WHOLE = 1, U_TRI = 2, U_SLIDE = 4, U_PROP = 8, U_CLOUD = 16, U_ALIGN = 32, U_KEYF = 64, U_FAIL = 128,
                   U_TRK = 256, U_DEPTH = 512, U_PUSH = 1024, U_SLIDE_TD = 2048, U_SELECT = 4096, U_SELECT_BACK = 8192,
-                  U_RELO_SET = 16384, U_RELO_RESOLVE = 32768, U_RELO_FINISH = 65536, U_KEEP = 131072 };
+                  U_RELO_SET = 16384, U_RELO_RESOLVE = 32768, U_RELO_FINISH = 65536, U_KEEP = 131072, U_SFM = 262144 };
 constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE | U_SLIDE | U_PROP;
 
 // S: the struct of the member; D, nmember: the struct the dims come from (`d` in `count`) and its batch size (`N` in `count`)
@@ -56,13 +56,13 @@ constexpr unsigned U_GEOM = U_WHOLE | U_TRI | U_SLIDE | U_CLOUD, U_IMU = U_WHOLE
 const Field WINDOW_FIELDS[] = {
     WIN(pose, double, N * 77, U_GEOM | U_PROP | U_ALIGN | U_FAIL | U_RELO_SET | U_RELO_FINISH, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
     WIN(speedbias, double, N * 99, U_IMU | U_ALIGN | U_FAIL, U_WHOLE | U_SLIDE | U_PROP | U_ALIGN)
-    WIN(ex_pose, double, N * 7, U_GEOM | U_ALIGN, U_WHOLE | U_SLIDE)
+    WIN(ex_pose, double, N * 7, U_GEOM | U_ALIGN | U_SFM, U_WHOLE | U_SLIDE)
     WIN(inv_depth, double, N * d.max_feat, U_GEOM | U_ALIGN | U_TRK | U_DEPTH, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_TRK | U_DEPTH)
-    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_KEYF | U_TRK | U_DEPTH | U_RELO_RESOLVE, U_SLIDE | U_TRK)
-    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK | U_RELO_RESOLVE, U_SLIDE | U_TRK)
-    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
-    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
-    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(n_feat, int32_t, N, U_GEOM | U_ALIGN | U_SFM | U_KEYF | U_TRK | U_DEPTH | U_RELO_RESOLVE, U_SLIDE | U_TRK)
+    WIN(feat_start, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_SFM | U_KEYF | U_TRK | U_RELO_RESOLVE, U_SLIDE | U_TRK)
+    WIN(feat_nobs, int32_t, N * d.max_feat, U_WHOLE | U_TRI | U_SLIDE | U_ALIGN | U_SFM | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(feat_obs_begin, int32_t, N * d.max_feat, U_GEOM | U_ALIGN | U_SFM | U_KEYF | U_TRK, U_SLIDE | U_TRK)
+    WIN(obs_xy, double, N * d.max_obs * 2, U_GEOM | U_ALIGN | U_SFM | U_KEYF | U_TRK, U_SLIDE | U_TRK)
     WIN(imu_n, int32_t, N * 10, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
     WIN(imu_dt, double, N * 10 * d.max_samp, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
     WIN(imu_acc, double, N * 10 * (d.max_samp + 1) * 3, U_IMU | U_PUSH, U_SLIDE | U_PUSH)
@@ -142,6 +142,27 @@ const Field ALIGN_OUT_FIELDS[] = {AO(ok, int32_t, N) AO(delta_bg, double, N * 3)
                                   AO(g_world, double, N * 3) AO(deltas, double, N * (d.max_frames - 1) * 10)};
 #undef AO
 constexpr Table ALIGN_OUT = table_of(ALIGN_OUT_FIELDS);
+
+// avm_sfm_batch / avm_sfm_out (avm_global_sfm_batch).  The outputs travel both ways: a stream writes only the rows its ok allows, the
+// others return as the caller passed them.  SfmDims: the three sizes the outputs' extents come from (two structs hold them)
+struct SfmDims {
+  int32_t n_windows, max_frames, max_feat;
+};
+#define SF(member, type, count) FIELD(avm_sfm_batch, avm_sfm_batch, n_windows, "sf_" #member, member, type, count, U_WHOLE, 0)
+const Field SFM_FIELDS[] = {SF(l, int32_t, N) SF(n_frames, int32_t, N) SF(key_index, int32_t, N * AVM_NFRAMES) SF(frame_n_pts, int32_t, N * d.max_frames)
+                            SF(frame_pt_id, int32_t, N * d.max_frames * d.max_pts) SF(relative_R, double, N * 9) SF(relative_T, double, N * 3)
+                            SF(frame_pt_xy, double, N * d.max_frames * d.max_pts * 2)};
+#undef SF
+constexpr Table SFM = table_of(SFM_FIELDS);
+#define SO(member, type, count) FIELD(avm_sfm_out, SfmDims, n_windows, "sfo_" #member, member, type, count, U_WHOLE, U_WHOLE)
+const Field SFM_OUT_FIELDS[] = {SO(ok, int32_t, N) SO(frame_R, double, N * d.max_frames * 9) SO(frame_T, double, N * d.max_frames * 3)
+                                SO(q, double, N * AVM_NFRAMES * 4) SO(T, double, N * AVM_NFRAMES * 3) SO(point, double, N * d.max_feat * 3)
+                                SO(point_state, int32_t, N * d.max_feat) SO(ba_counts, int32_t, N * 3) SO(ba_cost, double, N * 2)
+                                SO(pnp_q, double, N * AVM_NFRAMES * 4) SO(pnp_t, double, N * AVM_NFRAMES * 3)};
+#undef SO
+constexpr Table SFM_OUT = table_of(SFM_OUT_FIELDS);
+static_assert(sizeof(avm_sfm_batch) == offsetof(avm_sfm_batch, l) + SFM.n * sizeof(void*), "SFM names every array of avm_sfm_batch");
+static_assert(sizeof(avm_sfm_out) == SFM_OUT.n * sizeof(void*), "SFM_OUT names every array of avm_sfm_out");
 
 // avm_image_batch: the image of avm_add_image_batch (pools "ai_" ...), the image and image_out of avm_fsel_select_image_batch ("si_" ...,
 // "so_" ...: the prefix of on_device), and that call's avm_select_state, whose batch size is the image's

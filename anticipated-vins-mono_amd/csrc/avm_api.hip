@@ -32,5 +32,6 @@ using namespace avm;
 #include "api/tracks.hpp"
 #include "api/relo.hpp"
 #include "api/align.hpp"
+#include "api/sfm.hpp"
 #include "api/fsel.hpp"
 #include "api/debug.hpp"

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/avm.h"
+#include "sfm/rules.hpp"  // (with include/avm_init.h)
 
 namespace avm {
 
@@ -245,6 +246,22 @@ hipError_t launch_align_gyro_bias(const AlignArgs& a, hipStream_t stream);
 hipError_t launch_align_solve(const AlignArgs& a, hipStream_t stream);
 hipError_t launch_align_prepare(const AlignArgs& a, hipStream_t stream);
 hipError_t launch_align_apply(const AlignArgs& a, hipStream_t stream);
+
+// ---- the deterministic half of Estimator::initialStructure (global_sfm.hip; the table check: sfm/rules.hpp) -----------------------------
+struct SfmArgs {
+  avm_sfm_batch s;       // device pointers
+  avm_window_batch w;    // device pointers: the track tables and ex_pose of `full`
+  const int32_t* feat_id;
+  avm_sfm_out out;       // device pointers
+  // stages, committed per stream by sfm_commit_kernel: st [B] 0 = the BA was accepted, else the stream's ok; fst [B][max_frames] a frame's
+  // outcome (0 / 3); q [B][11][4], T [B][11][3], point [B][max_feat][3], state [B][max_feat], frame_R / frame_T as the outputs
+  int32_t *st, *fst, *sstate;
+  double *sq, *sT, *spoint, *sR, *sfT;
+};
+hipError_t launch_validate_sfm(const avm_sfm_batch& s, int* first_bad, hipStream_t stream);
+hipError_t launch_sfm_chain_ba(const SfmArgs& a, hipStream_t stream);
+hipError_t launch_sfm_frame_pnp(const SfmArgs& a, hipStream_t stream);
+hipError_t launch_sfm_commit(const SfmArgs& a, hipStream_t stream);
 
 // Launch of a kernel whose dynamic LDS exceeds the default limit.  hipFuncAttributeMaxDynamicSharedMemorySize is set once per process
 // and kernel, by the first call: a function-local static per Kernel, initialised under the language's guard, so concurrent first calls from

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import abi, buffers
+from . import abi, buffers, init_buffers
 from .lib import Context
 
 
@@ -181,6 +181,37 @@ class Estimator:
         self.ctx.call("avm_visual_initial_align_batch", C.byref(self.options), align.mem, C.byref(sa), C.byref(sw) if sw is not None else None,
                       C.byref(so))
         return out
+
+    def globalSFM(self, sfm: buffers.SfmArrays, full: buffers.WindowArrays, feat_id, out: init_buffers.SfmOutArrays = None,
+                  align: buffers.AlignArrays = None):
+        """The deterministic half of Estimator::initialStructure (estimator.cpp:247-344) for B streams: GlobalSFM::construct and the PnP
+        of every frame (avm_global_sfm_batch, include/avm_init.h).  sfm: relativePose's result and the frames' images (synth.make_sfm);
+        full: the whole f_manager.feature list (its track tables and ex_pose are read, nothing is written); feat_id [B, max_feat] where
+        the tables live.  With `align`, frame_R / frame_T of the result ARE align's own arrays (its max_frames must be sfm's): the
+        alignment reads what the SfM wrote, with no copy.  Returns the SfmOutArrays; a stream writes only the rows its ok allows."""
+        sfm = init_buffers.SfmBatchArrays.of(sfm)
+        MF, MFE = sfm.dims["max_frames"], full.dims["max_feat"]
+        out = out or init_buffers.SfmOutArrays.alloc(sfm.n_windows, MF, MFE, self.ctx.device_str if sfm.on_device else None)
+        if align is not None:
+            assert align.dims["max_frames"] == MF and align.on_device == sfm.on_device
+            out.a["frame_R"], out.a["frame_T"] = align.a["frame_R"], align.a["frame_T"]
+        ss, sw, so = sfm.struct(), full.struct(), out.struct()
+        self.ctx.call("avm_global_sfm_batch", sfm.mem, C.byref(ss), C.byref(sw), abi.iptr(buffers.like(sfm, feat_id, np.int32, (sfm.n_windows, MFE))),
+                      C.byref(so))
+        return out
+
+    def initialStructure(self, sfm: buffers.SfmArrays, full: buffers.WindowArrays, feat_id, align: buffers.AlignArrays,
+                         windows: buffers.WindowArrays = None):
+        """Estimator::initialStructure after relativePose: globalSFM() into align's frame_R / frame_T, then visualInitialAlign(align,
+        windows); on the device the two calls chain with no host trip.  Returns (SfmOutArrays, AlignOutArrays).
+        A stream whose SfM failed (ok != 0) wrote no frame pose; this method then sets that stream's frame_R / frame_T rows of `align`
+        to NaN, which the alignment answers with ITS ok = 0 (non-finite input ends that window alone, include/avm.h) and leaves the
+        window's state alone.  The caller prefills nothing; it loses what those rows held."""
+        so = self.globalSFM(sfm, full, feat_id, align=align)
+        bad = so.a["ok"] != 0
+        align.a["frame_R"][bad] = np.nan
+        align.a["frame_T"][bad] = np.nan
+        return so, self.visualInitialAlign(align, windows)
 
     @staticmethod
     def reset_linearization_biases(windows: buffers.WindowArrays):

@@ -41,15 +41,18 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in abi.PROTOTYPES.items():
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
+        for table in (abi.PROTOTYPES, abi.PROTOTYPES_INIT):
+            for name, (restype, argtypes) in table.items():
+                f = getattr(L, name)
+                f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
 
 # the functions include/avm.h declares: __graft_entry__.build() looks every one up
 EXPORTS = [name for name in abi.PROTOTYPES if not name.startswith("avm_debug_")]
+# ... and the ones of include/avm_init.h
+EXPORTS_INIT = list(abi.PROTOTYPES_INIT)
 
 
 class Context:

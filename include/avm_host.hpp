@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "avm.h"
+#include "avm_init.h"
 
 namespace avm_host {
 
@@ -241,6 +242,7 @@ struct ImageFrame {
   Vector3d T{0, 0, 0};
   bool is_key_frame = false;
   IntegrationBase pre_integration;  // unused on the first frame of the map
+  std::map<int, std::array<double, 2>> points;  // feature id -> its normalized xy in camera 0 (ImageFrame::points, the part initialStructure reads)
 };
 
 // flat tables of all_image_frame in the layout of avm_align_batch (one window); owns the storage the batch points into
@@ -258,6 +260,81 @@ struct AlignTables {
     return b;
   }
 };
+
+// The tables of avm_global_sfm_batch for one stream (avm_init.h) and its outputs; owns the storage the structs point into
+struct SfmTables {
+  int32_t l = 0, n_frames = 0, n_feat = 0, ok = -1;
+  int max_frames = AVM_NFRAMES, max_pts = 1, max_feat = 1, max_obs = 1, ba_max_num_iterations = 50;
+  std::vector<int32_t> key_index, frame_n_pts, frame_pt_id, feat_start, feat_nobs, feat_obs_begin, feat_id, point_state, ba_counts;
+  std::vector<double> relative_R, relative_T, frame_pt_xy, obs_xy, ex_pose, frame_R, frame_T, q, T, point, ba_cost, pnp_q, pnp_t;
+  avm_sfm_batch batch() const {
+    avm_sfm_batch b{};
+    b.n_windows = 1, b.max_frames = max_frames, b.max_pts = max_pts, b.ba_max_num_iterations = ba_max_num_iterations, b.ba_max_solver_time_s = 0.0;
+    b.l = &l, b.n_frames = &n_frames, b.key_index = key_index.data(), b.frame_n_pts = frame_n_pts.data(), b.frame_pt_id = frame_pt_id.data();
+    b.relative_R = relative_R.data(), b.relative_T = relative_T.data(), b.frame_pt_xy = frame_pt_xy.data();
+    return b;
+  }
+  avm_window_batch full() const {  // the members the call reads; everything else NULL
+    avm_window_batch b{};
+    b.n_windows = 1, b.max_feat = max_feat, b.max_obs = max_obs;
+    b.ex_pose = const_cast<double*>(ex_pose.data()), b.n_feat = &n_feat, b.feat_start = feat_start.data(), b.feat_nobs = feat_nobs.data();
+    b.feat_obs_begin = feat_obs_begin.data(), b.obs_xy = obs_xy.data();
+    return b;
+  }
+  avm_sfm_out out() {
+    avm_sfm_out o{};
+    o.ok = &ok, o.frame_R = frame_R.data(), o.frame_T = frame_T.data(), o.q = q.data(), o.T = T.data(), o.point = point.data();
+    o.point_state = point_state.data(), o.ba_counts = ba_counts.data(), o.ba_cost = ba_cost.data(), o.pnp_q = pnp_q.data(), o.pnp_t = pnp_t.data();
+    return o;
+  }
+};
+
+// f_manager.feature (the WHOLE list, estimator.cpp:247-260), all_image_frame with every frame's points (:298-330), the window's
+// Headers and relativePose's result -> the tables of avm_global_sfm_batch; the output arrays are sized and zeroed.  Plain vectors, no
+// call into the library.
+inline void marshal_sfm(const std::list<FeaturePerId>& feature, const std::map<double, ImageFrame>& all_image_frame, const double* Headers,
+                        int l, const double* relative_R, const double* relative_T, const double* ex_pose, SfmTables& t) {
+  const size_t F = all_image_frame.size();
+  if (F < (size_t)AVM_NFRAMES) throw Error(AVM_ERR_INVALID, "all_image_frame holds fewer than 11 frames");
+  if (F > AVM_MAX_ALIGN_FRAMES) throw Error(AVM_ERR_CAPACITY, "all_image_frame holds more than 64 frames (AVM_MAX_ALIGN_FRAMES)");
+  size_t n_obs = 0, P = 1;
+  for (const auto& f : feature) n_obs += f.feature_per_frame.size();
+  for (const auto& kv : all_image_frame) P = std::max(P, kv.second.points.size());
+  if (feature.size() > AVM_MAX_FEAT_WIDE || n_obs > AVM_MAX_OBS_WIDE) throw Error(AVM_ERR_CAPACITY, "f_manager.feature holds more than 384 features / 4224 observations");
+  if (P > AVM_MAX_IMAGE_PTS) throw Error(AVM_ERR_CAPACITY, "an image holds more than 1024 points (AVM_MAX_IMAGE_PTS)");
+  const size_t NFE = std::max<size_t>(feature.size(), 1), NO = std::max<size_t>(n_obs, 1);
+  t.l = l, t.n_frames = (int32_t)F, t.n_feat = (int32_t)feature.size();
+  t.max_frames = (int)F, t.max_pts = (int)P, t.max_feat = (int)NFE, t.max_obs = (int)NO;
+  t.relative_R.assign(relative_R, relative_R + 9), t.relative_T.assign(relative_T, relative_T + 3), t.ex_pose.assign(ex_pose, ex_pose + 7);
+  t.feat_start.assign(NFE, 0), t.feat_nobs.assign(NFE, 0), t.feat_obs_begin.assign(NFE, 0), t.feat_id.assign(NFE, 0), t.obs_xy.assign(NO * 2, 0.0);
+  size_t e = 0, o = 0;
+  for (const auto& f : feature) {
+    t.feat_start[e] = f.start_frame, t.feat_nobs[e] = (int32_t)f.feature_per_frame.size(), t.feat_obs_begin[e] = (int32_t)o, t.feat_id[e] = f.feature_id;
+    for (const auto& pf : f.feature_per_frame) t.obs_xy[2 * o] = pf.point[0], t.obs_xy[2 * o + 1] = pf.point[1], o++;
+    e++;
+  }
+  t.frame_n_pts.assign(F, 0), t.frame_pt_id.assign(F * P, 0), t.frame_pt_xy.assign(F * P * 2, 0.0);
+  size_t k = 0;
+  for (auto it = all_image_frame.begin(); it != all_image_frame.end(); ++it, ++k) {
+    size_t n = 0;
+    for (const auto& pt : it->second.points) {  // std::map order: ids ascending
+      t.frame_pt_id[k * P + n] = pt.first;
+      t.frame_pt_xy[(k * P + n) * 2] = pt.second[0], t.frame_pt_xy[(k * P + n) * 2 + 1] = pt.second[1];
+      n++;
+    }
+    t.frame_n_pts[k] = (int32_t)n;
+  }
+  t.key_index.assign(AVM_NFRAMES, 0);
+  for (int i = 0; i <= AVM_WINDOW_SIZE; i++) {
+    const auto it = all_image_frame.find(Headers[i]);
+    if (it == all_image_frame.end()) throw Error(AVM_ERR_INVALID, "Headers[" + std::to_string(i) + "] is not a key of all_image_frame");
+    t.key_index[i] = (int32_t)std::distance(all_image_frame.begin(), it);
+  }
+  t.ok = -1;
+  t.frame_R.assign(F * 9, 0.0), t.frame_T.assign(F * 3, 0.0), t.q.assign(AVM_NFRAMES * 4, 0.0), t.T.assign(AVM_NFRAMES * 3, 0.0);
+  t.point.assign(NFE * 3, 0.0), t.point_state.assign(NFE, 0), t.ba_counts.assign(3, 0), t.ba_cost.assign(2, 0.0);
+  t.pnp_q.assign(AVM_NFRAMES * 4, 0.0), t.pnp_t.assign(AVM_NFRAMES * 3, 0.0);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Estimator: the members optimization() reads and writes (estimator.h:62-115), and HP-A itself
@@ -572,6 +649,32 @@ class Estimator {
     g = Vector3d{g_world[0], g_world[1], g_world[2]};
     solver_flag = NON_LINEAR;
     return true;
+  }
+
+  // Estimator::initialStructure (estimator.cpp:247-353) after relativePose: GlobalSFM::construct and the PnP of every frame on the
+  // device (avm_global_sfm_batch), ImageFrame::R / ::T / ::is_key_frame of every frame, then visualInitialAlign().  Returns the
+  // reference's bool; sfm_ok keeps the SfM's own outcome (avm_init.h: 0, or 1..4), sfm the tables and results of the call.  The IMU
+  // excitation check (:213-245) and relativePose (:262-268: l, relative_R, relative_T) stay the caller's.
+  int sfm_ok = -1;
+  SfmTables sfm;
+  bool initialStructure(int l, const double relative_R[9], const double relative_T[3]) {
+    vector2double();
+    marshal_sfm(f_manager.feature, all_image_frame, Headers, l, relative_R, relative_T, para_Ex_Pose[0], sfm);
+    const avm_sfm_batch sb = sfm.batch();
+    const avm_window_batch fb = sfm.full();
+    avm_sfm_out so = sfm.out();
+    ctx_.check(avm_global_sfm_batch(ctx_.get(), AVM_MEM_HOST, &sb, &fb, sfm.feat_id.data(), &so), "avm_global_sfm_batch");
+    sfm_ok = sfm.ok;
+    if (sfm_ok != 0) return false;
+    size_t k = 0;
+    int i = 0;
+    for (auto it = all_image_frame.begin(); it != all_image_frame.end(); ++it, ++k) {
+      std::copy(sfm.frame_R.begin() + k * 9, sfm.frame_R.begin() + k * 9 + 9, it->second.R.begin());
+      std::copy(sfm.frame_T.begin() + k * 3, sfm.frame_T.begin() + k * 3 + 3, it->second.T.begin());
+      it->second.is_key_frame = i <= AVM_WINDOW_SIZE && sfm.key_index[i] == (int32_t)k;  // (:286-297, :341-343)
+      if (it->second.is_key_frame) i++;
+    }
+    return visualInitialAlign();
   }
 
   // Estimator::slideWindow (estimator.cpp:996-1107) with slideWindowOld / slideWindowNew and the three FeatureManager
