@@ -33,17 +33,46 @@ AVM_DEV void lds_base_check() {
 AVM_DEV double uni(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
+// A loop-carried uniform double, held as its two 32-bit halves.  Where a uni() value is merged at a loop head or behind a branch, the
+// compiler weighs the merged 64-bit value's uses - FP64 arithmetic, all of it vector instructions - and moves the whole chain back to
+// vector registers; the halves are integers, merge in scalar registers, and become a double again (a register pair, no instruction
+// of its own) at the use.
+struct unid {
+  int hi, lo;
+  AVM_DEV unid(double v = 0) { *this = v; }
+  AVM_DEV unid& operator=(double v) {
+    hi = __builtin_amdgcn_readfirstlane(__double2hiint(v)), lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+    return *this;
+  }
+  AVM_DEV operator double() const { return __hiloint2double(hi, lo); }
+};
+// ... and a flag or count every lane holds alike (what an outlined phase returns, what LDS holds): a branch on it is a scalar branch, and
+// the loop scalars assigned behind it stay in scalar registers.
+AVM_DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+AVM_DEV bool uni(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+
+// A fresh copy of the thread index (and of the lane / wavefront index), opaque to the compiler.  The kernel bodies use the whole register
+// file; whatever they derive from threadIdx.x once (t >> 6, lds + L_X + t, the start address of a strided loop) the compiler hoists out of
+// the trust-region loop and the window loop, keeps live across every outlined phase, spills, and reloads at the use: one dependent round
+// trip to scratch memory per value.  Behind the empty asm there is nothing to hoist or to share with an earlier copy: a value derived from
+// a fresh index is recomputed where it is used (a v_and / v_lshrrev or two) and dies with the segment that asked for it.  Every phase of a
+// kernel body takes its own at its head (`const int t = fresh_tid();`); none lives across an outlined call or a loop iteration.
+AVM_DEV int fresh_tid() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+AVM_DEV int fresh_lane() { return fresh_tid() & 63; }
+AVM_DEV int fresh_wave() { return fresh_tid() >> 6; }  // (per lane; __builtin_amdgcn_readfirstlane makes it a scalar)
 
 // Workgroup reductions of the solve kernel with ONE barrier each.  The partial sums of consecutive reductions go to alternating
 // halves of lds[L_RED]: a wavefront can only overwrite a half two reductions later, i.e. after a barrier that every wavefront
 // reaches with its reads of that half done.  Which half is next is a counter every wavefront keeps for itself in LDS (all
 // wavefronts run the same sequence of reductions, so the counters agree); red_init() zeroes it at kernel entry.
-// (The address from an opaque copy of the thread index: the compiler cannot hoist it, so every reduction computes it with two VALU
-//  instructions.  Computed once it was kept for the whole kernel, spilled, and every reduction began by reloading it from scratch memory.)
+// (The address from fresh_wave(): the compiler cannot hoist it, so every reduction computes it with two VALU instructions.  Computed
+//  once it was kept for the whole kernel, spilled, and every reduction began by reloading it from scratch memory.)
 AVM_DEV int* red_counter() {
-  int t = threadIdx.x;
-  asm volatile("" : "+v"(t));
-  return reinterpret_cast<int*>(LDS() + L_RED_CNT) + (t >> 6);
+  return reinterpret_cast<int*>(LDS() + L_RED_CNT) + fresh_wave();
 }
 AVM_DEV void red_init() {
   if ((threadIdx.x & 63) == 0) *red_counter() = 0;

@@ -26,8 +26,13 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
   AVM_PRIO_LIGHT();
   double* lds = LDS();
   int* ids = reinterpret_cast<int*>(lds + L_INT);
-  const int t = threadIdx.x;
+  // (no thread index of the kernel's own: every segment below takes a fresh one - fresh_tid(), solve/lds.hpp)
   const avm_options& o = lds_opt();
+  // The same options from the kernel arguments (scalar registers), for the trust-region loop's own decisions.  A comparison with a value
+  // read from LDS is a per-lane branch to the compiler, and every loop scalar that is assigned on one side of such a branch only is merged
+  // behind it in a vector register (which is spilled and reloaded), whatever uni() did to the assignment.  With the branches of the loop
+  // decided in scalar registers (these options; uni() on what an outlined phase returns or LDS holds) the scalars stay scalar.
+  const avm_options& ou = A.opt;
   const avm_window_batch& B = A.b;
 
 #ifdef AVM_WIN_LIST
@@ -80,63 +85,75 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
     const long long pw__ = clock64();
     const long long wall0 = A.time_cap_ticks > 0 ? wall_clock64() : 0;  // (only thread 0's copy is ever compared)
     // ---------------- load ----------------
-    for (int i = t; i < 77; i += NT) lds[L_X + i] = B.pose[(size_t)w * 77 + i];
-    for (int i = t; i < 99; i += NT) lds[L_X + XSB + i] = B.speedbias[(size_t)w * 99 + i];
-    for (int i = t; i < MAXE; i += NT) lds[L_X + XLAM + i] = i < c.nf ? B.inv_depth[(size_t)w * B.max_feat + i] : 1.0;
+    {  // states
+      const int t = fresh_tid();
+      for (int i = t; i < 77; i += NT) lds[L_X + i] = B.pose[(size_t)w * 77 + i];
+      for (int i = t; i < 99; i += NT) lds[L_X + XSB + i] = B.speedbias[(size_t)w * 99 + i];
+      for (int i = t; i < MAXE; i += NT) lds[L_X + XLAM + i] = i < c.nf ? B.inv_depth[(size_t)w * B.max_feat + i] : 1.0;
+    }
+    {  // the solve's vectors
+      const int t = fresh_tid();
 #ifdef AVM_X
-    for (int i = t; i < VEC; i += NT) lds[L_SC + i] = 1.0, lds[L_ST + i] = 0.0, lds[L_Y + i] = 0.0, lds[L_DD + i] = 1.0;
-    if (t < 7) {
-      lds[L_X + XEX + t] = B.ex_pose[(size_t)w * 7 + t];
-      // relo_Pose is frame 11 of the state; without a relocalization frame it mirrors pose 0 (never read by a factor)
-      lds[L_X + 7 * NFR + t] = c.has_relo ? B.relo_pose[(size_t)w * 7 + t] : B.pose[(size_t)w * 77 + t];
-    }
-    if (t == 7) lds[L_X + XTD] = (c.est_td && B.td) ? B.td[w] : 0.0;
-    if (t == 8) lds[L_X + XTD + 1] = 0.0;
+      for (int i = t; i < VEC; i += NT) lds[L_SC + i] = 1.0, lds[L_ST + i] = 0.0, lds[L_Y + i] = 0.0, lds[L_DD + i] = 1.0;
+      if (t < 7) {
+        lds[L_X + XEX + t] = B.ex_pose[(size_t)w * 7 + t];
+        // relo_Pose is frame 11 of the state; without a relocalization frame it mirrors pose 0 (never read by a factor)
+        lds[L_X + 7 * NFR + t] = c.has_relo ? B.relo_pose[(size_t)w * 7 + t] : B.pose[(size_t)w * 77 + t];
+      }
+      if (t == 7) lds[L_X + XTD] = (c.est_td && B.td) ? B.td[w] : 0.0;
+      if (t == 8) lds[L_X + XTD + 1] = 0.0;
 #elif defined(AVM_TP)
-    for (int i = t; i < VEC; i += NT) lds[L_SC + i] = 1.0, lds[L_ST + i] = 0.0, lds[L_Y + i] = 0.0, lds[L_DD + i] = 1.0;
+      for (int i = t; i < VEC; i += NT) lds[L_SC + i] = 1.0, lds[L_ST + i] = 0.0, lds[L_Y + i] = 0.0, lds[L_DD + i] = 1.0;
 #else
-    for (int i = t; i < VEC; i += NT) lds[L_SC + i] = 1.0, lds[L_ST + i] = 0.0, lds[L_Y + i] = 0.0, lds[L_DG + i] = 0.0, lds[L_DD + i] = 1.0;
+      for (int i = t; i < VEC; i += NT) lds[L_SC + i] = 1.0, lds[L_ST + i] = 0.0, lds[L_Y + i] = 0.0, lds[L_DG + i] = 0.0, lds[L_DD + i] = 1.0;
 #endif
-    for (int i = t; i < MAXPRIOR; i += NT) lds[L_DXP + i] = 0.0, lds[L_RP + i] = 0.0;
-    if (t < c.nf) {
-      ids[I_FSTART + t] = B.feat_start[(size_t)w * B.max_feat + t];
-      ids[I_FNOBS + t] = B.feat_nobs[(size_t)w * B.max_feat + t];
-      ids[I_FOBS + t] = B.feat_obs_begin[(size_t)w * B.max_feat + t];
+      for (int i = t; i < MAXPRIOR; i += NT) lds[L_DXP + i] = 0.0, lds[L_RP + i] = 0.0;
     }
-    if (t >= PBT0 && t < PBT0 + c.pnblk) {  // the prior's block table (one round trip instead of one per block)
-      const int k = t - PBT0;
-      ids[I_PBLK + k * 3] = B.prior_blk_kind[(size_t)w * B.max_pblk + k], ids[I_PBLK + k * 3 + 1] = B.prior_blk_frame[(size_t)w * B.max_pblk + k];
-    }
+    {  // tables: the features' track tables, the prior's block table, ric / tic
+      const int t = fresh_tid();
+      if (t < c.nf) {
+        ids[I_FSTART + t] = B.feat_start[(size_t)w * B.max_feat + t];
+        ids[I_FNOBS + t] = B.feat_nobs[(size_t)w * B.max_feat + t];
+        ids[I_FOBS + t] = B.feat_obs_begin[(size_t)w * B.max_feat + t];
+      }
+      if (t >= PBT0 && t < PBT0 + c.pnblk) {  // the prior's block table (one round trip instead of one per block)
+        const int k = t - PBT0;
+        ids[I_PBLK + k * 3] = B.prior_blk_kind[(size_t)w * B.max_pblk + k], ids[I_PBLK + k * 3 + 1] = B.prior_blk_frame[(size_t)w * B.max_pblk + k];
+      }
 #ifndef AVM_X
-    if (t == 0) {
-      const double* ex = B.ex_pose + (size_t)w * 7;
-      double R[9];
-      q2R(quat{ex[6], ex[3], ex[4], ex[5]}, R);
-      for (int k = 0; k < 9; k++) lds[L_RIC + k] = R[k];
-      for (int k = 0; k < 3; k++) lds[L_RIC + 9 + k] = ex[k];
-    }
+      if (t == 0) {
+        const double* ex = B.ex_pose + (size_t)w * 7;
+        double R[9];
+        q2R(quat{ex[6], ex[3], ex[4], ex[5]}, R);
+        for (int k = 0; k < 9; k++) lds[L_RIC + k] = R[k];
+        for (int k = 0; k < 3; k++) lds[L_RIC + 9 + k] = ex[k];
+      }
 #endif
+    }
     __syncthreads();
     PROFQ(c, 38);
+    {  // observation slot -> feature
+      const int t = fresh_tid();
 #ifndef AVM_X
-    if (t < 7) lds[L_RIC + 12 + t] = B.ex_pose[(size_t)w * 7 + t];  // current ex_pose for the prior's dx
-    if (t == 7) lds[L_RIC + 19] = B.td ? B.td[w] : 0.0;             // ... and para_Td (a constant here)
+      if (t < 7) lds[L_RIC + 12 + t] = B.ex_pose[(size_t)w * 7 + t];  // current ex_pose for the prior's dx
+      if (t == 7) lds[L_RIC + 19] = B.td ? B.td[w] : 0.0;             // ... and para_Td (a constant here)
 #endif
-    if (t < c.nf) {
-      const int s0 = ids[I_FOBS + t], no = ids[I_FNOBS + t];
-      for (int k = 0; k < no; k++) c.osf[s0 + k] = t;
+      if (t < c.nf) {
+        const int s0 = ids[I_FOBS + t], no = ids[I_FNOBS + t];
+        for (int k = 0; k < no; k++) c.osf[s0 + k] = t;
+      }
     }
     {
       // fs[a] = first feature with start >= a, and per frame the features observed in it (as imu_j) in feature order:
       // one wavefront per list, features along the lanes, positions from a ballot's prefix population count
-      const int ln = t & 63;
+      const int t = fresh_tid(), ln = t & 63;
       for (int q = t >> 6; q <= NFR; q += NT / 64) {
         int cnt = 0;
         for (int e0 = 0; e0 < c.nf; e0 += 64) cnt += __popcll(__ballot(e0 + ln < c.nf && ids[I_FSTART + min(e0 + ln, MAXE - 1)] < q));
         if (ln == 0) ids[I_FS + q] = cnt;
       }
     }
-    if (t == 0) {
+    if (fresh_tid() == 0) {  // the prior's index lists
       int off = 0;
 #ifdef AVM_TP
       int psb_ = 0;
@@ -169,8 +186,8 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       ids[I_CRFIT] = (nsb_ <= 1 && sbfr_ == 0) ? 1 : 0;
 #endif
     }
-    for (int f = 1 + (t >> 6); f < NFR; f += NT / 64) {  // features observed in frame f (as imu_j), in feature order
-      const int ln = t & 63;
+    for (int f = 1 + fresh_wave(); f < NFR; f += NT / 64) {  // features observed in frame f (as imu_j), in feature order
+      const int ln = fresh_lane();
       int n = 0;
       unsigned am = 0;  // start frames that occur among the frame's factors (one accumulation run of the frame task each)
       for (int e0 = 0; e0 < c.nf; e0 += 64) {
@@ -184,16 +201,20 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       }
       if (ln == 0) ids[I_NCOV + f] = n, ids[I_NRUN + f] = __popc(am);
     }
-    if (t == 0) ids[I_NCOV] = 0;
+    {
+      const int t = fresh_tid();
+      if (t == 0) ids[I_NCOV] = 0;
 #ifdef AVM_X
-    // frame 11: the features matched in the relocalization frame (the host's list, in its order)
-    for (int k = t; k < c.relo_n; k += NT) c.cov[(NFRP - 1) * MAXE + k] = min(max(B.relo_feat[(size_t)w * B.max_feat + k], 0), max(c.nf - 1, 0));
-    if (t == 64) ids[I_NCOV + NFRP - 1] = c.relo_n;
+      // frame 11: the features matched in the relocalization frame (the host's list, in its order)
+      for (int k = t; k < c.relo_n; k += NT) c.cov[(NFRP - 1) * MAXE + k] = min(max(B.relo_feat[(size_t)w * B.max_feat + k], 0), max(c.nf - 1, 0));
+      if (t == 64) ids[I_NCOV + NFRP - 1] = c.relo_n;
 #endif
+    }
     __syncthreads();
     PROFQ(c, 39);
+    // frame deal (each form takes its fresh thread index at its head)
 #ifdef AVM_X
-    if (t == 0) {  // longest-processing-time assignment of the frames to the assembling wavefronts
+    if (fresh_tid() == 0) {  // longest-processing-time assignment of the frames to the assembling wavefronts
       int done = 0;
       ids[I_FRW] = -1;
       // (the loads in registers - constant indices only: indexed by a run-time value the array lived in private memory, 53 scratch instructions
@@ -217,7 +238,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       }
     }
 #elif defined(AVM_TP)
-    if (t < 64) {
+    if (const int t = fresh_tid(); t < 64) {
       // Longest-processing-time assignment of the frames to the four wavefronts (lane q keeps the load of wavefront q, in factors).
       // Every wavefront has a SIMD to itself within the workgroup; wavefront 2 also evaluates the raw IMU Jacobians (about two
       // chunks' worth) and two fifths of the prior's rows, wavefront 3 the other three fifths: they start with that load.
@@ -242,7 +263,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       }
     }
 #else
-    if (t < 64) {
+    if (const int t = fresh_tid(); t < 64) {
       // Longest-processing-time assignment of the frames to the assembling wavefronts, by the lanes of wavefront 0 (lane q
       // keeps the factor count of wavefront q).  A wavefront's cost is its number of 64-factor chunks over ALL its frames;
       // wavefronts w and w + 4 share a SIMD, so the quantity to keep level is the chunk count per SIMD (the raw-IMU
@@ -275,6 +296,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
     // once per window: the structural zeros of the scratch slot (raw IMU Jacobians outside their blocks, E^T F of
     // the frames that do not observe a feature) - the evaluations only ever rewrite the same nonzero entries
     {
+      const int t = fresh_tid();
       gdouble* IJR = c.sc + Scratch::IJRAW;
       for (int i = t; i < (NFR - 1) * IJBLK; i += NT) IJR[i] = 0.0;
       gdouble* Wt = c.sc + Scratch::W;
@@ -302,10 +324,10 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
 
     PROF(c, 9);
     // ---------------- TrustRegionMinimizer ----------------
-    if (t < 32) lds[L_SUM + t] = 0.0;
+    if (const int t = fresh_tid(); t < 32) lds[L_SUM + t] = 0.0;
     int n_successful = 0, accept_mask = 0;
-    double initial_cost = 0;
-    double radius = o.initial_trust_region_radius, mu = 1e-8;
+    unid initial_cost = 0;
+    unid radius = ou.initial_trust_region_radius, mu = 1e-8;
     const double min_mu = 1e-8, max_mu = 1.0, mu_inc = 10.0;
     bool reuse = false, first = true, have_alpha = false;
 #if defined(AVM_X) || defined(AVM_TP)
@@ -313,16 +335,17 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
 #else
     auto DG = [&](int i) { return lds[L_DG + i]; };
 #endif
-    double alpha = 0, dogleg_step_norm = 0;
-    double gnorm = 0, gn_norm = 0, ytg = 0, jusq = 0;  // |g/D|, |D y|, y^T g, |J u|^2
-    double k1 = 0, k2 = 0;                             // step = -(k1 * g/D^2 + k2 * y)
-    double x_cost = 0, x_norm = 0, gradient_max_norm = 0;
+    unid alpha = 0, dogleg_step_norm = 0;
+    unid gnorm = 0, gn_norm = 0, ytg = 0, jusq = 0;  // |g/D|, |D y|, y^T g, |J u|^2
+    unid k1 = 0, k2 = 0;                             // step = -(k1 * g/D^2 + k2 * y)
+    unid x_cost = 0, x_norm = 0, gradient_max_norm = 0;
     int iteration = 0, num_invalid = 0, termination = AVM_TERM_NO_CONVERGENCE;
     bool step_ok = true;
 
     // squared ambient norm over the variable parameter blocks (Ceres' reduced program: constant blocks are not in it)
 #ifdef AVM_X
     auto amb_sq = [&](const double* xa, const double* xb) {  // |xa - xb|^2, xb == nullptr: |xa|^2
+      const int t = fresh_tid();
       double s = 0;
       auto term = [&](int i) {
         const double d = xb ? xa[i] - xb[i] : xa[i];
@@ -339,7 +362,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
 #else
     auto amb_norm = [&](const double* xs) {
       double s = 0;
-      for (int i = t; i < 176 + c.nf; i += NT) s += xs[i] * xs[i];
+      for (int i = fresh_tid(); i < 176 + c.nf; i += NT) s += xs[i] * xs[i];
       return sqrt(block_sum1(s));
     };
 #endif
@@ -351,7 +374,8 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       const bool was_first = first;
       (void)was_first;
       if (first) {
-        if (o.jacobi_scaling) {
+        if (ou.jacobi_scaling) {
+          const int t = fresh_tid();
 #ifdef AVM_TP
           if (t < NF) lds[L_SC + t] = 1.0 / (1.0 + sqrt(lds[s_off(t, t)]));
           for (int e = t; e < c.nf; e += NT) lds[L_SC + NF + e] = 1.0 / (1.0 + sqrt(lds[L_HEE + e]));
@@ -365,6 +389,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       // gradient_max_norm = |x - Plus(x, -g)|_inf with the unscaled gradient
       double gm = 0;
       {
+        const int t = fresh_tid();
         const double* x = lds + L_X;
         const double* g = lds + L_G;
         if (t < NFR) {
@@ -392,7 +417,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       }
       gradient_max_norm = uni(block_max1(gm));
       __syncthreads();
-      if (c.prof && t == 0) c.prof[43] += clock64() - pt__;
+      if (c.prof && fresh_tid() == 0) c.prof[43] += clock64() - pt__;
       scale_system(c, was_first);
       PROF(c, 10);
     };
@@ -402,25 +427,30 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
     };
     // eval_jac() stages the frame tasks' rows in the LDS range that also holds the Gauss-Newton step, the dogleg step
     // and the candidate state, so a speculative evaluation parks what a rejection needs (current point, GN step)
-    // in the spare tail of the slot's prior region
-    gdouble* spec_save = c.sc + Scratch::HP + HP_SPEC;
+    // in the spare tail of the slot's prior region (its address from the LDS context at every use: kept for the window it was one more
+    // spilled register pair, and an LDS read is cheaper than a trip to scratch memory)
+    auto spec_save = [&]() { return c.sc + Scratch::HP + HP_SPEC; };
     auto spec_enter = [&]() {  // x -> backup, x <- candidate
       __syncthreads();
-      for (int i = t; i < XN; i += NT) spec_save[i] = lds[L_X + i], lds[L_X + i] = lds[L_XC + i];
-      for (int i = t; i < VEC; i += NT) spec_save[XN + i] = lds[L_Y + i];
+      const int t = fresh_tid();
+      gdouble* save = spec_save();
+      for (int i = t; i < XN; i += NT) save[i] = lds[L_X + i], lds[L_X + i] = lds[L_XC + i];
+      for (int i = t; i < VEC; i += NT) save[XN + i] = lds[L_Y + i];
       __syncthreads();
     };
     auto spec_restore = [&]() {  // x <- backup, candidate <- x
       __syncthreads();
-      for (int i = t; i < XN; i += NT) {
+      gdouble* save = spec_save();
+      for (int i = fresh_tid(); i < XN; i += NT) {
         const double cand = lds[L_X + i];
-        lds[L_X + i] = spec_save[i];
+        lds[L_X + i] = save[i];
         lds[L_XC + i] = cand;
       }
       __syncthreads();
     };
     auto spec_restore_gn_step = [&]() {  // after the system at x has been rebuilt (eval_jac stages over it again)
-      for (int i = t; i < VEC; i += NT) lds[L_Y + i] = spec_save[XN + i];
+      gdouble* save = spec_save();
+      for (int i = fresh_tid(); i < VEC; i += NT) lds[L_Y + i] = save[XN + i];
       __syncthreads();
     };
     // Speculation (exact: the same evaluations, fewer of them).  Ceres evaluates the cost at the candidate and, if
@@ -433,7 +463,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
     x_norm = uni(amb_norm(lds + L_X));
     evaluate_x();
     initial_cost = x_cost;
-    double ref_cost = x_cost;
+    unid ref_cost = x_cost;
 
     while (true) {
       PROFQ_T0();
@@ -441,29 +471,29 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       if (iteration > 0) {
         if (step_ok) n_successful++;
         if (iteration <= AVM_MAX_ITER_TRACE) {
-          if (t == 0) lds[L_SUM + iteration - 1] = x_cost, lds[L_SUM + 16 + iteration - 1] = radius;
+          if (fresh_tid() == 0) lds[L_SUM + iteration - 1] = x_cost, lds[L_SUM + 16 + iteration - 1] = radius;
           if (step_ok) accept_mask |= 1 << (iteration - 1);
         }
       }
       if (A.time_cap_ticks > 0) {
         // MaxSolverTimeReached (checked before the iteration limit, like Ceres): options.max_solver_time_in_seconds of
         // estimator.cpp:803-806.  One thread reads the clock, the verdict goes through LDS so that it is workgroup-uniform.
-        if (t == 0) ids[I_TIMEUP] = wall_clock64() - wall0 >= A.time_cap_ticks;
+        if (fresh_tid() == 0) ids[I_TIMEUP] = wall_clock64() - wall0 >= A.time_cap_ticks;
         __syncthreads();
-        if (ids[I_TIMEUP]) {
+        if (uni(ids[I_TIMEUP])) {
           termination = AVM_TERM_NO_CONVERGENCE;
           break;
         }
       }
-      if (iteration >= o.max_num_iterations) {
+      if (iteration >= ou.max_num_iterations) {
         termination = AVM_TERM_NO_CONVERGENCE;
         break;
       }
-      if (step_ok && gradient_max_norm <= o.gradient_tolerance) {
+      if (step_ok && gradient_max_norm <= ou.gradient_tolerance) {
         termination = AVM_TERM_GRADIENT_TOL;
         break;
       }
-      if (radius <= o.min_trust_region_radius) {
+      if (radius <= ou.min_trust_region_radius) {
         termination = AVM_TERM_MIN_RADIUS;
         break;
       }
@@ -474,16 +504,19 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
         reuse = true;
         have_alpha = false;
         // D = sqrt(clamp(diag(J'^T J'))), g/D
+        {
+          const int t = fresh_tid();
 #ifdef AVM_TP
-        if (t < NF) lds[L_DD + t] = sqrt(fmin(fmax(lds[s_off(t, t)], o.min_lm_diagonal), o.max_lm_diagonal));
-        for (int e = t; e < c.nf; e += NT) lds[L_DD + NF + e] = sqrt(fmin(fmax(lds[L_HEE + e], o.min_lm_diagonal), o.max_lm_diagonal));
+          if (t < NF) lds[L_DD + t] = sqrt(fmin(fmax(lds[s_off(t, t)], o.min_lm_diagonal), o.max_lm_diagonal));
+          for (int e = t; e < c.nf; e += NT) lds[L_DD + NF + e] = sqrt(fmin(fmax(lds[L_HEE + e], o.min_lm_diagonal), o.max_lm_diagonal));
 #else
-        if (t < NF) lds[L_DD + t] = sqrt(fmin(fmax(lds[L_S + roff(t) + t], o.min_lm_diagonal), o.max_lm_diagonal));
-        if (t >= 192 && t < 192 + c.nf) lds[L_DD + NF + t - 192] = sqrt(fmin(fmax(lds[L_HEE + t - 192], o.min_lm_diagonal), o.max_lm_diagonal));
+          if (t < NF) lds[L_DD + t] = sqrt(fmin(fmax(lds[L_S + roff(t) + t], o.min_lm_diagonal), o.max_lm_diagonal));
+          if (t >= 192 && t < 192 + c.nf) lds[L_DD + NF + t - 192] = sqrt(fmin(fmax(lds[L_HEE + t - 192], o.min_lm_diagonal), o.max_lm_diagonal));
 #endif
+        }
         __syncthreads();
         double g2 = 0;
-        for (int i = t; i < NF + c.nf; i += NT) {
+        for (int i = fresh_tid(); i < NF + c.nf; i += NT) {
           const double v = lds[L_G + i] / lds[L_DD + i];
 #if !defined(AVM_X) && !defined(AVM_TP)
           lds[L_DG + i] = v;
@@ -507,11 +540,11 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
           // factorization + both triangular solves on the register tiles of the four wavefronts (y -> lds[L_Y])
           bool ok;
           AVM_PRIO_BULK_CHOL();  // (its pivot chains raise themselves to 3)
-          switch (__builtin_amdgcn_readfirstlane(t >> 6)) {
-            case 0: ok = chol_regs<0>(); break;
-            case 1: ok = chol_regs<1>(); break;
-            case 2: ok = chol_regs<2>(); break;
-            default: ok = chol_regs<3>(); break;
+          switch (__builtin_amdgcn_readfirstlane(fresh_wave())) {
+            case 0: ok = uni(chol_regs<0>()); break;
+            case 1: ok = uni(chol_regs<1>()); break;
+            case 2: ok = uni(chol_regs<2>()); break;
+            default: ok = uni(chol_regs<3>()); break;
           }
           AVM_PRIO_LIGHT();
           PROF(c, 12);
@@ -522,24 +555,24 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
           }
 #else
           bool ok;
-          if (ids[I_CRFIT]) {  // (uniform: the window's prior has the structure chol_regs' pattern is closed for)
-            switch (__builtin_amdgcn_readfirstlane(t >> 6)) {
-              case 0: ok = chol_regs<0>(); break;
-              case 1: ok = chol_regs<1>(); break;
-              case 2: ok = chol_regs<2>(); break;
-              case 3: ok = chol_regs<3>(); break;
+          if (uni(ids[I_CRFIT])) {  // (uniform: the window's prior has the structure chol_regs' pattern is closed for)
+            switch (__builtin_amdgcn_readfirstlane(fresh_wave())) {
+              case 0: ok = uni(chol_regs<0>()); break;
+              case 1: ok = uni(chol_regs<1>()); break;
+              case 2: ok = uni(chol_regs<2>()); break;
+              case 3: ok = uni(chol_regs<3>()); break;
 #ifdef AVM_X
-              case 4: ok = chol_regs<4>(); break;
-              case 5: ok = chol_regs<5>(); break;
-              case 6: ok = chol_regs<6>(); break;
-              default: ok = chol_regs<7>(); break;
+              case 4: ok = uni(chol_regs<4>()); break;
+              case 5: ok = uni(chol_regs<5>()); break;
+              case 6: ok = uni(chol_regs<6>()); break;
+              default: ok = uni(chol_regs<7>()); break;
 #else
-              default: ok = chol_regs<4>(); break;  // (wavefronts 4..7: no tiles)
+              default: ok = uni(chol_regs<4>()); break;  // (wavefronts 4..7: no tiles)
 #endif
             }
             PROF(c, 12);
           } else {
-            ok = cholesky_lds(c.prof);
+            ok = uni(cholesky_lds(c.prof));
             PROF(c, 12);
             if (ok) chol_solve_lds(L_Y);
             PROF(c, 13);
@@ -550,7 +583,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
             continue;
           }
 #endif
-          const double bad_y = back_substitute(c, mu);
+          const double bad_y = uni(back_substitute(c, mu));
           PROF(c, 14);
           if (bad_y > 0) {
             mu = uni(mu * mu_inc);
@@ -563,7 +596,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
         PROFQ_T0();
         if (solver_ok) {
           double a1 = 0, a2 = 0;
-          for (int i = t; i < NF + c.nf; i += NT) {
+          for (int i = fresh_tid(); i < NF + c.nf; i += NT) {
             const double yv = lds[L_Y + i], dv = lds[L_DD + i] * yv;
             a1 += dv * dv;
             a2 += yv * lds[L_G + i];
@@ -582,7 +615,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
           dogleg_step_norm = gn_norm;
         } else {
           if (!have_alpha) {  // Cauchy point, needed only when the GN step leaves the trust region
-            for (int i = t; i < VEC; i += NT) lds[L_ST + i] = i < NF + c.nf ? DG(i) / lds[L_DD + i] : 0.0;
+            for (int i = fresh_tid(); i < VEC; i += NT) lds[L_ST + i] = i < NF + c.nf ? DG(i) / lds[L_DD + i] : 0.0;
             __syncthreads();
             PROFQ(c, 33);
             jusq = uni(jac_times_vec_sq(c, o));
@@ -604,14 +637,14 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
             const double beta = (cc <= 0) ? (dd - cc) / bma : (radius * radius - a2n) / (dd + cc);
             k1 = uni(alpha * (1.0 - beta)), k2 = uni(beta);
             double s2 = 0;
-            for (int i = t; i < NF + c.nf; i += NT) {
+            for (int i = fresh_tid(); i < NF + c.nf; i += NT) {
               const double v = -k1 * DG(i) - k2 * lds[L_DD + i] * lds[L_Y + i];
               s2 += v * v;
             }
             dogleg_step_norm = uni(sqrt(block_sum1(s2)));
           }
         }
-        for (int i = t; i < VEC; i += NT)
+        for (int i = fresh_tid(); i < VEC; i += NT)
           lds[L_ST + i] = i < NF + c.nf ? -(k1 * DG(i) / lds[L_DD + i] + k2 * lds[L_Y + i]) : 0.0;
         // model_cost_change = -step^T g - 1/2 step^T H step, with H y = g - mu D^2 y
         {
@@ -619,7 +652,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
           const double yDy = gn_norm * gn_norm;                 // y^T D^2 y
           const double uHy = utg - mu * ytg;                    // u^T (g - mu D^2 y)
           const double yHy = ytg - mu * yDy;
-          const double sHs = k1 * k1 * (k1 != 0 ? jusq : 0.0) + 2 * k1 * k2 * uHy + k2 * k2 * yHy;
+          const double sHs = k1 * k1 * (k1 != 0 ? (double)jusq : 0.0) + 2 * k1 * k2 * uHy + k2 * k2 * yHy;
           model_cost_change = uni((k1 * utg + k2 * ytg) - 0.5 * sHs);
         }
         step_is_valid = model_cost_change > 0.0;
@@ -627,7 +660,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
         __syncthreads();
       }
       if (!step_is_valid) {
-        if (++num_invalid >= o.max_num_consecutive_invalid_steps) {
+        if (++num_invalid >= ou.max_num_consecutive_invalid_steps) {
           termination = AVM_TERM_FAILURE;
           break;
         }
@@ -645,7 +678,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       const double step_norm = uni(sqrt(amb_sq(lds + L_X, lds + L_XC)));
 #else
       double d2 = 0;
-      for (int i = t; i < 176 + c.nf; i += NT) {
+      for (int i = fresh_tid(); i < 176 + c.nf; i += NT) {
         const double d = lds[L_X + i] - lds[L_XC + i];
         d2 += d * d;
       }
@@ -654,7 +687,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       // the last iteration the options allow: the minimizer stops right after it (the iteration limit is checked before
       // the gradient tolerance, trust_region_minimizer.cc FinalizeIterationAndCheckIfMinimizerCanContinue), so the
       // Jacobian Ceres evaluates at the accepted point is never used: only the cost is computed there
-      const bool last_iteration = iteration >= o.max_num_iterations;
+      const bool last_iteration = iteration >= ou.max_num_iterations;
       const bool spec = speculate && !last_iteration;
       double cand_cost;
       PROFQ(c, 35);
@@ -669,19 +702,19 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
         PROF(c, 15);
       }
       PROFQ_T0();
-      if (step_norm <= o.parameter_tolerance * (x_norm + o.parameter_tolerance)) {
+      if (step_norm <= ou.parameter_tolerance * (x_norm + ou.parameter_tolerance)) {
         if (spec) spec_restore();  // the minimizer stops at the current point, not at the candidate
         termination = AVM_TERM_PARAMETER_TOL;
         break;
       }
       const double cost_change = x_cost - cand_cost;
-      if (fabs(cost_change) <= o.function_tolerance * x_cost) {
+      if (fabs(cost_change) <= ou.function_tolerance * x_cost) {
         if (spec) spec_restore();
         termination = AVM_TERM_FUNCTION_TOL;
         break;
       }
       const double rel = uni((ref_cost - cand_cost) / model_cost_change);
-      if (rel > o.min_relative_decrease) {
+      if (rel > ou.min_relative_decrease) {
         if (spec) {
           // the system at the accepted point is already assembled
           x_norm = uni(amb_norm(lds + L_X));
@@ -689,7 +722,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
           post_evaluate();
         } else {
           __syncthreads();
-          for (int i = t; i < XN; i += NT) lds[L_X + i] = lds[L_XC + i];
+          for (int i = fresh_tid(); i < XN; i += NT) lds[L_X + i] = lds[L_XC + i];
           __syncthreads();
           x_norm = uni(amb_norm(lds + L_X));
           if (last_iteration)
@@ -724,7 +757,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
       // rot_diff from yaw of frame 0 before / after ; stored in lds[L_GF..+9], origin_P0 in +9..12
       gauge_rot_diff(B.pose + (size_t)w * 77, (B.failure_occur && B.last_pose0 && B.failure_occur[w]) ? B.last_pose0 + (size_t)w * 7 : nullptr, L_GF);
       __syncthreads();
-      if (t < NFRP) {
+      if (const int t = fresh_tid(); t < NFRP) {
         const double* rd = lds + L_GF;
         const double* x = lds + L_X;
         quat q = qnormalized(quat{x[t * 7 + 6], x[t * 7 + 3], x[t * 7 + 4], x[t * 7 + 5]});
@@ -750,7 +783,7 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
         }
 #endif
       }
-      if (t == 64) {
+      if (fresh_tid() == 64) {
         double* ex = B.ex_pose + (size_t)w * 7;
         double R[9];
 #ifdef AVM_X
@@ -764,20 +797,20 @@ __global__ __launch_bounds__(NT) AVM_SOLVE_OCC void AVM_SOLVE_KERNEL(AVM_SOLVE_A
         ex[3] = qo.x, ex[4] = qo.y, ex[5] = qo.z, ex[6] = qo.w;
       }
 #ifdef AVM_X
-      if (t == 65 && c.est_td && B.td) B.td[w] = lds[L_X + XTD];
+      if (fresh_tid() == 65 && c.est_td && B.td) B.td[w] = lds[L_X + XTD];
 #endif
 #ifdef AVM_TP
-      for (int e = t; e < c.nf; e += NT) B.inv_depth[(size_t)w * B.max_feat + e] = 1.0 / (1.0 / lds[L_X + XLAM + e]);
+      for (int e = fresh_tid(); e < c.nf; e += NT) B.inv_depth[(size_t)w * B.max_feat + e] = 1.0 / (1.0 / lds[L_X + XLAM + e]);
 #else
-      if (t >= 128 && t < 128 + c.nf) {
+      if (const int t = fresh_tid(); t >= 128 && t < 128 + c.nf) {
         const int e = t - 128;
         B.inv_depth[(size_t)w * B.max_feat + e] = 1.0 / (1.0 / lds[L_X + XLAM + e]);
       }
 #endif
     }
     PROFQ(c, 37);
-    if (c.prof && t == 0) c.prof[31] += 1, c.prof[42] += clock64() - pw__;
-    if (t == 0 && A.summary) {
+    if (c.prof && fresh_tid() == 0) c.prof[31] += 1, c.prof[42] += clock64() - pw__;
+    if (fresh_tid() == 0 && A.summary) {
       avm_solve_summary* so = A.summary + w;
       so->termination = termination;
       so->num_iterations = iteration;

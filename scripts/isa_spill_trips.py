@@ -3,6 +3,10 @@
 
     scripts/isa_spill_trips.py window_solve.hip window_solve_tp_kernel -DAVM_TP=1
     scripts/isa_spill_trips.py window_solve.hip marginalize_tp_kernel -DAVM_TP=1 --lines      (per source line, 20-line buckets)
+    scripts/isa_spill_trips.py window_solve.hip window_solve_tp_kernel -DAVM_TP=1 --range solve_kernel.hpp:466:748
+                                                                                              (only what the line table puts in that range of
+                                                                                               that file, e.g. the trust-region loop; implies the
+                                                                                               line-table build of --lines)
 
 Per kernel (the function whose symbol contains the name; outlined callees are functions of their own and are not counted):
     scratch loads   scratch_load_* instructions
@@ -60,9 +64,14 @@ def writes_vgprs(op, ops):
     return set()
 
 
-def scan(disasm, kernel):
+def scan(disasm, kernel, src_range=None):
     """{function: dict(instructions, scratch_loads, trips, fed=[(source line, instruction, reload)], trip_lines=Counter, load_lines=Counter)}
-    for every function of the disassembly (llvm-objdump -d [-l] --symbolize-operands) whose symbol contains `kernel`"""
+    for every function of the disassembly (llvm-objdump -d [-l] --symbolize-operands) whose symbol contains `kernel`.
+    src_range = (file name, first line, last line): count only the instructions the line table (-l) attributes to that range - a trip where
+    its wait stands, a fed exchange where the exchange stands; what is outstanding or reloaded is still followed through the whole function."""
+    def inside(ln):
+        return src_range is None or (ln is not None and ln[0] == src_range[0] and src_range[1] <= ln[1] <= src_range[2])
+
     res = {}
     cur = st = None
     line = None
@@ -84,23 +93,25 @@ def scan(disasm, kernel):
         if not m or st is None:
             continue
         op, ops = m.group(1), operands(m.group(2))
-        st["instructions"] += 1
+        counted = inside(line)
+        st["instructions"] += counted
         bucket = (line[0], line[1] // 20 * 20) if line else None
         if is_lane_exchange(op):
             for o in ops[1:]:
                 hit = [reloaded[r] for r in vgprs(o) if r in reloaded]
                 if hit:
-                    st["fed"].append((line, l.strip(), hit[0]))
+                    if counted:
+                        st["fed"].append((line, l.strip(), hit[0]))
                     break
         if op == "s_waitcnt" and "vmcnt" in m.group(2) and outstanding:
-            st["trips"] += 1
-            st["trip_lines"][bucket] += 1
+            st["trips"] += counted
+            st["trip_lines"][bucket] += counted
             outstanding = 0
         for r in writes_vgprs(op, ops):
             reloaded.pop(r, None)
         if op.startswith("scratch_load"):
-            st["scratch_loads"] += 1
-            st["load_lines"][bucket] += 1
+            st["scratch_loads"] += counted
+            st["load_lines"][bucket] += counted
             outstanding += 1
             for r in vgprs(ops[0]):
                 reloaded[r] = l.strip()
@@ -113,16 +124,31 @@ def disassemble(co, lines=False):
     return subprocess.check_output([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", "--symbolize-operands"] + (["-l"] if lines else []) + [co], text=True)
 
 
+def parse_range(text):
+    """'solve_kernel.hpp:466:748' -> ('solve_kernel.hpp', 466, 748)"""
+    f, lo, hi = text.rsplit(":", 2)
+    return os.path.basename(f), int(lo), int(hi)
+
+
+def disassemble_with_lines(src, defs):
+    """the line-table build of scripts/isa_lines.py (the Makefile's flags plus -gline-tables-only), disassembled with source lines"""
+    from isa_lines import build
+    return disassemble(build(src, defs), True)
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--lines"]
-    lines = "--lines" in sys.argv
+    argv, src_range = sys.argv[1:], None
+    if "--range" in argv:
+        i = argv.index("--range")
+        src_range = parse_range(argv[i + 1])
+        del argv[i:i + 2]
+    args = [a for a in argv if a != "--lines"]
+    lines = "--lines" in argv or src_range is not None
     src, kernel, defs = args[0], args[1], args[2:]
-    if lines:
-        from isa_lines import build
-        co = build(src, defs)
-    else:
-        co = build_co(src, defs)
-    for f, st in scan(disassemble(co, lines), kernel).items():
+    disasm = disassemble_with_lines(src, defs) if lines else disassemble(build_co(src, defs))
+    if src_range:
+        print("only %s:%d..%d" % src_range)
+    for f, st in scan(disasm, kernel, src_range).items():
         print("%s: instructions %d, scratch loads %d, reload trips %d, lane exchanges fed by a reload %d" % (
             f, st["instructions"], st["scratch_loads"], st["trips"], len(st["fed"])))
         for ln, insn, rel in st["fed"][:20]:
